@@ -4,16 +4,23 @@ GANOptimizer.__call__, loss.py:120-134) at 256x256, bs = 8 per GPU, fp32, synthe
 (BASELINE.json configs[1]; configs[3] when launched on 8 GPUs).
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the --steps training steps and prints the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...); roofline, cpu_baseline and extra are null.  With --full it also carries
   roofline:     achieved TFLOP/s (algorithmic fp32 FLOPs) of the dominant kernel and of the whole matrix-core family (csrc/gemm_core.h,
                 conv3x3.h, attention.hip), measured with events on the launch stream around every launch of one extra (untimed)
                 training step.  The family computes every fp32 product as SIX bf16 MFMAs on exact three-way bf16 splits of both
                 operands (csrc/x6.h), so its ceiling is the dense bf16 matrix peak / 6 = 419.4 TFLOP/s of fp32-equivalent work
                 (the 157.3 TFLOP/s fp32-MFMA peak the round-1 kernels were priced against is reported next to it);
   cpu_baseline: the CPU restatement (oracle/picnet_cpu.py, kind "port") timed on this host's cores on a bounded
-                sample of the same workload.
+                sample of the same workload;
+  extra:        the C3 / C5 train_psp legs of bench_psp.py (N = 1 only).
+
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs) as DIR/<name>.npy; the inputs, the initial weights
+and the random draws of the step are seeded, so that two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -103,12 +110,37 @@ def synthetic(n, size, seed, dev):
 
 
 def train_step(G, D, gopt, batch):
+    """one training step; returns (generated image, (D_loss, G_loss, perc_loss, style_loss, cx_loss))"""
     from face_mask_inpaint_amd import functional as FF
 
     src, ref, gt, mask = batch
     m = FF.binarise_mask(mask)                      # train_reference_fill.py:340
     gen = G(src, ref, src_mask=m)                   # :342 (fresh N(0,1) draws for rsample)
-    return gopt(D, src, gt, ref, gen, m)            # :344-346
+    return gen.detach(), gopt(D, src, gt, ref, gen, m)  # :344-346
+
+
+LOSS_NAMES = ("d_loss", "g_loss", "perc_loss", "style_loss", "cx_loss")
+DUMP_MAX = {"gen": 1 << 22, "G_params": 1 << 21, "D_params": 1 << 21}  # values written per array at most (<= 32 MB in all)
+
+
+def dump_outputs(out_dir, G, D, gen, losses):
+    """the outputs of the last timed step as float32 .npy files: the five losses gopt returns (0-d), the generated image gen
+    (N, 3, H, W) and the parameters of G and D after the step's optimiser updates (all parameters in registration order, flattened
+    and concatenated).  An array with more than DUMP_MAX values is written as a fixed seeded sample: the values at the same sorted
+    random positions of its flattened form in every run (at the default size only G_params is sampled; ~21 MB in all)"""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {name: l.detach() for name, l in zip(LOSS_NAMES, losses)}
+    arrays["gen"] = gen
+    arrays["G_params"] = torch.cat([p.detach().reshape(-1) for p in G.parameters()])
+    arrays["D_params"] = torch.cat([p.detach().reshape(-1) for p in D.parameters()])
+    for name, t in arrays.items():
+        k = DUMP_MAX.get(name)
+        if k is not None and t.numel() > k:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def host_cores() -> int:
@@ -206,11 +238,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=8, help="images per GPU (weak scaling)")
     ap.add_argument("--size", type=int, default=256)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C3 / C5 pSp legs appended as 'extra' (N = 1 only)")
-    ap.add_argument("--profile-dump", default=None, help="write the per-shape launch table of the profiled step here")
+    ap.add_argument("--full", action="store_true", help="also the roofline (one extra profiled step), the CPU baseline and the C3 / C5 'extra' legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the profiled roofline step")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the C3 / C5 pSp legs appended as 'extra' (N = 1 only)")
+    ap.add_argument("--profile-dump", default=None, help="with --full: write the per-shape launch table of the profiled step here")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.profile_dump and (not args.full or args.no_roofline):
+        ap.error("--profile-dump comes from the profiled roofline step: it needs --full (without --no-roofline)")
+    do_roofline = args.full and not args.no_roofline
 
     from face_mask_inpaint_amd import launch
 
@@ -250,7 +289,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        losses = train_step(G, D, gopt, batch)
+        gen, losses = train_step(G, D, gopt, batch)
     sync()
     dt = time.perf_counter() - t0
     if world > 1:
@@ -260,12 +299,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     assert all(torch.isfinite(l).item() for l in losses), "non-finite loss"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, G, D, gen, losses)
+    del gen
 
     roofline = None
-    if not args.no_roofline and rank != 0:
+    if do_roofline and rank != 0:
         train_step(G, D, gopt, batch)  # the profiled step is a collective step: every rank takes part, rank 0 records
         torch.cuda.synchronize()
-    if not args.no_roofline and rank == 0:
+    if do_roofline and rank == 0:
         FF.PROFILE = []
         train_step(G, D, gopt, batch)
         torch.cuda.synchronize()
@@ -323,10 +365,10 @@ def main():
                                      for k, v in top[:7]}}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.size)
     extra = None
-    if rank == 0 and world == 1 and not args.no_extra:
+    if args.full and rank == 0 and world == 1 and not args.no_extra:
         # BASELINE configs[2] (C3) and the single-GPU leg of configs[4] (C5), so that the driver's fixed command times them too
         del G, D, gopt, batch
         torch.cuda.empty_cache()
@@ -340,7 +382,7 @@ def main():
         mine = torch.tensor([getattr(o, "collectives", 0) for o in (gopt.optimizer_G, gopt.optimizer_D)], device=dev, dtype=torch.int64)
         allc = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allc, mine)
-        collectives = {"per_rank_G_D_over_%d_steps" % (args.steps + args.warmup + (0 if args.no_roofline else 1)): [c.tolist() for c in allc]}
+        collectives = {"per_rank_G_D_over_%d_steps" % (args.steps + args.warmup + (1 if do_roofline else 0)): [c.tolist() for c in allc]}
 
     if rank == 0:
         imgs = args.batch * world * args.steps

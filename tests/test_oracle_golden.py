@@ -5,6 +5,7 @@ import pytest
 
 from oracle import picnet_cpu as O
 
+pytestmark = pytest.mark.usefixtures("golden_threads")
 TOL = dict(rtol=1e-5, atol=1e-6)
 
 

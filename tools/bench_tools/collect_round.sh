@@ -34,6 +34,6 @@ json.dump(res, open(os.path.join(root, "gpurun_out", tag + "_pmc_bf16_conv.json"
 print("pmc bf16 conv:", len(res["FETCH_SIZE"]), "kernels")
 PY
 cd $root
-python3 bench.py --steps 10 --warmup 3 --profile-dump gpurun_out/${tag}_shapes.txt > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err
+python3 bench.py --full --steps 10 --warmup 3 --profile-dump $out/${tag}_shapes.txt > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 python3 bench_psp.py > gpurun_out/${tag}_bench_psp.json 2> gpurun_out/${tag}_bench_psp.err
 tail -c 600 gpurun_out/${tag}_bench.json
