@@ -378,9 +378,7 @@ extern "C" int fmi_attention_fwd_f32(const float* q, const float* v1, const floa
                                      int N, int T, int D, int C1, int C2, void* stream) {
   if (!q || !v1 || !o1 || N <= 0 || T <= 0 || C1 <= 0 || C2 < 0 || (C2 > 0 && (!v2 || !o2))) return FMI_ERR_BAD_ARG;
   if (T % 128 != 0 || C1 % 32 != 0 || C2 % 32 != 0 || N > 65535) return FMI_ERR_UNSUPPORTED;
-  static const int nw_dbg = getenv("FMI_ATT_NW") ? atoi(getenv("FMI_ATT_NW")) : 0;  // debug: force 2 / 4 / 8 waves per workgroup
-  int nw = (T % 256 == 0 && (int64_t)(T / 256) * N >= 256) ? 8 : ((int64_t)(T / 128) * N < 256 ? 2 : 4);
-  if (nw_dbg == 2 || nw_dbg == 4 || (nw_dbg == 8 && T % 256 == 0)) nw = nw_dbg;
+  const int nw = (T % 256 == 0 && (int64_t)(T / 256) * N >= 256) ? 8 : ((int64_t)(T / 128) * N < 256 ? 2 : 4);
   if ((((uintptr_t)q | (uintptr_t)v1 | (uintptr_t)v2 | (uintptr_t)o1 | (uintptr_t)o2) & 15) != 0) return FMI_ERR_BAD_ARG;
   const int nct = (C1 + C2) / 32;
   const dim3 grid(T / (nw * 32), N), block(nw * 64);
@@ -838,11 +836,9 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_kernel(const float* __restri
 //  * the query-side tiles of the four key blocks are summed in LDS (ds_add_f32) before the global atomics, as before.
 // Per query tile and wave: 264 bf16 MFMAs (8 448 matrix-pipe cycles; the fp32 kernel: 352 MFMAs, 22 528 cycles).
 // =====================================================================================================
-// DVLO, DVN: the value-channel tiles (32 channels each) whose dV this launch accumulates; FULL: also dP, dS, dK and both dQ terms.
 // With all 8 channel tiles in one launch the 128 dV + 32 dK accumulator registers leave no room for the V pieces (192 registers): V stays
-// fp32 and is split per tile (700 VALU instructions of ~2 400).  Two launches -- FULL with tiles 0..3, then a light one (S, P and dV of tiles
-// 4..7 only: no V, no dP, no atomics) -- cost 288 instead of 264 MFMAs per tile pair, but the first then holds 96 accumulator registers and
-// the optimiser keeps the V pieces across query tiles.
+// fp32 and is split per tile (700 VALU instructions of ~2 400).  (A two-launch form that kept the V pieces in registers -- 288 instead of
+// 264 MFMAs per tile pair -- measured 14.9 + 5.6 ms against 17.6 ms for the single launch.)
 #ifdef FMI_ATT_STAMP  // diagnostic build only (tools/bench_tools/build_flags.sh attstamp -DFMI_ATT_STAMP): cycle stamps of the phases of ONE query tile
 __device__ unsigned long long fmi_att_stamps[16];
 extern "C" int fmi_debug_attn_stamps(unsigned long long* host16) {
@@ -850,22 +846,20 @@ extern "C" int fmi_debug_attn_stamps(unsigned long long* host16) {
 }
 #define ATT_STAMP(i)                                                                                   \
   do {                                                                                                 \
-    if (blockIdx.x == 0 && blockIdx.y == 0 && i0 == 32 * 100 && wid == 0 && lane == 0 && FULL)          \
+    if (blockIdx.x == 0 && blockIdx.y == 0 && i0 == 32 * 100 && wid == 0 && lane == 0)                   \
       fmi_att_stamps[i] = __builtin_amdgcn_s_memtime();                                                \
   } while (0)
 #else
 #define ATT_STAMP(i)
 #endif
-template <int D, int NCT, int DVLO, int DVN, bool FULL>
+template <int D, int NCT>
 __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __restrict__ q, const float* __restrict__ v1,
                                                               const float* __restrict__ v2, const float* __restrict__ g1,
                                                               const float* __restrict__ g2, const float* __restrict__ lse,
                                                               const float* __restrict__ delta, float* __restrict__ gv1,
                                                               float* __restrict__ gv2, float* __restrict__ gq, int T, int C1, int C2, int kb0) {
   constexpr int CT = NCT * 32, LDQ = D + 1, NDT = D / 32;
-  constexpr int GLO = FULL ? 0 : DVLO * 32, GN = FULL ? CT : DVN * 32;   // gO channels staged per query tile
-  constexpr int HOIST_V = FULL && 2 * DVN <= NCT;                        // room for the V pieces in registers
-  constexpr int NQL = (8 * D) / 256 > 0 ? (8 * D) / 256 : 1, NVL = (8 * GN) / 256;
+  constexpr int NQL = (8 * D) / 256 > 0 ? (8 * D) / 256 : 1, NVL = (8 * CT) / 256;
   constexpr int GP = 2 * CT, GIMG = 32 * GP;   // gO piece image: row pitch, bytes per piece
   constexpr int QP = 192, QIMG = 32 * QP;      // Q piece image
   constexpr int TIMG = 32 * 64;                // dS^T piece image: [32 keys][32 q] bf16
@@ -907,21 +901,19 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __res
     *reinterpret_cast<uint2*>(d + 2 * KIMG) = make_uint2(a2, b2);
   }
   // B fragments of this wave's keys, V[key = l31][16 kk + 8 lh + j], in registers (the K fragments are read from the piece image per tile)
-  float vfrag[FULL ? CT / 16 : 1][8];
-  if constexpr (FULL) {
+  float vfrag[CT / 16][8];
 #pragma unroll
-    for (int kk = 0; kk < CT / 16; ++kk) {
-      const int c = 16 * kk + 8 * lh;
-      const float* src = (c < C1) ? v1b + (int64_t)(j0 + l31) * C1 + c : v2b + (int64_t)(j0 + l31) * C2 + (c - C1);
-      const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
-      vfrag[kk][0] = a.x, vfrag[kk][1] = a.y, vfrag[kk][2] = a.z, vfrag[kk][3] = a.w;
-      vfrag[kk][4] = b.x, vfrag[kk][5] = b.y, vfrag[kk][6] = b.z, vfrag[kk][7] = b.w;
-    }
+  for (int kk = 0; kk < CT / 16; ++kk) {
+    const int c = 16 * kk + 8 * lh;
+    const float* src = (c < C1) ? v1b + (int64_t)(j0 + l31) * C1 + c : v2b + (int64_t)(j0 + l31) * C2 + (c - C1);
+    const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
+    vfrag[kk][0] = a.x, vfrag[kk][1] = a.y, vfrag[kk][2] = a.z, vfrag[kk][3] = a.w;
+    vfrag[kk][4] = b.x, vfrag[kk][5] = b.y, vfrag[kk][6] = b.z, vfrag[kk][7] = b.w;
   }
 
-  f32x16 acc_dv[DVN], acc_dk[NDT];
+  f32x16 acc_dv[NCT], acc_dk[NDT];
 #pragma unroll
-  for (int c = 0; c < DVN; ++c)
+  for (int c = 0; c < NCT; ++c)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc_dv[c][r] = 0.f;
 #pragma unroll
@@ -941,12 +933,12 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __res
 #pragma unroll
     for (int i = 0; i < NVL; ++i) {
       const int f = tid + 256 * i;
-      const int row = f / (GN / 4), c = GLO + (f % (GN / 4)) * 4;
+      const int row = f / (CT / 4), c = (f % (CT / 4)) * 4;
       rg[i] = (c < C1) ? *reinterpret_cast<const float4*>(g1b + (int64_t)(i0 + row) * C1 + c)
                        : *reinterpret_cast<const float4*>(g2b + (int64_t)(i0 + row) * C2 + (c - C1));
     }
     rl = lseb[i0 + (tid & 31)];
-    if constexpr (FULL) rd = delb[i0 + (tid & 31)];
+    rd = delb[i0 + (tid & 31)];
   };
   auto swz = [](int row) { return ((row & 3) << 2) | ((row >> 2) & 3); };
   auto lstore = [&]() {
@@ -966,7 +958,7 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __res
 #pragma unroll
     for (int i = 0; i < NVL; ++i) {
       const int f = tid + 256 * i;
-      const int row = f / (GN / 4), c4 = GLO / 4 + f % (GN / 4), ch = c4 >> 1;
+      const int row = f / (CT / 4), c4 = f % (CT / 4), ch = c4 >> 1;
       uint32_t a0, a1, a2, b0, b1, b2;
       split3_pair(rg[i].x, rg[i].y, a0, a1, a2);
       split3_pair(rg[i].z, rg[i].w, b0, b1, b2);
@@ -1075,7 +1067,7 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __res
       for (int pc = 0; pc < 3; ++pc)
         a[pc] = tr2_nowait(g_tr + (uint32_t)(pc * GIMG + 16 * s * GP) + ch0, g_tr + (uint32_t)(pc * GIMG + (16 * s + 8) * GP) + ch1);
     };
-    if constexpr (FULL) {
+    {
       // ---- P first (it needs S only), then ONE loop over the channel steps that carries both products whose reduction runs over the
       // channels / whose output is channels: dP[q][key] += gO[q][c] V[key][c] (step kk: 16 channels; the V pieces are split per step,
       // ~45 VALU instructions) and dV^T[c][key] += gO^T[c][q] P[q][key] (step j = kk: one 32-channel tile of one 16-query half; no VALU).
@@ -1111,14 +1103,12 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __res
       // accumulators take 192 of the 256 AGPRs, so half of the V fragments live in VGPRs ("+v") and half in the remaining AGPRs ("+a";
       // with "+v" on all of them each use cost a v_accvgpr_read AND a v_accvgpr_write back)
       auto v_touch = [&](int kk) {
-        if constexpr (!HOIST_V) {
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            if (kk < (CT / 16) / 2)
-              asm volatile("" : "+v"(vfrag[kk][j]));
-            else
-              asm volatile("" : "+a"(vfrag[kk][j]));
-          }
+        for (int j = 0; j < 8; ++j) {
+          if (kk < (CT / 16) / 2)
+            asm volatile("" : "+v"(vfrag[kk][j]));
+          else
+            asm volatile("" : "+a"(vfrag[kk][j]));
         }
       };
       auto ds_make = [&](int s, bf16x8_t (&ds)[3]) {
@@ -1141,7 +1131,7 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __res
             aq[c][pc] = tr2_nowait(q_tr + (uint32_t)(pc * QIMG + 16 * s * QP + 64 * c), q_tr + (uint32_t)(pc * QIMG + (16 * s + 8) * QP + 64 * c));
       };
       bf16x8_t aq0[NDT][3], aq1[NDT][3], ds0[3], ds1[3];
-      constexpr int NDP = CT / 16, NDV = 2 * DVN;   // NDV <= NDP: the dV step of the tile (s, c) = (j / DVN, j % DVN) rides on dP step j
+      constexpr int NDP = CT / 16, NDV = 2 * NCT;   // NDV <= NDP: the dV step of the tile (s, c) = (j / NCT, j % NCT) rides on dP step j
       static_assert(NDV <= NDP, "dV steps ride on the dP steps");
       // A step has two halves of six MFMAs.  First half: dP with the fragments a (gO rows) and b (V pieces) made during the step before;
       // the gO^T fragment t of this step's dV tile is read at its start.  Second half: dV with t; a is dead by then and receives the gO
@@ -1159,7 +1149,7 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __res
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int kk = 0; kk < NDP; ++kk) {
-        if (kk < NDV) gt_frag(kk / DVN, DVLO + kk % DVN, t);
+        if (kk < NDV) gt_frag(kk / NCT, kk % NCT, t);
         if (kk + 1 < NDP) {
           v_touch(kk + 1);
           v_split_half(kk + 1, 0, wn);
@@ -1177,7 +1167,7 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __res
           g_frag(kk + 1, a);
           v_split_half(kk + 1, 1, wn);
         }
-        if (kk < NDV) acc_dv[kk < NDV ? kk % DVN : 0] = mfma_x6(t, pp[kk < NDV ? kk / DVN : 0], acc_dv[kk < NDV ? kk % DVN : 0]);
+        if (kk < NDV) acc_dv[kk < NDV ? kk % NCT : 0] = mfma_x6(t, pp[kk < NDV ? kk / NCT : 0], acc_dv[kk < NDV ? kk % NCT : 0]);
 #pragma unroll
         for (int g = 0; g < 6; ++g) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -1225,38 +1215,8 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __res
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
-    } else {
-      // ---- second pass over the other channels: P, then dV^T[c][key] += gO^T[c][q] P[q][key] alone
-    ATT_STAMP(2);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sp[r] = __expf(sp[r] - lse_i[(r & 3) + 8 * (r >> 2) + 4 * lh]);
-    ATT_STAMP(3);
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        bf16x8_t pp[3];
-        const float f[8] = {sp[8 * s], sp[8 * s + 1], sp[8 * s + 2], sp[8 * s + 3], sp[8 * s + 4], sp[8 * s + 5], sp[8 * s + 6], sp[8 * s + 7]};
-        split3_bf16(f, pp);
-        bf16x8_t a[3], an[3];
-        gt_frag(s, DVLO, a);
-        pin3(a);
-#pragma unroll
-        for (int j = 0; j < DVN; ++j) {  // fragment j + 1 is read before the MFMAs of fragment j are issued and pinned after them
-          if (j + 1 < DVN) gt_frag(s, DVLO + j + 1, an);
-          __builtin_amdgcn_sched_barrier(0);  // the scheduler otherwise sinks the reads below the MFMAs, right in front of their wait
-          acc_dv[j] = mfma_x6(a, pp, acc_dv[j]);
-          __builtin_amdgcn_sched_barrier(0);
-          if (j + 1 < DVN) pin3(an);
-#pragma unroll
-          for (int pc = 0; pc < 3; ++pc) a[pc] = an[pc];
-        }
-      }
     }
-    if constexpr (!FULL) {
-    ATT_STAMP(4);
-      __builtin_amdgcn_sched_barrier(0);
-      gload(i0 + 32 < T ? i0 + 32 : i0);
-    }
-    if constexpr (FULL) {
+    {
       // ---- query side: dQ[q][d] = dS[q][key] K[key][d] for this wave's keys
     ATT_STAMP(5);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the transposed image was written by this wave; a wave's LDS operations complete in order
@@ -1325,9 +1285,6 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __res
         for (int w = 0; w < 4; ++w) sum += part[rr][w];
         atomicAdd(gq + ((int64_t)n * T + i0 + (r & 3) + 8 * (r >> 2) + 4 * lh) * D + c * 32 + l31, sum);
       }
-    } else {
-      __syncthreads();   // every wave is done with the query tile
-      lstore();
     }
     __syncthreads();
     ATT_STAMP(11);
@@ -1340,15 +1297,15 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __res
   // ---- epilogue: dV rows of this wave's keys (plain stores) and the key-side dQ (atomics)
   const int64_t row = (int64_t)n * T + j0 + l31;
 #pragma unroll
-  for (int c = 0; c < DVN; ++c) {
-    const int ch = (DVLO + c) * 32;
+  for (int c = 0; c < NCT; ++c) {
+    const int ch = c * 32;
     float* ob = (ch < C1) ? gv1 + row * C1 + ch : gv2 + row * C2 + (ch - C1);
 #pragma unroll
     for (int g = 0; g < 4; ++g)
       *reinterpret_cast<float4*>(ob + 8 * g + 4 * lh) = make_float4(acc_dv[c][4 * g], acc_dv[c][4 * g + 1], acc_dv[c][4 * g + 2], acc_dv[c][4 * g + 3]);
   }
 #pragma unroll
-  for (int c = 0; c < (FULL ? NDT : 0); ++c) {
+  for (int c = 0; c < NDT; ++c) {
     float* gqb = gq + row * D + c * 32;
 #pragma unroll
     for (int r = 0; r < 16; ++r) atomicAdd(gqb + (r & 3) + 8 * (r >> 2) + 4 * lh, acc_dk[c][r]);
@@ -1388,9 +1345,8 @@ extern "C" int fmi_attention_bwd_f32(const float* q, const float* v1, const floa
   // reproducible mode: the query-side tiles of dQ receive one atomic contribution per KEY BLOCK; launching the key blocks one after the
   // other (stream order) fixes the order of those additions -- same kernels, grid.x = 1, key-block offset as an argument
   const bool det = fmi_det();
-  static const int bwd_dbg = getenv("FMI_ATT_BWD") ? atoi(getenv("FMI_ATT_BWD")) : 0;  // debug: 1 / 2 force a structure
   const bool small = (int64_t)(T / 128) * N < 128;  // short sequences: the first structure has 4x the workgroups
-  if (T % 128 == 0 && bwd_dbg != 1 && (bwd_dbg == 2 || !small)) {  // second structure: one key block per wave, fragments in registers, 4x fewer atomics
+  if (T % 128 == 0 && !small) {  // second structure: one key block per wave, fragments in registers, 4x fewer atomics
     const dim3 grid2(T / 128, N);
     auto lds2 = [](int d, int ct) {
       return sizeof(float) * (size_t)(32 * (ct + 1) + 32 * (d + 1) + 64 + 4 * 32 * (d + 1) + 4 * 32 * 33 + 4 * (d / 32) * 16 * 64);
@@ -1398,31 +1354,19 @@ extern "C" int fmi_attention_bwd_f32(const float* q, const float* v1, const floa
     auto lds2x = [](int d, int ct) {
       return (size_t)(3 * 32 * 2 * ct + 3 * 32 * 192 + 64 * 4 + 4 * 3 * 32 * (2 * d + 16) + 4 * ((d / 32) * 4096 > 6144 ? (d / 32) * 4096 : 6144));
     };
-    // two launches (dV of channel tiles 0..3 with everything else, then a light S / P / dV launch for tiles 4..7) let the first keep the V
-    // pieces in registers: measured 14.9 + 5.6 ms against 17.6 ms for the single launch -- off unless FMI_ATT_BWD_2PASS is set
-    static const bool one_pass = getenv("FMI_ATT_BWD_2PASS") == nullptr;
-#define ATTB2_X6(DD, NN, LO, CNT, FULLP)                                                                                 \
-  do {                                                                                                                   \
-    static fmi_attr_flags attr_setx{}; int attr_setx_dev;\
-    if (fmi_attr_needed(attr_setx, attr_setx_dev)) {                                                                                                    \
-      if (hipFuncSetAttribute((const void*)attn_bwd2_x6_kernel<DD, NN, LO, CNT, FULLP>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)lds2x(DD, NN * 32)) != hipSuccess)                                                    \
-        return FMI_ERR_LAUNCH;                                                                                           \
-      fmi_attr_mark(attr_setx, attr_setx_dev);                                                                                                  \
-    }                                                                                                                    \
-    for (int kb = 0; kb < (det ? (int)grid2.x : 1); ++kb)                                                                \
-      hipLaunchKernelGGL((attn_bwd2_x6_kernel<DD, NN, LO, CNT, FULLP>), det ? dim3(1, grid2.y) : grid2, block, lds2x(DD, NN * 32), st, q, v1, v2, go1, go2, lse, \
-                         (const float*)delta_scratch, gv1, gv2, gq_zeroed, T, C1, C2, kb);                                \
-  } while (0)
 #define ATTB2_LAUNCH(DD, NN)                                                                                             \
   do {                                                                                                                   \
     if (FMI_X6) {                                                                                                        \
-      if (NN == 8 && !one_pass) {                                                                                        \
-        ATTB2_X6(DD, NN, 0, NN / 2, true);                                                                               \
-        ATTB2_X6(DD, NN, NN / 2, NN / 2, false);                                                                         \
-      } else {                                                                                                           \
-        ATTB2_X6(DD, NN, 0, NN, true);                                                                                   \
+      static fmi_attr_flags attr_setx{}; int attr_setx_dev;\
+      if (fmi_attr_needed(attr_setx, attr_setx_dev)) {                                                                   \
+        if (hipFuncSetAttribute((const void*)attn_bwd2_x6_kernel<DD, NN>, hipFuncAttributeMaxDynamicSharedMemorySize,    \
+                                (int)lds2x(DD, NN * 32)) != hipSuccess)                                                  \
+          return FMI_ERR_LAUNCH;                                                                                         \
+        fmi_attr_mark(attr_setx, attr_setx_dev);                                                                         \
       }                                                                                                                  \
+      for (int kb = 0; kb < (det ? (int)grid2.x : 1); ++kb)                                                              \
+        hipLaunchKernelGGL((attn_bwd2_x6_kernel<DD, NN>), det ? dim3(1, grid2.y) : grid2, block, lds2x(DD, NN * 32), st, q, v1, v2, go1, go2, \
+                           lse, (const float*)delta_scratch, gv1, gv2, gq_zeroed, T, C1, C2, kb);                        \
       return fmi_launch_status();                                                                                        \
     }                                                                                                                    \
     static fmi_attr_flags attr_set2{}; int attr_set2_dev;\
@@ -1442,7 +1386,6 @@ extern "C" int fmi_attention_bwd_f32(const float* q, const float* v1, const floa
     if (D == 32 && nct == 4) ATTB2_LAUNCH(32, 4);
     if (D == 64 && nct == 4) ATTB2_LAUNCH(64, 4);
 #undef ATTB2_LAUNCH
-#undef ATTB2_X6
   }
   const dim3 grid(T / 32, N);
   auto lds_bytes = [](int d, int ct) { return sizeof(float) * (size_t)(2 * 32 * (ct + 1) + 2 * 32 * (d + 1) + 64 + 4 * 2 * 1024 + 2 * 32 * 33); };

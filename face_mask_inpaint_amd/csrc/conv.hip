@@ -6,9 +6,9 @@
 #include "convt3x3.h"
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-static bool ep_scalar() {  // debug: FMI_EP_SCALAR = never use the 16-byte epilogue (read once)
-  static const bool v = getenv("FMI_EP_SCALAR") != nullptr;
-  return v;
+// the 16-byte epilogue: Nout % 4 == 0, 16-byte rows, every tensor it touches 16-byte aligned
+static int ep_vec(const ConvEp& ep, int Nout) {
+  return Nout % 4 == 0 && ep.cstride % 4 == 0 && aligned16(ep.y) && aligned16(ep.bias) && aligned16(ep.res) && aligned16(ep.mask);
 }
 
 static int check_desc(const fmi_conv_desc* d) {
@@ -42,6 +42,27 @@ static ConvGeom fwd_geom(const fmi_conv_desc* d, const float* x, int n_eff) {
   return g;
 }
 
+// adjoint-geometry gather of sub-pixel phase (py, px): anchors = the pixels of dx congruent to (py, px) modulo the stride, taps = the
+// kernel taps that reach them (none: nty = 0, ntx = 1, an empty reduction)
+static ConvGeom adj_geom(const fmi_conv_desc* d, const float* dy, int n_eff, int py, int px) {
+  const int s = d->stride, dl = d->dil > 1 ? d->dil : 1;
+  ConvGeom g{};
+  g.N = n_eff; g.IH = d->OH; g.IW = d->OW; g.C = d->K; g.cstride = d->y_cstride;
+  g.GH = (d->H - py + s - 1) / s; g.GW = (d->W - px + s - 1) / s; g.S = 1;
+  g.kh0 = (py + d->pad) % s; g.kw0 = (px + d->pad) % s;
+  g.nty = g.kh0 < d->kh ? (d->kh - g.kh0 + s - 1) / s : 0;
+  g.ntx = g.kw0 < d->kw ? (d->kw - g.kw0 + s - 1) / s : 0;
+  g.dy0 = (py + d->pad - g.kh0) / s; g.dx0 = (px + d->pad - g.kw0) / s;
+  g.ystep = -dl; g.xstep = -dl; g.khstep = s; g.kwstep = s; g.kw = d->kw;  // dl > 1 only with s == 1 (the caller checks)
+  g.pad_mode = 0;
+  g.vec = (d->K % 4 == 0) && (d->y_cstride % 4 == 0) && aligned16(dy);
+  g.dGW = make_fastdiv(g.GW); g.dG = make_fastdiv(g.GH * g.GW); g.dC = make_fastdiv(g.C);
+  g.dntx = make_fastdiv(g.ntx > 0 ? g.ntx : 1);
+  g.img_bs = (int64_t)d->OH * d->OW * d->y_cstride;
+  if (g.nty == 0 || g.ntx == 0) { g.nty = 0; g.ntx = 1; }
+  return g;
+}
+
 #ifndef FMI_HOST_EMU
 // y[pixel][k] = bias[k] + residual[pixel][k] (either may be null): first pass of a split-reduction convolution
 __global__ void __launch_bounds__(256) conv_split_init_kernel(float* __restrict__ y, const float* __restrict__ bias,
@@ -65,8 +86,6 @@ static int conv_ksplit(int64_t M, int N, int K) {
   // keep the 128-wide tiles (operand reuse) and fill the chip by splitting the reduction instead of shrinking the tile
   const int64_t tiles = ceil_div64(M, 128) * ceil_div64(N, N <= 32 ? 32 : (N <= 64 ? 64 : 128));
   if (K < 512 || fmi_det()) return 1;  // reproducible mode: no split reduction (partial sums would meet through atomics)
-  static const int ks_dbg = getenv("FMI_KS") ? atoi(getenv("FMI_KS")) : 0;  // experiment: force the split
-  if (ks_dbg > 0) return ks_dbg;
   if (tiles >= 320) {
     // between one and two "waves" of workgroups (3 per CU x 256 CUs) the CUs that got 3 tiles set the time while the others idle
     // (VGG 28^2: 588 tiles = 2.3 per CU): splitting the work unit lets the dispatcher even it out.  Measured (TFLOP/s, split 1 / 2 / 3):
@@ -87,92 +106,56 @@ static int conv_ksplit(int64_t M, int N, int K) {
 #endif
 }
 
-// y3_done: set by a path whose own launch wrote the requested piece image d->y3 (none does today: an 8-byte-per-lane epilogue form was
-// measured at 1.7 TB/s, slower than the separate fmi_split3_f32 pass the caller runs otherwise)
-static int fwd_impl(const fmi_conv_desc* d, const float* x, const float* wf, const float* bias, const float* residual, float* y, int act,
-                    int batch_w, int64_t w_bstride, void* stream, bool* y3_done) {
-  int rc = check_desc(d);
-  if (rc) return rc;
-  if (!x || !wf || !y || batch_w < 1 || act < 0 || act > 2) return FMI_ERR_BAD_ARG;
-  if (batch_w > 1 && batch_w != d->N) return FMI_ERR_BAD_ARG;
-#ifndef FMI_HOST_EMU
-  if (batch_w == 1 && fmi_conv2d_thin_supported(d) && aligned16(x))
-    return fmi_conv2d_thin_fwd_f32(d, x, wf, bias, residual, y, act, stream);
-#endif
-  const int n_eff = batch_w > 1 ? 1 : d->N;
-  ConvGeom g = fwd_geom(d, x, n_eff);
+// One output phase: the forward convolution, or one sub-pixel phase of the adjoint (flip = 1: the 3x3 tap-reuse kernels take the
+// flipped taps of the adjoint's weight pack).  g gathers x (g.C channels at pitch g.cstride; x3 = its bf16 piece image or null); w / w3 =
+// the weights packed for this direction and their piece image (null where it cannot be used); ep writes Nout channels.  may_split: the
+// reduction may be split over workgroups, whose partial sums meet through atomics in an output initialised first; shared_init: the caller
+// has initialised the output once for all phases (the adjoint's strided split) and this phase only adds to it.
+static int conv_phase(const fmi_conv_desc* d, const ConvGeom& g, const float* x, const void* x3, const float* w, const void* w3p,
+                      int64_t w_bstride, int Nout, int flip, ConvEp ep, int batch_w, bool may_split, bool shared_init, hipStream_t st) {
   ConvK la{x, g};
-  ConvWX lb{wf, g, w_bstride, d->K, (d->K % 4 == 0) && aligned16(wf) && (w_bstride % 4 == 0)};
+  ConvWX lb{w, g, w_bstride, Nout, (Nout % 4 == 0) && aligned16(w) && (w_bstride % 4 == 0)};
+  const int ks = may_split ? conv_ksplit(g.Mdim(), Nout, g.Kdim()) : 1;
 #ifndef FMI_HOST_EMU
-  // bf16 piece images of the weights (fmi_weight_prepare_f32 writes them): [3][taps][C / 8][K][8]
-  const uint16_t* w3 = (FMI_X6 && batch_w == 1 && d->C % 16 == 0 && aligned16(d->w3)) ? (const uint16_t*)d->w3 : nullptr;
-#endif
-  ConvEp ep{y, bias, residual, d->OH, d->OW, 1, 0, 0, d->OH, d->OW, d->y_cstride, act, g.dGW, g.dG,
-            (int64_t)d->OH * d->OW * d->y_cstride};
-  ep.vec = !ep_scalar() && d->K % 4 == 0 && d->y_cstride % 4 == 0 && aligned16(y) && aligned16(bias) && aligned16(residual);
-#ifndef FMI_HOST_EMU
-  const int ks = (act == 0 && batch_w == 1) ? conv_ksplit(g.Mdim(), d->K, g.Kdim()) : 1;
-  // both operands as bf16 piece images (conv_p3.h): the activation pieces of x came from x's producer
-  static const bool p3_off = getenv("FMI_P3_OFF") != nullptr;
-  static const bool c3p3_off = getenv("FMI_C3P3_OFF") != nullptr;
-  const bool p3_any = !p3_off && batch_w == 1 && d->x_cstride == d->C && p3_generic_ok(g, d->x3, w3, d->K);
-  if (p3_any && !c3p3_off && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->dil <= 1 &&
-      conv3x3_p3_eligible(d->x3, w3, d->C, d->K, (int64_t)d->N * d->H * d->W)) {
-    C3P3Args ca{(const uint16_t*)d->x3, w3, d->N, d->H, d->W, d->C, d->K, 0, make_fastdiv(d->W), make_fastdiv(d->H * d->W)};
-    if (ks > 1) {
-      const int64_t total = (int64_t)d->N * d->OH * d->OW * d->K;
-      hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, y, bias, residual, d->K,
-                         d->y_cstride, total);
-      ep.bias = nullptr;
-      ep.res = nullptr;
-      ep.act = 3;
-      ep.vec = 0;
+  if (shared_init || ks > 1) {
+    if (!shared_init) {
+      const int64_t total = (int64_t)g.N * ep.OHt * ep.OWt * Nout;
+      hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, st, ep.y, ep.bias, ep.res, Nout, ep.cstride,
+                         total);
     }
-    return launch_conv3x3_p3(ca, ep, g.Mdim(), ks, (hipStream_t)stream);
-  }
-  if (p3_any) {
-    if (ks > 1) {
-      const int64_t total = (int64_t)d->N * d->OH * d->OW * d->K;
-      hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, y, bias, residual, d->K,
-                         d->y_cstride, total);
-      ep.bias = nullptr;
-      ep.res = nullptr;
-      ep.act = 3;
-      ep.vec = 0;
-    }
-    return launch_gemm_p3(ConvK3{(const uint16_t*)d->x3, g, make_fastdiv(g.ntaps())}, ConvWX3{w3, g, (int64_t)d->kh * d->kw * d->C * d->K, d->K}, ep, g.Mdim(), d->K, g.Kdim(), ks,
-                          (hipStream_t)stream);
-  }
-  static const bool c3_off = getenv("FMI_C3_OFF") != nullptr;
-  const bool c3 = !c3_off && !(FMI_EXP & 32) && batch_w == 1 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->pad_mode == 0 && d->dil <= 1 &&
-                  conv3x3_eligible(x, wf, d->C, d->x_cstride, d->K, (int64_t)d->N * d->H * d->W);
-  if (c3) {
-    C3Args ca{x, wf, d->N, d->H, d->W, d->C, d->x_cstride, d->K, 0, make_fastdiv(d->W), make_fastdiv(d->H * d->W), w3};
-    if (ks > 1) {
-      const int64_t total = (int64_t)d->N * d->OH * d->OW * d->K;
-      hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, y, bias, residual, d->K,
-                         d->y_cstride, total);
-      ep.bias = nullptr;
-      ep.res = nullptr;
-      ep.act = 3;
-      ep.vec = 0;
-    }
-    return launch_conv3x3(ca, ep, g.Mdim(), ks, (hipStream_t)stream);
-  }
-  if (ks > 1) {
-    const int64_t total = (int64_t)d->N * d->OH * d->OW * d->K;
-    hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, y, bias, residual, d->K,
-                       d->y_cstride, total);
     ep.bias = nullptr;
     ep.res = nullptr;
     ep.act = 3;
     ep.vec = 0;
-    if (w3 && la.dma_ok()) return launch_gemm(la, ConvWX3{w3, g, (int64_t)d->kh * d->kw * d->C * d->K, d->K}, ep, g.Mdim(), d->K, g.Kdim(), 1, ks, (hipStream_t)stream);
-    return launch_gemm(la, lb, ep, g.Mdim(), d->K, g.Kdim(), 1, ks, (hipStream_t)stream);
   }
-  if (w3 && la.dma_ok()) return launch_gemm(la, ConvWX3{w3, g, (int64_t)d->kh * d->kw * d->C * d->K, d->K}, ep, g.Mdim(), d->K, g.Kdim(), 1, 1, (hipStream_t)stream);
+  const uint16_t* w3 = (const uint16_t*)w3p;
+  const int64_t w3_stride = (int64_t)d->kh * d->kw * d->C * d->K;
+  const int64_t pixels = (int64_t)g.N * g.IH * g.IW;
+  const bool tap3 = d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->dil <= 1 && g.pad_mode == 0;
+  // both operands as bf16 piece images (conv_p3.h): the activation pieces of x came from x's producer
+  const bool p3 = batch_w == 1 && g.cstride == g.C && g.Kdim() > 0 && p3_generic_ok(g, x3, w3, Nout);
+  if (p3 && tap3 && conv3x3_p3_eligible(x3, w3, g.C, Nout, pixels)) {
+    const C3P3Args ca{(const uint16_t*)x3, w3, g.N, g.IH, g.IW, g.C, Nout, flip, make_fastdiv(g.IW), make_fastdiv(g.IH * g.IW)};
+    return launch_conv3x3_p3(ca, ep, g.Mdim(), ks, st);
+  }
+  if (p3)
+    return launch_gemm_p3(ConvK3{(const uint16_t*)x3, g, make_fastdiv(g.ntaps())}, ConvWX3{w3, g, w3_stride, Nout}, ep, g.Mdim(), Nout,
+                          g.Kdim(), ks, st);
+  if (batch_w == 1 && tap3 && conv3x3_eligible(x, w, g.C, g.cstride, Nout, pixels)) {
+    const C3Args ca{x, w, g.N, g.IH, g.IW, g.C, g.cstride, Nout, flip, make_fastdiv(g.IW), make_fastdiv(g.IH * g.IW), w3};
+    return launch_conv3x3(ca, ep, g.Mdim(), ks, st);
+  }
+  if (w3 && la.dma_ok()) return launch_gemm(la, ConvWX3{w3, g, w3_stride, Nout}, ep, g.Mdim(), Nout, g.Kdim(), 1, ks, st);
 #endif
-  return launch_gemm(la, lb, ep, g.Mdim(), d->K, g.Kdim(), batch_w, 1, (hipStream_t)stream);
+  return launch_gemm(la, lb, ep, g.Mdim(), Nout, g.Kdim(), batch_w, ks, st);
+}
+
+// d->w3, the bf16 piece image of the weights, where the kernels can read it: shared weights, 16-channel groups of the reduction
+static const void* weight_pieces(const fmi_conv_desc* d, int batch_w, int red_c) {
+#ifndef FMI_HOST_EMU
+  if (FMI_X6 && batch_w == 1 && red_c % 16 == 0 && aligned16(d->w3)) return d->w3;
+#endif
+  return nullptr;
 }
 
 static int check_y3(const fmi_conv_desc* d, int out_c, int out_cs) {
@@ -186,65 +169,68 @@ extern "C" int fmi_conv2d_fwd_f32(const fmi_conv_desc* d, const float* x, const 
   if (!d) return FMI_ERR_BAD_ARG;
   int rc = check_y3(d, d->K, d->y_cstride);
   if (rc) return rc;
-  bool y3_done = false;
-  rc = fwd_impl(d, x, wf, bias, residual, y, act, batch_w, w_bstride, stream, &y3_done);
+  rc = check_desc(d);
+  if (rc) return rc;
+  if (!x || !wf || !y || batch_w < 1 || act < 0 || act > 2) return FMI_ERR_BAD_ARG;
+  if (batch_w > 1 && batch_w != d->N) return FMI_ERR_BAD_ARG;
+  auto finish = [&](int rc) {  // the piece image of y, if one is requested
 #ifndef FMI_HOST_EMU
-  if (rc == FMI_OK && d->y3 && !y3_done) rc = fmi_split3_f32(y, d->y3, nullptr, (int64_t)d->N * d->OH * d->OW, d->K, 0, 0.f, stream);
+    if (rc == FMI_OK && d->y3) rc = fmi_split3_f32(y, d->y3, nullptr, (int64_t)d->N * d->OH * d->OW, d->K, 0, 0.f, stream);
 #endif
-  return rc;
+    return rc;
+  };
+#ifndef FMI_HOST_EMU
+  if (batch_w == 1 && fmi_conv2d_thin_supported(d) && aligned16(x))
+    return finish(fmi_conv2d_thin_fwd_f32(d, x, wf, bias, residual, y, act, stream));
+#endif
+  const ConvGeom g = fwd_geom(d, x, batch_w > 1 ? 1 : d->N);
+  // bf16 piece images of the weights (fmi_weight_prepare_f32 writes them): [3][taps][C / 8][K][8]
+  const void* w3 = weight_pieces(d, batch_w, d->C);
+  ConvEp ep{y, bias, residual, d->OH, d->OW, 1, 0, 0, d->OH, d->OW, d->y_cstride, act, g.dGW, g.dG, (int64_t)d->OH * d->OW * d->y_cstride};
+  ep.vec = ep_vec(ep, d->K);
+  return finish(conv_phase(d, g, x, d->x3, wf, w3, w_bstride, d->K, 0, ep, batch_w, act == 0 && batch_w == 1, false, (hipStream_t)stream));
 }
 
-static int dgrad_impl2(const fmi_conv_desc* d, const float* dy, const float* wt, const float* bias, const float* residual,
-                       const float* mask, float mslope, float* dx, int batch_w, int64_t w_bstride, void* stream, bool* y3_done);
 static int dgrad_impl(const fmi_conv_desc* d, const float* dy, const float* wt, const float* bias, const float* residual,
                       const float* mask, float mslope, float* dx, int batch_w, int64_t w_bstride, void* stream) {
   if (!d) return FMI_ERR_BAD_ARG;
   int rc = check_y3(d, d->C, d->x_cstride);
   if (rc) return rc;
-  bool y3_done = false;
-  rc = dgrad_impl2(d, dy, wt, bias, residual, mask, mslope, dx, batch_w, w_bstride, stream, &y3_done);
-#ifndef FMI_HOST_EMU
-  if (rc == FMI_OK && d->y3 && !y3_done) rc = fmi_split3_f32(dx, d->y3, nullptr, (int64_t)d->N * d->H * d->W, d->C, 0, 0.f, stream);
-#endif
-  return rc;
-}
-static int dgrad_impl2(const fmi_conv_desc* d, const float* dy, const float* wt, const float* bias, const float* residual,
-                       const float* mask, float mslope, float* dx, int batch_w, int64_t w_bstride, void* stream, bool* y3_done) {
-  int rc = check_desc(d);
+  rc = check_desc(d);
   if (rc) return rc;
   if (!dy || !wt || !dx || batch_w < 1) return FMI_ERR_BAD_ARG;
   if (d->pad_mode != 0) return FMI_ERR_UNSUPPORTED;  // reflect: run on the padded extent, then fmi_reflect_pad_fold_f32
   if (batch_w > 1 && batch_w != d->N) return FMI_ERR_BAD_ARG;
   if (mask && bias) return FMI_ERR_UNSUPPORTED;  // the mask applies to the bare adjoint; a residual is added AFTER it (ConvEp: v * mask + res)
+  auto finish = [&](int rc) {  // the piece image of dx, if one is requested
+#ifndef FMI_HOST_EMU
+    if (rc == FMI_OK && d->y3) rc = fmi_split3_f32(dx, d->y3, nullptr, (int64_t)d->N * d->H * d->W, d->C, 0, 0.f, stream);
+#endif
+    return rc;
+  };
 #ifndef FMI_HOST_EMU
   if (batch_w == 1 && !bias && !residual && !mask && fmi_conv2d_thin_supported(d) && aligned16(dx))
-    return fmi_conv2d_thin_dgrad_f32(d, dy, wt, dx, stream);
+    return finish(fmi_conv2d_thin_dgrad_f32(d, dy, wt, dx, stream));
   if (batch_w == 1 && !bias && !residual && !mask && d->C <= 4 && d->x_cstride == d->C) {  // thin INPUT: VGG16's first layer
     const int rc_thin = fmi_conv2d_thin_input_dgrad_f32(d, dy, wt, dx, stream);
-    if (rc_thin != FMI_ERR_UNSUPPORTED) return rc_thin;
+    if (rc_thin != FMI_ERR_UNSUPPORTED) return finish(rc_thin);
   }
 #endif
   const int n_eff = batch_w > 1 ? 1 : d->N;
   const int s = d->stride;
-  const int dl = d->dil > 1 ? d->dil : 1;
-#ifndef FMI_HOST_EMU
   // bf16 piece images of the adjoint's weights: [3][taps][K / 8][C][8]
-  const uint16_t* w3 = (FMI_X6 && batch_w == 1 && d->K % 16 == 0 && aligned16(d->w3)) ? (const uint16_t*)d->w3 : nullptr;
-  const int64_t w3_stride = (int64_t)d->kh * d->kw * d->K * d->C;
-#endif
-  if (dl > 1 && s != 1) return FMI_ERR_UNSUPPORTED;  // adjoint of a dilated AND strided convolution: not needed by modules/drn.py
+  const void* w3 = weight_pieces(d, batch_w, d->K);
+  if (d->dil > 1 && s != 1) return FMI_ERR_UNSUPPORTED;  // adjoint of a dilated AND strided convolution: not needed by modules/drn.py
+  bool strided_split = false;
 #ifndef FMI_HOST_EMU
   // Strided adjoints of small feature maps (the stride-2 style heads of the pSp encoder: 512 -> 512 at 16^2 .. 2^2) are a few
   // output tiles per sub-pixel phase with up to 128 reduction tiles each -- 0.25 ms of pure load latency per call.  If any phase
   // wants a split reduction, dx is initialised once and EVERY phase adds its (partial) sums atomically.
-  bool strided_split = false;
   if (s > 1 && batch_w == 1) {
     for (int py = 0; py < s && !strided_split; ++py)
       for (int px = 0; px < s && !strided_split; ++px) {
-        const int GH = (d->H - py + s - 1) / s, GW = (d->W - px + s - 1) / s;
-        const int kh0 = (py + d->pad) % s, kw0 = (px + d->pad) % s;
-        const int nty = kh0 < d->kh ? (d->kh - kh0 + s - 1) / s : 0, ntx = kw0 < d->kw ? (d->kw - kw0 + s - 1) / s : 0;
-        if (GH > 0 && GW > 0 && conv_ksplit((int64_t)d->N * GH * GW, d->C, (int64_t)nty * ntx * d->K) > 1) strided_split = true;
+        const ConvGeom g = adj_geom(d, dy, n_eff, py, px);
+        if (g.GH > 0 && g.GW > 0 && conv_ksplit(g.Mdim(), d->C, g.Kdim()) > 1) strided_split = true;
       }
     if (strided_split) {
       const int64_t total = (int64_t)d->N * d->H * d->W * d->C;
@@ -252,137 +238,34 @@ static int dgrad_impl2(const fmi_conv_desc* d, const float* dy, const float* wt,
                          d->x_cstride, total);
     }
   }
-#endif
-#ifndef FMI_HOST_EMU
   // thin ConvTranspose2d(3, stride 2) on a large map: all four sub-pixel phases in one tap-reuse launch (convt3x3.h)
-  static const bool ct3_off = getenv("FMI_CT3_OFF") != nullptr;
-  if (!ct3_off && batch_w == 1 && !strided_split && !d->x3 && !(FMI_EXP & 32) && convt3x3_eligible(d, dy, w3)) {
+  if (batch_w == 1 && !strided_split && !d->x3 && convt3x3_eligible(d, dy, (const uint16_t*)w3)) {
     CT3Args ca{};
-    ca.x = dy; ca.w3 = w3; ca.N = d->N; ca.H = d->OH; ca.W = d->OW; ca.Cred = d->K; ca.cs = d->y_cstride; ca.Nout = d->C;
+    ca.x = dy; ca.w3 = (const uint16_t*)w3; ca.N = d->N; ca.H = d->OH; ca.W = d->OW; ca.Cred = d->K; ca.cs = d->y_cstride; ca.Nout = d->C;
     ca.dW = make_fastdiv(d->OW); ca.dHW = make_fastdiv(d->OH * d->OW);
     ConvEp ep{dx, bias, residual, d->OH, d->OW, 2, 0, 0, d->H, d->W, d->x_cstride, 0, ca.dW, ca.dHW, (int64_t)d->H * d->W * d->x_cstride};
-    ep.vec = !ep_scalar() && d->C % 4 == 0 && d->x_cstride % 4 == 0 && aligned16(dx) && aligned16(bias) && aligned16(residual) && aligned16(mask);
     ep.mask = mask;
     ep.mslope = mslope;
+    ep.vec = ep_vec(ep, d->C);
     ca.ep = ep;
-    return launch_convt3x3(ca, d->N * d->OH * d->OW, (hipStream_t)stream);
+    return finish(launch_convt3x3(ca, d->N * d->OH * d->OW, (hipStream_t)stream));
   }
 #endif
   for (int py = 0; py < s; ++py) {
     for (int px = 0; px < s; ++px) {
-      const int GH = (d->H - py + s - 1) / s, GW = (d->W - px + s - 1) / s;
-      if (GH <= 0 || GW <= 0) continue;
-      ConvGeom g{};
-      g.N = n_eff; g.IH = d->OH; g.IW = d->OW; g.C = d->K; g.cstride = d->y_cstride;
-      g.GH = GH; g.GW = GW; g.S = 1;
-      g.kh0 = (py + d->pad) % s; g.kw0 = (px + d->pad) % s;
-      g.nty = g.kh0 < d->kh ? (d->kh - g.kh0 + s - 1) / s : 0;
-      g.ntx = g.kw0 < d->kw ? (d->kw - g.kw0 + s - 1) / s : 0;
-      g.dy0 = (py + d->pad - g.kh0) / s; g.dx0 = (px + d->pad - g.kw0) / s;
-      g.ystep = -dl; g.xstep = -dl; g.khstep = s; g.kwstep = s; g.kw = d->kw;  // dl > 1 only with s == 1 (checked above)
-      g.pad_mode = 0;
-      g.vec = (d->K % 4 == 0) && (d->y_cstride % 4 == 0) && aligned16(dy);
-      g.dGW = make_fastdiv(GW); g.dG = make_fastdiv(GH * GW); g.dC = make_fastdiv(g.C);
-      g.dntx = make_fastdiv(g.ntx > 0 ? g.ntx : 1);
-      g.img_bs = (int64_t)d->OH * d->OW * d->y_cstride;
-      if (g.nty == 0 || g.ntx == 0) { g.nty = 0; g.ntx = 1; }
-      ConvK la{dy, g};
-      ConvWX lb{wt, g, w_bstride, d->C, (d->C % 4 == 0) && aligned16(wt) && (w_bstride % 4 == 0)};
-      ConvEp ep{dx, bias, residual, GH, GW, s, py, px, d->H, d->W, d->x_cstride, 0, g.dGW, g.dG,
+      const ConvGeom g = adj_geom(d, dy, n_eff, py, px);
+      if (g.GH <= 0 || g.GW <= 0) continue;
+      ConvEp ep{dx, bias, residual, g.GH, g.GW, s, py, px, d->H, d->W, d->x_cstride, 0, g.dGW, g.dG,
                 (int64_t)d->H * d->W * d->x_cstride};
-      ep.vec = !ep_scalar() && d->C % 4 == 0 && d->x_cstride % 4 == 0 && aligned16(dx) && aligned16(bias) && aligned16(residual) && aligned16(mask);
       ep.mask = mask;
       ep.mslope = mslope;
-#ifndef FMI_HOST_EMU
-      static const bool p3_off = getenv("FMI_P3_OFF") != nullptr;
-      const bool p3 = !p3_off && batch_w == 1 && d->y_cstride == d->K && g.Kdim() > 0 && p3_generic_ok(g, d->x3, w3, d->C);
-      const int ks_p = strided_split ? conv_ksplit(g.Mdim(), d->C, g.Kdim()) : ((s == 1 && batch_w == 1) ? conv_ksplit(g.Mdim(), d->C, g.Kdim()) : 1);
-      static const bool c3p3_off = getenv("FMI_C3P3_OFF") != nullptr;
-      if (p3 && !c3p3_off && s == 1 && d->kh == 3 && d->kw == 3 && d->pad == 1 && d->dil <= 1 &&
-          conv3x3_p3_eligible(d->x3, w3, d->K, d->C, (int64_t)d->N * d->H * d->W)) {
-        C3P3Args ca{(const uint16_t*)d->x3, w3, d->N, d->OH, d->OW, d->K, d->C, 1, make_fastdiv(d->OW), make_fastdiv(d->OH * d->OW)};
-        if (ks_p > 1) {
-          const int64_t total = (int64_t)d->N * d->H * d->W * d->C;
-          hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, dx, bias, residual,
-                             d->C, d->x_cstride, total);
-          ep.bias = nullptr;
-          ep.res = nullptr;
-          ep.act = 3;
-          ep.vec = 0;
-        }
-        rc = launch_conv3x3_p3(ca, ep, g.Mdim(), ks_p, (hipStream_t)stream);
-        if (rc) return rc;
-        continue;
-      }
-      if (p3) {
-        if (!strided_split && ks_p > 1) {
-          const int64_t total = (int64_t)d->N * d->H * d->W * d->C;
-          hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, dx, bias, residual,
-                             d->C, d->x_cstride, total);
-        }
-        if (strided_split || ks_p > 1) {
-          ep.bias = nullptr;
-          ep.res = nullptr;
-          ep.act = 3;
-          ep.vec = 0;
-        }
-        rc = launch_gemm_p3(ConvK3{(const uint16_t*)d->x3, g, make_fastdiv(g.ntaps())}, ConvWX3{w3, g, w3_stride, d->C}, ep, g.Mdim(), d->C, g.Kdim(), ks_p, (hipStream_t)stream);
-        if (rc) return rc;
-        continue;
-      }
-      if (strided_split) {
-        ep.bias = nullptr;
-        ep.res = nullptr;
-        ep.act = 3;
-        ep.vec = 0;
-        if (w3 && la.dma_ok()) rc = launch_gemm(la, ConvWX3{w3, g, w3_stride, d->C}, ep, g.Mdim(), d->C, g.Kdim(), 1, conv_ksplit(g.Mdim(), d->C, g.Kdim()), (hipStream_t)stream);
-        else rc = launch_gemm(la, lb, ep, g.Mdim(), d->C, g.Kdim(), 1, conv_ksplit(g.Mdim(), d->C, g.Kdim()), (hipStream_t)stream);
-        if (rc) return rc;
-        continue;
-      }
-      const int ks = (s == 1 && batch_w == 1) ? conv_ksplit(g.Mdim(), d->C, g.Kdim()) : 1;
-      static const bool c3_off = getenv("FMI_C3_OFF") != nullptr;
-      const bool c3 = !c3_off && !(FMI_EXP & 32) && s == 1 && batch_w == 1 && d->kh == 3 && d->kw == 3 && d->pad == 1 && d->dil <= 1 &&
-                      conv3x3_eligible(dy, wt, d->K, d->y_cstride, d->C, (int64_t)d->N * d->H * d->W);
-      if (c3) {  // adjoint of a 3x3 stride-1 pad-1 convolution = the same convolution of dy with flipped taps
-        C3Args ca{dy, wt, d->N, d->OH, d->OW, d->K, d->y_cstride, d->C, 1, make_fastdiv(d->OW), make_fastdiv(d->OH * d->OW), w3};
-        if (ks > 1) {
-          const int64_t total = (int64_t)d->N * d->H * d->W * d->C;
-          hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, dx, bias, residual,
-                             d->C, d->x_cstride, total);
-          ep.bias = nullptr;
-          ep.res = nullptr;
-          ep.act = 3;
-          ep.vec = 0;
-        }
-        rc = launch_conv3x3(ca, ep, g.Mdim(), ks, (hipStream_t)stream);
-        if (rc) return rc;
-        continue;
-      }
-      if (ks > 1) {
-        const int64_t total = (int64_t)d->N * d->H * d->W * d->C;
-        hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, dx, bias, residual,
-                           d->C, d->x_cstride, total);
-        ep.bias = nullptr;
-        ep.res = nullptr;
-        ep.act = 3;
-        ep.vec = 0;
-        if (w3 && la.dma_ok()) rc = launch_gemm(la, ConvWX3{w3, g, w3_stride, d->C}, ep, g.Mdim(), d->C, g.Kdim(), 1, ks, (hipStream_t)stream);
-        else rc = launch_gemm(la, lb, ep, g.Mdim(), d->C, g.Kdim(), 1, ks, (hipStream_t)stream);
-        if (rc) return rc;
-        continue;
-      }
-      if (w3 && la.dma_ok()) {
-        rc = launch_gemm(la, ConvWX3{w3, g, w3_stride, d->C}, ep, g.Mdim(), d->C, g.Kdim(), 1, 1, (hipStream_t)stream);
-        if (rc) return rc;
-        continue;
-      }
-#endif
-      rc = launch_gemm(la, lb, ep, g.Mdim(), d->C, g.Kdim(), batch_w, 1, (hipStream_t)stream);
+      ep.vec = ep_vec(ep, d->C);
+      rc = conv_phase(d, g, dy, d->x3, wt, w3, w_bstride, d->C, 1, ep, batch_w, batch_w == 1 && (s == 1 || strided_split), strided_split,
+                      (hipStream_t)stream);
       if (rc) return rc;
     }
   }
-  return FMI_OK;
+  return finish(FMI_OK);
 }
 extern "C" int fmi_conv2d_dgrad_f32(const fmi_conv_desc* d, const float* dy, const float* wt, const float* bias,
                                     const float* residual, float* dx, int batch_w, int64_t w_bstride, void* stream) {
@@ -405,7 +288,7 @@ extern "C" int fmi_conv_transpose2d_pair_f32(const fmi_conv_desc* d, const float
   ca.N = d->N; ca.H = d->OH; ca.W = d->OW; ca.Cred = d->K; ca.cs = d->y_cstride; ca.Nout = d->C;
   ca.dW = make_fastdiv(d->OW); ca.dHW = make_fastdiv(d->OH * d->OW);
   ConvEp ep{y, bias, nullptr, d->OH, d->OW, 2, 0, 0, d->H, d->W, d->x_cstride, 0, ca.dW, ca.dHW, (int64_t)d->H * d->W * d->x_cstride};
-  ep.vec = !ep_scalar() && d->C % 4 == 0 && d->x_cstride % 4 == 0 && aligned16(y) && aligned16(bias);
+  ep.vec = ep_vec(ep, d->C);
   ca.ep = ep;
   return launch_convt3x3(ca, d->N * d->OH * d->OW, (hipStream_t)stream);
 #else
@@ -436,8 +319,7 @@ extern "C" int fmi_conv2d_wgrad_f32(const fmi_conv_desc* d, const float* x, cons
 #ifndef FMI_HOST_EMU
   // both operands as bf16 piece images (d->x3 = pieces of x, d->y3 = pieces of dy, INPUTS here): no split arithmetic, transposed LDS reads.
   // The bias gradient does not ride along on this path (the caller runs fmi_bias_grad_f32).
-  static const bool wg3_off = getenv("FMI_WG3_OFF") != nullptr || getenv("FMI_P3_OFF") != nullptr;
-  if (!wg3_off && FMI_X6 && batch_w == 1 && !dbias && wgrad_p3_ok(d, d->x3, d->y3))
+  if (FMI_X6 && batch_w == 1 && !dbias && wgrad_p3_ok(d, d->x3, d->y3))
     return launch_wgrad_p3(d, (const uint16_t*)d->x3, (const uint16_t*)d->y3, dwf, (hipStream_t)stream);
 #endif
   const int n_eff = batch_w > 1 ? 1 : d->N;
@@ -457,8 +339,6 @@ extern "C" int fmi_conv2d_wgrad_f32(const fmi_conv_desc* d, const float* x, cons
   const int64_t kmax = Kg / 512;
   if (ksplit > kmax) ksplit = kmax;
   if (ksplit < 1) ksplit = 1;
-  static const int wks_dbg = getenv("FMI_WKS") ? atoi(getenv("FMI_WKS")) : 0;  // experiment: force the pixel split of the weight gradient
-  if (wks_dbg > 0) ksplit = wks_dbg;
   if (fmi_det()) ksplit = 1;  // reproducible mode: one workgroup per tile walks the whole pixel reduction
   if (ksplit * batch_w > 65535) ksplit = 65535 / batch_w;
   return launch_gemm(la, lb, ep, Mg, Ng, Kg, batch_w, (int)ksplit, (hipStream_t)stream);

@@ -114,13 +114,9 @@ __global__ void __launch_bounds__(256) conv3x3_dma_kernel(C3Args a, ConvEp ep, i
                  : "memory");
   };
   auto issue = [&](int it, int st) {
-#ifdef FMI_C3_KY_OUTER
-    const int ky = it / cchunks, c0 = (it - ky * cchunks) * 16;  // wave-uniform
-#else
     // channel chunk OUTER, kernel row INNER: the three kernel rows re-read one channel chunk of neighbouring image rows while it is still in
     // the XCD's L2 (with the kernel row outer every activation byte came three times from beyond L2)
     const int cc_ = it / 3, ky = it - 3 * cc_, c0 = cc_ * 16;  // wave-uniform
-#endif
     const uint32_t sa = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(st * STAGE) * 4u + (uint32_t)wid * 1024u);  // + this wave's slot
     const uint32_t sb = sa + RA * BK * 4;
     const int64_t aoff = (int64_t)(ky - 1) * a.W * a.cs + c0;
@@ -263,13 +259,12 @@ static int launch_conv3x3(const C3Args& a, const ConvEp& ep, int M, int ksplit, 
 #define C3_LAUNCH(TILE) C3_LAUNCH_(TILE, false)
   auto wgs = [&](int bm, int bn) { return ceil_div64(M, bm) * ceil_div64(a.Nout, bn) * ksplit; };
   const int N = a.Nout;
-  const bool fl = it_chunk > 13 && (fmi_det() || fmi_blocked_acc());  // blocked accumulation of a long unsplit reduction (conv_p3.h)
+  const bool fl = it_chunk > 13 && fmi_det();  // blocked accumulation of a long unsplit reduction (conv_p3.h)
 #if FMI_X6
-  static const bool w3_off = getenv("FMI_W3_OFF") != nullptr;  // debug A/B: split the weight fragments in registers as well
   // piece images of the weights: 2 x 27 KB of LDS at 64 columns (two workgroups per CU; a 128-column piece tile would leave one).  Measured
   // at 8 x 128^2 256 -> 256 / 24 x 224^2 64 -> 64 / 8 x 32^2 128 -> 128: 163 / 154 / 81 TFLOP/s against 170 / 144 / 75 with both operands split in the
   // consuming waves (128 x 128 tiles): taken for narrow outputs and for launches too small to fill the chip with the large tile
-  if (a.w3 && N > 32 && !w3_off && (N <= 64 || wgs(128, 128) < 800)) {
+  if (a.w3 && N > 32 && (N <= 64 || wgs(128, 128) < 800)) {
     C3_LAUNCH_(Tile128x64w, true);
     return fmi_launch_status();
   }

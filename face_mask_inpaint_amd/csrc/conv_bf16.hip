@@ -342,15 +342,11 @@ __global__ void __launch_bounds__(256) f32_to_bf16_kernel(const float* __restric
 
 #include "conv_bf16_8ph.h"
 
-// kernel selection override (tests / A-B timing): 0 = by shape, 1 = never the 8-wave tiles, 2 = no eight-phase kernel, 8 = the
-// eight-phase kernel wherever it is legal.  FMI_BF16_TILE in the environment sets the initial value.
-static int g_bf16_tile_mode = -1;
-static int bf16_tile_mode() {
-  if (g_bf16_tile_mode < 0) g_bf16_tile_mode = getenv("FMI_BF16_TILE") ? atoi(getenv("FMI_BF16_TILE")) : 0;
-  return g_bf16_tile_mode;
-}
+// kernel selection override (tests): 0 = by shape, 1 = never the 8-wave tiles, 2 = no eight-phase kernel, 8 = the eight-phase kernel
+// wherever it is legal
+static int g_bf16_tile_mode = 0;
 extern "C" int fmi_debug_bf16_tile(int mode) {
-  const int prev = bf16_tile_mode();
+  const int prev = g_bf16_tile_mode;
   if (mode >= 0) g_bf16_tile_mode = mode;
   return prev;
 }
@@ -392,7 +388,7 @@ static int launch_conv_bf16(ConvSetB& set, int nph, int N, bf16_t* y, float* ws,
       hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(fmi_bw_grid(out_elems / 4, 256)), dim3(256), 0, st, ws, y, out_elems / 4);      \
   } while (0)
   auto wgs = [&](int bm, int bn) { return ceil_div64(Mmax, bm) * ceil_div64(N, bn) * nph; };
-  const int tile_dbg = bf16_tile_mode();
+  const int tile_dbg = g_bf16_tile_mode;
   // the eight-phase kernel (conv_bf16_8ph.h): whole 64-deep reduction tiles, 8-byte output stores, no split reduction
   bool ok8 = BK == 64 && tile_dbg != 1 && tile_dbg != 2 && N % 4 == 0 && N > 64;
   for (int p = 0; p < nph && ok8; ++p)
@@ -748,7 +744,7 @@ extern "C" int fmi_conv2d_wgrad_bf16(const fmi_conv_desc* d, const uint16_t* x, 
   a.Kout = d->K; a.ycs = d->y_cstride; a.Mrows = d->kh * d->kw * d->C; a.P = d->N * d->OH * d->OW;
   // the eight-phase kernel (wgrad_bf16_8ph.h): 256 x 256 tiles, one workgroup per CU -- for wide layers with a long pixel range
   {
-    const int mode = bf16_tile_mode();
+    const int mode = g_bf16_tile_mode;
     const int64_t tm8 = ceil_div64(a.Mrows, 256), tn8 = ceil_div64(d->K, 256);
     const bool fits = d->K >= 256 && tn8 * 256 - d->K <= d->K / 8 && tm8 * 256 - a.Mrows <= a.Mrows / 8 && tm8 * tn8 <= 256 && a.P >= 4096 &&
                       (int64_t)d->kh * d->kw * d->C < (1ll << 30) && (int64_t)d->N * d->H * d->W * d->x_cstride < (1ll << 31);
@@ -781,8 +777,7 @@ extern "C" int fmi_conv2d_wgrad_bf16(const fmi_conv_desc* d, const uint16_t* x, 
   ksplit = ceil_div64(a.P, a.kchunk);
   a.tiles = (int)(tm * tn);
   a.ksplit = (int)ksplit;
-  static const bool xcd_off = getenv("FMI_WGRAD_XCD_OFF") != nullptr;  // debug: splits in grid.y, tiles over all XCDs
-  a.xcd_splits = (ksplit >= 8 && !xcd_off) ? 1 : 0;
+  a.xcd_splits = ksplit >= 8 ? 1 : 0;
   const int64_t nwg = a.xcd_splits ? tm * tn * ceil_div64(ksplit, 8) * 8 : tm * tn;
   if (nwg > 0x7fffffffLL) return FMI_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)nwg, a.xcd_splits ? 1u : (unsigned)ksplit);

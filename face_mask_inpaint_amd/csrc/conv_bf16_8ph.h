@@ -50,10 +50,6 @@ struct EpActB {
   int on;
 };
 
-#ifndef FMI_8P_EXP
-#define FMI_8P_EXP 0  // timing experiments (wrong results except 1): 1 no stagger, 2 no DMA issue, 4 no LDS reads, 8 no MFMAs, 16 no stores, 32 no output stage
-#endif
-
 typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 
@@ -136,10 +132,6 @@ __global__ void __launch_bounds__(512) conv_bf16_8ph_kernel(ConvSetB set, EpActB
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
   // one half-image = NA (NB) LDS-DMA instructions of this thread, 8 KB apart; M0 (the LDS base) is saved and restored once per group
   auto dma = [&](const void* const (&gp)[4], int n, uint32_t dst) {
-    if (FMI_8P_EXP & 2) {
-      asm volatile("" ::"v"(gp[0]), "v"(gp[1]), "v"(gp[2]), "v"(gp[3]), "s"(dst));
-      return;
-    }
     unsigned keep;
     if (n == 1)
       asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
@@ -192,11 +184,6 @@ __global__ void __launch_bounds__(512) conv_bf16_8ph_kernel(ConvSetB set, EpActB
 
   const int nt = K >> 6;  // reduction tiles (K % 64 == 0 is the host's condition for this kernel)
   auto read_a = [&](int st, int sub) {
-    if (FMI_8P_EXP & 4) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(ax[r][0]), "+v"(ax[r][1]));
-      return;
-    }
     const unsigned char* p0 = lds + st * STAGE + sub * AH + a_off0;
     const unsigned char* p1 = lds + st * STAGE + sub * AH + a_off1;
 #pragma unroll
@@ -206,11 +193,6 @@ __global__ void __launch_bounds__(512) conv_bf16_8ph_kernel(ConvSetB set, EpActB
     }
   };
   auto read_b = [&](int st, int sub, bf16x8 (&bw)[2][2]) {
-    if (FMI_8P_EXP & 4) {
-#pragma unroll
-      for (int c = 0; c < 2; ++c) asm volatile("" : "+v"(bw[c][0]), "+v"(bw[c][1]));
-      return;
-    }
     const unsigned char* p0 = lds + st * STAGE + sub * BH + b_off0;
     const unsigned char* p1 = lds + st * STAGE + sub * BH + b_off1;
 #pragma unroll
@@ -220,11 +202,6 @@ __global__ void __launch_bounds__(512) conv_bf16_8ph_kernel(ConvSetB set, EpActB
     }
   };
   auto mfmas = [&](f32x4v (&d)[4][2], const bf16x8 (&bw)[2][2]) {
-    if (FMI_8P_EXP & 8) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(d[r][0]), "+v"(d[r][1]) : "v"(ax[r][0]), "v"(ax[r][1]), "v"(bw[0][0]), "v"(bw[0][1]), "v"(bw[1][0]), "v"(bw[1][1]));
-      return;
-    }
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -265,7 +242,7 @@ __global__ void __launch_bounds__(512) conv_bf16_8ph_kernel(ConvSetB set, EpActB
     advance(t2);
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if (grp && !(FMI_8P_EXP & 1)) __builtin_amdgcn_s_barrier();  // the second four waves run one barrier behind
+    if (grp) __builtin_amdgcn_s_barrier();  // the second four waves run one barrier behind
     int st = 0;
     // ONE loop body for every reduction tile (two specialised copies -- steady state / last two tiles -- double the code for two
     // scalar branches per phase; a persistent variant with both copies made the allocator shuffle accumulators where they met)
@@ -317,7 +294,7 @@ __global__ void __launch_bounds__(512) conv_bf16_8ph_kernel(ConvSetB set, EpActB
       FMI_8P_END();
       st ^= 1;
     }
-    if (!grp && !(FMI_8P_EXP & 1)) __builtin_amdgcn_s_barrier();
+    if (!grp) __builtin_amdgcn_s_barrier();
   }
 #undef FMI_8P_MID
 #undef FMI_8P_END
@@ -327,19 +304,6 @@ __global__ void __launch_bounds__(512) conv_bf16_8ph_kernel(ConvSetB set, EpActB
   const ConvEpB ep = set.ph[blockIdx.y].ep;
   const int M = set.ph[blockIdx.y].M, N = set.N;
   const int cl = 4 * (lane >> 4);
-  if (FMI_8P_EXP & 32) {  // timing: no output stage at all (one store that keeps the accumulators alive)
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int c = 0; c < 2; ++c) t += acc[i][j][r][c][0] + acc[i][j][r][c][1] + acc[i][j][r][c][2] + acc[i][j][r][c][3];
-    if (t == 123.25f) ep.y[0] = 1;
-    return;
-  }
   const float nwv = (act.on && act.noise) ? act.nw[0] : 0.f;
   // a plain stride-1 convolution writes anchor row r to pixel r: no decode of (sample, y, x) per row -- eight of them per lane were a
   // quarter of this stage's instructions; the sample index is only needed for the per-sample column scale
@@ -404,7 +368,7 @@ __global__ void __launch_bounds__(512) conv_bf16_8ph_kernel(ConvSetB set, EpActB
           uint2 v;
           v.x = *reinterpret_cast<const uint32_t*>(&lo);
           v.y = *reinterpret_cast<const uint32_t*>(&hi);
-          if (!(FMI_8P_EXP & 16) || M < 0) *reinterpret_cast<uint2*>(ep.y + off + col) = v;
+          *reinterpret_cast<uint2*>(ep.y + off + col) = v;
         }
       }
     }

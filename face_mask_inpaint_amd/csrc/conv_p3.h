@@ -17,9 +17,6 @@
 #pragma once
 #include "gemm_core.h"
 
-#ifndef FMI_P3_EXP
-#define FMI_P3_EXP 0  // timing experiments (wrong results): 1 A copies read the zero chunk, 2 B copies read the zero chunk, 4 no MFMAs, 8 no LDS reads in the loop, 16 no barrier
-#endif
 #ifndef FMI_HOST_EMU
 struct ConvK3 {  // A operand: gathered pixels x (tap, 16-channel group) from a p3 image
   const uint16_t* p3;
@@ -170,14 +167,14 @@ __global__ void __launch_bounds__(256) gemm_p3_kernel(ConvK3 la, ConvWX3 lb, Con
     for (int j = 0; j < NLA; ++j) {
       if (j >= na_w) break;
       const void* g = la.chunk(da[j], ta);
-      if (!g || (FMI_P3_EXP & 1)) g = zchunk;
+      if (!g) g = zchunk;
       glds16_p3(g, sa + j * 4096);
     }
 #pragma unroll
     for (int j = 0; j < NLB; ++j) {
       if (j >= nb_w) break;
       const void* g = lb.chunk(db[j], tb);
-      if (!g || (FMI_P3_EXP & 2)) g = zchunk;
+      if (!g) g = zchunk;
       glds16_p3(g, sb + j * 4096);
     }
   };
@@ -185,10 +182,6 @@ __global__ void __launch_bounds__(256) gemm_p3_kernel(ConvK3 la, ConvWX3 lb, Con
     const unsigned char* sa = lds + st * STAGE;
     const unsigned char* sb = sa + ABYTES;
     bf16x8_t pa[T::TM][3], pb[T::TN][3];
-#if FMI_P3_EXP & 8
-    for (int i = 0; i < T::TM; ++i) for (int pc = 0; pc < 3; ++pc) for (int e = 0; e < 8; ++e) pa[i][pc][e] = (__bf16)(float)(st + i + pc);
-    for (int j = 0; j < T::TN; ++j) for (int pc = 0; pc < 3; ++pc) for (int e = 0; e < 8; ++e) pb[j][pc][e] = (__bf16)(float)(st + j + pc);
-#else
 #pragma unroll
     for (int i = 0; i < T::TM; ++i) {
       const int r = wm + i * 32 + l31;
@@ -200,20 +193,10 @@ __global__ void __launch_bounds__(256) gemm_p3_kernel(ConvK3 la, ConvWX3 lb, Con
     for (int j = 0; j < T::TN; ++j)
 #pragma unroll
       for (int pc = 0; pc < 3; ++pc) pb[j][pc] = *reinterpret_cast<const bf16x8_t*>(sb + pc * (2 * BN * 16) + (lh * BN + wn + j * 32 + l31) * 16);
-#endif
-#if FMI_P3_EXP & 4
-#pragma unroll
-    for (int i = 0; i < T::TM; ++i)
-#pragma unroll
-      for (int j = 0; j < T::TN; ++j)
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc) acc[i][j][pc] += (float)pa[i][pc][0] * (float)pb[j][pc][0];
-#else
 #pragma unroll
     for (int i = 0; i < T::TM; ++i)
 #pragma unroll
       for (int j = 0; j < T::TN; ++j) acc[i][j] = mfma_x6(pa[i], pb[j], acc[i][j]);
-#endif
   };
 
   const int nt = (k_end - k_begin + BK - 1) / BK;
@@ -223,9 +206,7 @@ __global__ void __launch_bounds__(256) gemm_p3_kernel(ConvK3 la, ConvWX3 lb, Con
   if constexpr (FL) p3_acc_clear<T>(acc2);
   for (int t = 0; t < nt; ++t) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's copies of tile t have landed
-#if !(FMI_P3_EXP & 16)
     __builtin_amdgcn_s_barrier();
-#endif
     asm volatile("" ::: "memory");
     if (t + 1 < nt) issue(k_begin + (t + 1) * BK, st ^ 1);
     compute(st);
@@ -258,24 +239,16 @@ static int launch_gemm_p3(const ConvK3& la, const ConvWX3& lb, const ConvEp& ep,
       hipLaunchKernelGGL((gemm_p3_kernel<TILE>), dim3((unsigned)(tm * tn), (unsigned)ksplit), dim3(256), 0, st, la, lb, ep, M, N, K, (int)tn, ksplit, \
                          kchunk);                                                                                                              \
   } while (0)
-  auto wgs = [&](int bm, int bn) { return ceil_div64(M, bm) * ceil_div64(N, bn) * ksplit; };
   // blocked accumulation (a second accumulator set: ~64 registers, an occupancy step for the 128 x 128 tile) where one workgroup adds more
   // than ~600 products in a row AND the run asks for it: the reproducible mode, where no split reduction blocks the sum for us
-  const bool fl = kchunk > 640 && (fmi_det() || fmi_blocked_acc());
-  static const int tile_dbg = getenv("FMI_P3_TILE") ? atoi(getenv("FMI_P3_TILE")) : 0;  // experiment: force a tile
-  if (tile_dbg == 1) { P3_LAUNCH(Tile128x128); return fmi_launch_status(); }
-  if (tile_dbg == 2) { P3_LAUNCH(Tile64x128); return fmi_launch_status(); }
-  if (tile_dbg == 3) { P3_LAUNCH(Tile128x64); return fmi_launch_status(); }
-  if (N <= 32) {
-    P3_LAUNCH(Tile128x32);
-  } else if (N <= 64) {
-    if (M > 64 && wgs(128, 64) >= 384) P3_LAUNCH(Tile128x64);
-    else P3_LAUNCH(Tile64x64);
-  } else {
-    if (M > 64 && wgs(128, 128) >= 800) P3_LAUNCH(Tile128x128);
-    else if (M > 32 && wgs(64, 128) >= 384) P3_LAUNCH(Tile64x128);
-    else if (M > 64 && wgs(32, 128) < 256) P3_LAUNCH(Tile64x128);
-    else P3_LAUNCH(Tile32x128);
+  const bool fl = kchunk > 640 && fmi_det();
+  switch (pick_gemm_tile(M, N, ksplit)) {
+    case GemmTile::t128x32: P3_LAUNCH(Tile128x32); break;
+    case GemmTile::t128x64: P3_LAUNCH(Tile128x64); break;
+    case GemmTile::t64x64: P3_LAUNCH(Tile64x64); break;
+    case GemmTile::t128x128: P3_LAUNCH(Tile128x128); break;
+    case GemmTile::t64x128: P3_LAUNCH(Tile64x128); break;
+    case GemmTile::t32x128: P3_LAUNCH(Tile32x128); break;
   }
 #undef P3_LAUNCH
   return fmi_launch_status();
@@ -477,16 +450,14 @@ static int launch_conv3x3_p3(const C3P3Args& a, const ConvEp& ep, int M, int ksp
                          ksplit, it_chunk);                                                                                                        \
   } while (0)
   auto wgs = [&](int bm, int bn) { return ceil_div64(M, bm) * ceil_div64(a.Nout, bn) * ksplit; };
-  static const int tile_dbg = getenv("FMI_C3P3_TILE") ? atoi(getenv("FMI_C3P3_TILE")) : 0;  // experiment: force a tile
   const int N = a.Nout;
   // blocked accumulation: the eight-wave tiles hold one workgroup per CU (LDS) at 150 of 256 registers -- the second accumulator set is
-  // free there, so every long reduction takes it; the four-wave tiles only on request (occupancy)
+  // free there, so every long reduction takes it; the four-wave tiles only in the reproducible mode (occupancy)
   const bool long_red = it_chunk > 13;
   int pick;
-  if (tile_dbg) pick = tile_dbg;
-  else if (N > 64) pick = wgs(256, 128) >= 256 ? 1 : 3;
+  if (N > 64) pick = wgs(256, 128) >= 256 ? 1 : 3;
   else pick = wgs(256, 64) >= 256 ? 2 : 4;
-  const bool fl = long_red && (pick <= 2 || fmi_det() || fmi_blocked_acc());
+  const bool fl = long_red && (pick <= 2 || fmi_det());
   if (pick == 1) C3P3_LAUNCH(C3P3_256x128);
   else if (pick == 2) C3P3_LAUNCH(C3P3_256x64);
   else if (pick == 3) C3P3_LAUNCH(C3P3_128x128);
@@ -671,7 +642,6 @@ __global__ void __launch_bounds__(T::NW * 64) wgrad_p3_kernel(WgP3Args a, int ti
 using WG3_128x128 = P3Tile<2, 2, 2, 2>;
 using WG3_128x64 = P3Tile<2, 2, 2, 1>;
 using WG3_128x32 = P3Tile<4, 1, 1, 1>;
-using WG3_256x128 = P3Tile<4, 2, 2, 2>;  // 8 waves
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // 3 x 3 stride-1 zero-padded weight gradient with TAP REUSE along x.  The kernel above stages x once per tap: a 128 x 128 tile moves
@@ -949,8 +919,7 @@ static int launch_wgrad_p3(const fmi_conv_desc* d, const uint16_t* x3, const uin
   g.kh0 = 0; g.kw0 = 0; g.khstep = 1; g.kwstep = 1; g.kw = d->kw;
   g.dGW = make_fastdiv(g.GW); g.dG = make_fastdiv(g.GH * g.GW); g.dC = make_fastdiv(g.C); g.dntx = make_fastdiv(g.ntx);
   a.Kout = d->K; a.Mrows = d->kh * d->kw * d->C; a.P = d->N * d->OH * d->OW;
-  static const int tile_dbg = getenv("FMI_WG3_TILE") ? atoi(getenv("FMI_WG3_TILE")) : 0;  // experiment: 1 = the 8-wave 256 x 128 tile, 2 = never the tap-reuse kernel
-  if (tile_dbg != 2 && wgrad3x3_p3_ok(d)) {
+  if (wgrad3x3_p3_ok(d)) {
     Wg3x3Args w{};
     w.x3 = x3; w.dy3 = dy3; w.dwf = dwf;
     w.H = d->H; w.W = d->W; w.C = d->C; w.Kout = d->K; w.P = d->N * d->H * d->W;
@@ -971,7 +940,7 @@ static int launch_wgrad_p3(const fmi_conv_desc* d, const uint16_t* x3, const uin
     const int64_t nwg3 = w.xcd_splits ? tm3 * tn3 * ceil_div64(ks, 8) * 8 : tm3 * tn3;
     if (nwg3 > 0x7fffffffLL) return FMI_ERR_UNSUPPORTED;
     const dim3 grid3((unsigned)nwg3, w.xcd_splits ? 1u : (unsigned)ks);
-    const bool fl3 = w.kchunk > 640 && (fmi_det() || fmi_blocked_acc());
+    const bool fl3 = w.kchunk > 640 && fmi_det();
 #define WG3X3_LAUNCH(GA_, TN_)                                                                                 \
   do {                                                                                                         \
     if (fl3) hipLaunchKernelGGL((wgrad3x3_p3_kernel<GA_, TN_, true>), grid3, dim3(256), 0, st, w, (int)tn3);   \
@@ -982,10 +951,8 @@ static int launch_wgrad_p3(const fmi_conv_desc* d, const uint16_t* x3, const uin
 #undef WG3X3_LAUNCH
     return fmi_launch_status();
   }
-  const bool big = tile_dbg == 1 && d->K > 64;
-  const int bm = big ? 256 : 128;
   const int bn = d->K <= 32 ? 32 : (d->K <= 64 ? 64 : 128);
-  const int64_t tm = ceil_div64(a.Mrows, bm), tn = ceil_div64(d->K, bn);
+  const int64_t tm = ceil_div64(a.Mrows, 128), tn = ceil_div64(d->K, bn);
   int64_t ksplit = 2048 / (tm * tn);
   const int64_t kmax = a.P / 512;
   if (ksplit > kmax) ksplit = kmax;
@@ -1001,14 +968,13 @@ static int launch_wgrad_p3(const fmi_conv_desc* d, const uint16_t* x3, const uin
   const int64_t nwg = a.xcd_splits ? tm * tn * ceil_div64(ksplit, 8) * 8 : tm * tn;
   if (nwg > 0x7fffffffLL) return FMI_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)nwg, a.xcd_splits ? 1u : (unsigned)ksplit);
-  const bool fl = a.kchunk > 640 && (fmi_det() || fmi_blocked_acc());  // blocked accumulation of a long unsplit pixel reduction
+  const bool fl = a.kchunk > 640 && fmi_det();  // blocked accumulation of a long unsplit pixel reduction
 #define WG3_LAUNCH(TILE, NT)                                                                              \
   do {                                                                                                    \
     if (fl) hipLaunchKernelGGL((wgrad_p3_kernel<TILE, true>), grid, dim3(NT), 0, st, a, (int)tn);         \
     else hipLaunchKernelGGL((wgrad_p3_kernel<TILE>), grid, dim3(NT), 0, st, a, (int)tn);                  \
   } while (0)
-  if (big) WG3_LAUNCH(WG3_256x128, 512);
-  else if (bn == 32) WG3_LAUNCH(WG3_128x32, 256);
+  if (bn == 32) WG3_LAUNCH(WG3_128x32, 256);
   else if (bn == 64) WG3_LAUNCH(WG3_128x64, 256);
   else WG3_LAUNCH(WG3_128x128, 256);
 #undef WG3_LAUNCH

@@ -46,10 +46,6 @@ __host__ __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) 
   return (t + ((n - t) >> f.s1)) >> f.s2;
 }
 
-#ifndef FMI_EXP
-#define FMI_EXP 0  // bit mask of timing experiments (results become wrong): 1 no barrier, 2 no global loads, 4 no LDS stores in the main loop, 8 loads re-read the first tile; 16 = prefetch distance 2 (results stay right)
-#endif
-
 // ---- tile configurations ----
 template <int WM_, int WN_, int TM_, int TN_>
 struct TileCfg {
@@ -317,7 +313,7 @@ struct ConvWX3 {
   struct Ctx {};
   __device__ __forceinline__ void set_batch(int) {}
   __device__ __forceinline__ Ctx prep(int) const { return Ctx{}; }
-  // register-staged path (FMI_DMA_OFF / FMI_DMA_OFF_RANGE / FMI_EXP & 32 debugging, or a loader pair without LDS-DMA): the fp32 weight is
+  // register-staged path (FMI_DMA_OFF / FMI_DMA_OFF_RANGE debugging, or a loader pair without LDS-DMA): the fp32 weight is
   // the exact sum of its three pieces, added from the smallest up
   __device__ __forceinline__ float elem(int x, int k) const {
     const int t = (int)fdiv((uint32_t)k, g.dC);
@@ -625,9 +621,7 @@ static __device__ __attribute__((aligned(16))) float fmi_chunk_zero[4] = {0.f, 0
 // the issue section of conv3x3_p3_kernel, and (the counter is shared) a wait for every LDS read in flight wherever reads precede it.
 __device__ __forceinline__ const float* fmi_zero_chunk_ptr() {
   const float* p = fmi_chunk_zero;
-#ifndef FMI_ZCHUNK_NOPIN  // A/B build: the address re-materialised at every use, as before
   asm volatile("" : "+s"(p));
-#endif
   return p;
 }
 static __device__ __attribute__((aligned(16))) float fmi_chunk_one[4] = {1.f, 0.f, 0.f, 0.f};
@@ -717,9 +711,6 @@ __global__ void __launch_bounds__(256) gemm_mfma_f32_kernel(LA la, LB lb, EP ep,
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
   float4 ra0[NLA], rb0[NLB];
-#if FMI_EXP & 16
-  float4 ra1[NLA], rb1[NLB];
-#endif
   auto gload = [&](float4 (&ra)[NLA], float4 (&rb)[NLB], int k0) {
 #pragma unroll
     for (int j = 0; j < NLA; ++j) ra[j] = aact[j] ? la.load4(ca[j], m0 + ax[j], k0 + ak[j]) : zero4();
@@ -803,42 +794,16 @@ __global__ void __launch_bounds__(256) gemm_mfma_f32_kernel(LA la, LB lb, EP ep,
     gload(ra0, rb0, k_begin);
     lstore(ra0, rb0, 0);
   }
-#if FMI_EXP & 16
-  // two register sets: the loads of tile t+2 are issued before tile t is computed (prefetch distance 2)
-  if (k_begin + BK < k_end) gload(ra1, rb1, k_begin + BK);
-  __syncthreads();
-  int buf = 0;
-  for (int k0 = k_begin; k0 < k_end; k0 += 2 * BK) {
-    if (k0 + 2 * BK < k_end) gload(ra0, rb0, k0 + 2 * BK);
-    compute(buf);
-    if (k0 + BK < k_end) lstore(ra1, rb1, buf ^ 1);
-    __syncthreads();
-    buf ^= 1;
-    if (k0 + BK >= k_end) break;
-    if (k0 + 3 * BK < k_end) gload(ra1, rb1, k0 + 3 * BK);
-    compute(buf);
-    if (k0 + 2 * BK < k_end) lstore(ra0, rb0, buf ^ 1);
-    __syncthreads();
-    buf ^= 1;
-  }
-#else
   __syncthreads();
   int buf = 0;
   for (int k0 = k_begin; k0 < k_end; k0 += BK) {
     const bool more = k0 + BK < k_end;
-#if !(FMI_EXP & 2)
-    if (more) gload(ra0, rb0, (FMI_EXP & 8) ? k_begin : k0 + BK);
-#endif
+    if (more) gload(ra0, rb0, k0 + BK);
     compute(buf);
-#if !(FMI_EXP & 4)
     if (more) lstore(ra0, rb0, buf ^ 1);
-#endif
-#if !(FMI_EXP & 1)
     __syncthreads();
-#endif
     buf ^= 1;
   }
-#endif
 
   store_tile<EP, T>(ep, acc, M, N, m0 + wm, n0 + wn, lh, l31);
 }
@@ -847,7 +812,7 @@ __global__ void __launch_bounds__(256) gemm_mfma_f32_kernel(LA la, LB lb, EP ep,
 // LDS-DMA pipeline (the default whenever both operands can be fetched in aligned 16-byte chunks).
 //
 // Operand tiles go global -> LDS directly (global_load_lds_dwordx4: no staging registers, no ds_write) into a ring of
-// FMI_NST 16-deep stages: the copies of tile t+FMI_NST-1 are issued right after the barrier that opens tile t, so a copy
+// NST = 2 16-deep stages: the copies of tile t+NST-1 are issued right after the barrier that opens tile t, so a copy
 // has a whole MFMA phase (~2048 cycles per wave, x the 3 workgroups that share a CU) to land.  The register-staged kernel
 // above exposes about half of the global-load latency and pays ~15 % in staging instructions (ablation table in
 // DESIGN.md).  Measured: 2 stages = 3 stages (125 vs 126 TFLOP/s at 4096^3) and better on narrow tiles (less LDS, more
@@ -863,9 +828,6 @@ __global__ void __launch_bounds__(256) gemm_mfma_f32_kernel(LA la, LB lb, EP ep,
 // Synchronisation: one raw s_barrier per tile.  Before it every wave waits (counted vmcnt) for its own copies of tile t;
 // after it the stage read one tile ago is free (all waves finished its ds_reads before arriving) and is refilled.
 // =====================================================================================
-#ifndef FMI_DMA_ATTR
-#define FMI_DMA_ATTR
-#endif
 template <class L, class = void>
 struct is_split3 : std::false_type {};
 template <class L>
@@ -874,13 +836,10 @@ struct is_split3<L, std::void_t<decltype(L::SPLIT3)>> : std::integral_constant<b
 // FL: blocked accumulation -- a second accumulator set, flushed every 32 tiles (512 reduction elements), so that a long unsplit
 // reduction is a sum of short fp32 chains (conv_p3.h)
 template <class LA, class LB, class EP, class T, bool FL = false>
-__global__ void __launch_bounds__(256) FMI_DMA_ATTR gemm_dma_f32_kernel(LA la, LB lb, EP ep, int M, int N, int K, int tiles_n,
+__global__ void __launch_bounds__(256) gemm_dma_f32_kernel(LA la, LB lb, EP ep, int M, int N, int K, int tiles_n,
                                                            int ksplit, int kchunk) {
   const float* const zchunk = fmi_zero_chunk_ptr();  // the zero chunk's address: read from the GOT ONCE (see fmi_zero_chunk_ptr)
-  #ifndef FMI_NST
-#define FMI_NST 2
-#endif
-  constexpr int BM = T::BM, BN = T::BN, BK = 16, NST = FMI_NST, DEPTH = NST - 1;  // DEPTH tiles are copied ahead of the one computed
+  constexpr int BM = T::BM, BN = T::BN, BK = 16, NST = 2, DEPTH = NST - 1;  // DEPTH tiles are copied ahead of the one computed
   // copies: a tile image has BX*4 16-byte chunks = BX/16 wave instructions; wave w issues instructions w, w+4, ...
   constexpr bool B3 = is_split3<LB>::value;  // B arrives as three bf16 piece images [2 channel groups][BN] x 16 bytes
   constexpr int NIB3 = 3 * BN / 32;         // wave instructions of the three piece images of a tile
@@ -1091,13 +1050,7 @@ __global__ void __launch_bounds__(256) FMI_DMA_ATTR gemm_dma_f32_kernel(LA la, L
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (t + DEPTH < nt) issue(k_begin + (t + DEPTH) * BK, stn);
-#if FMI_EXP & 64
-    __builtin_amdgcn_s_setprio(1);
-#endif
     compute(st);
-#if FMI_EXP & 64
-    __builtin_amdgcn_s_setprio(0);
-#endif
     st = st == NST - 1 ? 0 : st + 1;
     stn = stn == NST - 1 ? 0 : stn + 1;
     if constexpr (FL) {
@@ -1124,6 +1077,22 @@ __global__ void __launch_bounds__(256) FMI_DMA_ATTR gemm_dma_f32_kernel(LA la, L
   store_tile<EP, T>(ep, acc, M, N, m0 + wm, n0 + wn, lh, l31);
 }
 
+// Tile of the generic GEMM launchers (launch_gemm here, launch_gemm_p3 in conv_p3.h) for an M x N output with z workgroups per output
+// tile (batch x reduction splits): the largest tile that still gives ~1.5 workgroups per CU; small problems trade operand reuse for
+// occupancy.
+enum class GemmTile { t128x32, t128x64, t64x64, t128x128, t64x128, t32x128 };
+static GemmTile pick_gemm_tile(int M, int N, int64_t z) {
+  auto wgs = [&](int bm, int bn) { return ceil_div64(M, bm) * ceil_div64(N, bn) * z; };
+  const int64_t want = 384, want128 = 800;  // 128x128 only from ~one full round of workgroups (3 per CU) up: below that the
+                                           // fullest CUs set the time and the 64x128 tile balances better (measured: -0.7 ms per step)
+  if (N <= 32) return GemmTile::t128x32;
+  if (N <= 64) return (M > 64 && wgs(128, 64) >= want) ? GemmTile::t128x64 : GemmTile::t64x64;
+  if (M > 64 && wgs(128, 128) >= want128) return GemmTile::t128x128;
+  if (M > 32 && wgs(64, 128) >= want) return GemmTile::t64x128;
+  if (M > 64 && wgs(32, 128) < 256) return GemmTile::t64x128;
+  return GemmTile::t32x128;
+}
+
 // Host-side launcher: picks the tile from N (and M), validates the 32-bit index ranges the kernel assumes.
 template <class LA, class LB, class EP>
 static int launch_gemm(const LA& la, const LB& lb, const EP& ep, int M, int N, int K, int batch, int ksplit,
@@ -1141,7 +1110,7 @@ static int launch_gemm(const LA& la, const LB& lb, const EP& ep, int M, int N, i
   // FMI_DMA_OFF (debug): bit 0 dense GEMM, bit 1 conv forward / adjoint, bit 2 weight gradient -> use the register-staged kernel
   static const int dma_off = getenv("FMI_DMA_OFF") ? atoi(getenv("FMI_DMA_OFF")) : 0;
   const int family = std::is_same<LA, ConvK>::value ? 2 : (std::is_same<LA, WgradAX>::value ? 4 : 1);
-  bool dma = !(FMI_EXP & 32) && !(dma_off & family) && la.dma_ok() && lb.dma_ok();
+  bool dma = !(dma_off & family) && la.dma_ok() && lb.dma_ok();
   if (const char* r = getenv("FMI_DMA_OFF_RANGE")) {  // debug: "a:b" = launches a <= i < b of this process use the register-staged kernel
     long a = 0, b = 0;
     sscanf(r, "%ld:%ld", &a, &b);
@@ -1149,7 +1118,7 @@ static int launch_gemm(const LA& la, const LB& lb, const EP& ep, int M, int N, i
     if (i >= a && i < b) dma = false;
     if (getenv("FMI_DMA_TRACE")) fprintf(stderr, "[fmi launch %ld] family %d M %d N %d K %d batch %d ksplit %d dma %d (eligible %d %d)\n", i, family, M, N, K, batch, ksplit, (int)dma, (int)la.dma_ok(), (int)lb.dma_ok());
   }
-  const bool fl = kchunk > 640 && (fmi_det() || fmi_blocked_acc());  // blocked accumulation of a long unsplit reduction (LDS-DMA kernel)
+  const bool fl = kchunk > 640 && fmi_det();  // blocked accumulation of a long unsplit reduction (LDS-DMA kernel)
 #define FMI_LAUNCH(TILE)                                                                                      \
   do {                                                                                                        \
     const int64_t tm = ceil_div64(M, TILE::BM), tn = ceil_div64(N, TILE::BN);                                 \
@@ -1169,21 +1138,13 @@ static int launch_gemm(const LA& la, const LB& lb, const EP& ep, int M, int N, i
     hipLaunchKernelGGL((gemm_mfma_f32_kernel<LA, LB, EP, TILE>), dim3((unsigned)(tm * tn), (unsigned)gy), dim3(256), \
                        0, st, la, lb, ep, M, N, K, (int)tn, ksplit, kchunk);                                  \
   } while (0)
-  // largest tile that still gives ~1.5 workgroups per CU; small problems trade operand reuse for occupancy
-  const int64_t zs = gy;
-  auto wgs = [&](int bm, int bn) { return ceil_div64(M, bm) * ceil_div64(N, bn) * zs; };
-  const int64_t want = 384, want128 = 800;  // 128x128 only from ~one full round of workgroups (3 per CU) up: below that the
-                                           // fullest CUs set the time and the 64x128 tile balances better (measured: -0.7 ms per step)
-  if (N <= 32) {
-    FMI_LAUNCH(Tile128x32);
-  } else if (N <= 64) {
-    if (M > 64 && wgs(128, 64) >= want) FMI_LAUNCH(Tile128x64);
-    else FMI_LAUNCH(Tile64x64);
-  } else {
-    if (M > 64 && wgs(128, 128) >= want128) FMI_LAUNCH(Tile128x128);
-    else if (M > 32 && wgs(64, 128) >= want) FMI_LAUNCH(Tile64x128);
-    else if (M > 64 && wgs(32, 128) < 256) FMI_LAUNCH(Tile64x128);
-    else FMI_LAUNCH(Tile32x128);
+  switch (pick_gemm_tile(M, N, gy)) {
+    case GemmTile::t128x32: FMI_LAUNCH(Tile128x32); break;
+    case GemmTile::t128x64: FMI_LAUNCH(Tile128x64); break;
+    case GemmTile::t64x64: FMI_LAUNCH(Tile64x64); break;
+    case GemmTile::t128x128: FMI_LAUNCH(Tile128x128); break;
+    case GemmTile::t64x128: FMI_LAUNCH(Tile64x128); break;
+    case GemmTile::t32x128: FMI_LAUNCH(Tile32x128); break;
   }
 #undef FMI_LAUNCH
   return fmi_launch_status();

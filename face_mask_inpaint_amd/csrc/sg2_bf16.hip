@@ -528,8 +528,6 @@ extern "C" int fmi_internal_fir_run_launch(const void* in, const float* kernel, 
   const int R = bf16 ? 4 : 8;
   const int64_t tv = (int64_t)N * ((out_h + R - 1) / R) * ((out_w + 1) / 2) * CV;
   if (tv >= (1ll << 31) || out_h < 2 * R) return 0;
-  static const bool off = getenv("FMI_FIR_RUN_OFF") != nullptr;
-  if (off) return 0;
   const int grid = fmi_bw_grid(tv, 256);
   hipStream_t st = (hipStream_t)stream;
 #define RUN_LAUNCH(K_, BF_)                                                                                                          \

@@ -28,10 +28,6 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
 }
 __device__ __forceinline__ void split3_pair(float a, float b, uint32_t& q0, uint32_t& q1, uint32_t& q2) {
   q0 = cvt_pk_bf16(a, b);
-#if FMI_X6 == 2  // timing experiment: no split arithmetic (wrong results)
-  q1 = __float_as_uint(a), q2 = __float_as_uint(b);
-  return;
-#endif
   const float ra = a - __uint_as_float(q0 << 16), rb = b - __uint_as_float(q0 & 0xFFFF0000u);
   q1 = cvt_pk_bf16(ra, rb);
   const float sa = ra - __uint_as_float(q1 << 16), sb = rb - __uint_as_float(q1 & 0xFFFF0000u);
@@ -50,11 +46,6 @@ __device__ __forceinline__ void split3_bf16(const float (&f)[8], bf16x8_t (&p)[3
   p[2] = __builtin_bit_cast(bf16x8_t, q2);
 }
 __device__ __forceinline__ f32x16 mfma_x6(const bf16x8_t (&a)[3], const bf16x8_t (&b)[3], f32x16 c) {
-#if FMI_X6 == 3  // timing experiment: one product per pair (wrong results)
-  bf16x8_t a0 = a[0], b0 = b[0];
-  for (int e = 0; e < 8; ++e) a0[e] += a[1][e] + a[2][e], b0[e] += b[1][e] + b[2][e];
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, c, 0, 0, 0);
-#endif
   c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);

@@ -9,7 +9,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -177,8 +176,8 @@ def conv_desc(n, h, w, c, k, kh, kw, stride, pad, pad_mode=0, x_cs=None, y_cs=No
 # ---------------------------------------------------------------------------------------------------
 P3_ENABLED = True
 P3_MIN_PIXELS = 16384  # smaller feature maps are launch / latency bound: the in-wave split costs nothing there
-P3_MIN_WORK = int(os.environ.get("FMI_P3_MIN_WORK", "1152"))  # taps * output channels per activation element below which a split pass costs more than it returns
-P3_MIN_COUT = int(os.environ.get("FMI_P3_MIN_COUT", "64"))    # (both overridable for A/B runs: tools/bench_tools/README.md)
+P3_MIN_WORK = 1152  # taps * output channels per activation element below which a split pass costs more than it returns
+P3_MIN_COUT = 64
 
 
 def p3_wanted(pixels: int, cred: int, cout: int, taps: int) -> bool:
@@ -894,8 +893,6 @@ class _ConvTransposePair(torch.autograd.Function):
 def conv_transpose2d_pair_ok(x1, pw1: PackedWeight, x2, pw2: PackedWeight) -> bool:
     """the shapes fmi_conv_transpose2d_pair_f32 takes: fp32, thin outputs on a large map (convt3x3.h)"""
     if x1.dtype != torch.float32 or x2.dtype != torch.float32 or not x1.is_cuda or x1.shape[:3] != x2.shape[:3]:
-        return False
-    if os.environ.get("FMI_CT3_OFF"):
         return False
     n, h, w, cs1 = x1.shape
     cs2, cb = x2.shape[3], pw1.wf.shape[1]
@@ -1717,8 +1714,8 @@ def linear(x, w, bias=None, alpha=1.0):
 
 
 def _scale_bwd_ok(g, x, s, c):
-    """shapes the one-pass adjoint (fmi_scale_channels_bwd_f32) takes; off with FMI_SCALE_BWD_FUSED=0 (A/B)"""
-    return (_SCALE_BWD_FUSED and g.dtype == torch.float32 and c % 4 == 0 and c <= 1024 and g.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and
+    """shapes the one-pass adjoint (fmi_scale_channels_bwd_f32) takes"""
+    return (g.dtype == torch.float32 and c % 4 == 0 and c <= 1024 and g.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and
             s.data_ptr() % 16 == 0)
 
 
@@ -1727,9 +1724,6 @@ def _scale_channels_bwd(g, x, s, n, p, c):
     ws = _parts_ws(x.device, max(4096, n) * c)
     _L().scale_channels_bwd_f32(_p(g), _p(x), _p(s), _p(gx), _p(gs), _p(ws), ws.numel(), n, p, c, _st())
     return gx, gs
-
-
-_SCALE_BWD_FUSED = os.environ.get("FMI_SCALE_BWD_FUSED", "1") != "0"
 
 
 class _ScaleChannels(torch.autograd.Function):

@@ -11,7 +11,6 @@ go through ONE GEMM.  Public forwards take / return NCHW-shaped tensors; ``nhwc`
 from __future__ import annotations
 
 import math
-import os
 import random
 
 import torch
@@ -200,7 +199,7 @@ class ConstantInput(nn.Module):
         return self.input.repeat(input.shape[0], 1, 1, 1)
 
 
-FUSE_STYLED = os.environ.get("FMI_FUSE_STYLED", "1") != "0"  # bf16 decoder: StyledConv output stages fused into the convolution / the Blur (off: the separate passes)
+FUSE_STYLED = True  # bf16 decoder: StyledConv output stages fused into the convolution / the Blur (off: the separate passes)
 
 
 class StyledConv(nn.Module):

@@ -8,7 +8,7 @@ dev = torch.device("cuda:0")
 MODES = [int(m) for m in sys.argv[1:]] or [0]
 for mode in MODES:
   lib.debug_bf16_tile(mode)
-  print("FMI_BF16_TILE mode", mode, flush=True)
+  print("bf16 tile mode", mode, flush=True)
   for (n, c, k, h) in [(16, 512, 512, 64), (16, 256, 256, 128), (16, 128, 128, 256), (16, 512, 512, 32), (4, 64, 64, 512)]:
       d, oh, ow = FF.conv_desc(n, h, h, c, k, 3, 3, 1, 1, 0)
       x = torch.randn(n, h, h, c, device=dev).bfloat16()

@@ -1,4 +1,4 @@
-"""fp32 conv forward / adjoint at chosen shapes; FMI_KS=<n> overrides the reduction split"""
+"""fp32 conv forward / adjoint at chosen shapes"""
 import sys
 sys.path.insert(0, "/root/repo")
 sys.argv = [sys.argv[0], "none"]

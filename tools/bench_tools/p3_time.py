@@ -1,5 +1,5 @@
 """convolution forward with the activation operand as a bf16 piece image (fmi_conv_desc.x3) against the in-wave split:
-max difference of the results, TFLOP/s of both, and the cost of the standalone split pass.  FMI_P3_TILE=1/2/3 forces a tile."""
+max difference of the results, TFLOP/s of both, and the cost of the standalone split pass."""
 import ctypes as C, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from face_mask_inpaint_amd import functional as FF, _lib

@@ -1,4 +1,4 @@
-"""weight gradient with both operands as piece images (wgrad_p3_kernel): TFLOP/s per layer shape of the C2 step.  FMI_WG3_TILE=1 forces the 8-wave tile."""
+"""weight gradient with both operands as piece images (wgrad_p3_kernel): TFLOP/s per layer shape of the C2 step."""
 import ctypes as C, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from face_mask_inpaint_amd import functional as FF, _lib
