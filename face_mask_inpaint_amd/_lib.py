@@ -63,6 +63,7 @@ SIGNATURES = {
     "fmi_conv2d_thin_lrelu_dgrad_f32": [PD, vp, vp, vp, f32, vp, vp],
     "fmi_conv2d_thin_lrelu_wgrad_f32": [PD, vp, f32, vp, vp, vp, vp],
     "fmi_conv2d_thin_wgrad_f32": [PD, vp, vp, vp, vp, vp],
+    "fmi_conv2d_thin_lrelu_bwd_f32": [PD, vp, f32, vp, vp, vp, vp, vp, vp, vp, i64, vp],
     "fmi_conv2d_fwd_bf16": [PD, vp, vp, vp, vp, vp, i64, vp],
     "fmi_conv2d_dgrad_bf16": [PD, vp, vp, vp, vp, vp, i64, vp],
     "fmi_conv2d_wgrad_bf16": [PD, vp, vp, vp, vp],
@@ -165,7 +166,7 @@ SIGNATURES = {
 STATUS = {0: "ok", 1: "bad argument", 2: "unsupported shape/mode", 3: "kernel launch failed"}
 
 
-PREDICATES = {"fmi_debug_bf16_tile": [i32], "fmi_set_deterministic": [i32], "fmi_get_deterministic": [], "fmi_conv2d_thin_supported": [PD], "fmi_conv2d_bf16_supported": [PD], "fmi_conv2d_thin_lrelu_supported": [PD]}
+PREDICATES = {"fmi_debug_bf16_tile": [i32], "fmi_set_deterministic": [i32], "fmi_get_deterministic": [], "fmi_conv2d_thin_supported": [PD], "fmi_conv2d_bf16_supported": [PD], "fmi_conv2d_thin_lrelu_supported": [PD], "fmi_conv2d_thin_lrelu_bwd_ws_bytes": [PD]}
 
 
 class FmiError(RuntimeError):

@@ -12,6 +12,8 @@
 //   (forward and dgrad run as the 4x4x1-MFMA row-segment forms further down; the scalar per-pixel adjoint serves the border pass)
 //   wgrad   : per-lane accumulators [9][4][K] over a strided range of pixels, reduced over the wave's pixel groups by
 //             shuffles, over the workgroup's waves through LDS, over workgroups by fp32 atomics; dbias rides along.
+//   backward: when BOTH gradients of the fused block (LeakyReLU in front, tanh behind) are wanted they come out of one x-stationary pass
+//             (thin_lrelu_bwd_kernel further down): x read once, dx written once, no atomics.
 #include "common.h"
 #include <cstdlib>
 
@@ -327,79 +329,106 @@ __global__ void __launch_bounds__(256) thin_fwd_mfma_kernel(ThinArgs a, int qbit
 // fully coalesced 16-byte loads (8 consecutive lanes = one pixel's 128 bytes; the texture path is paced per wave instruction and
 // the gather of the row-segment kernel above -- 4 pixels x 16 B per MFMA block, 128 B apart -- costs it ~4x as many cycles per byte),
 // then every tap comes out of LDS as ds_read_b128 in the MFMA block layout.  Input bytes cross HBM/L2 1.33x instead of 9x.
+// Workgroups are persistent (one round of resident ones) and keep the window of their NEXT tile in flight during the arithmetic.
 constexpr int LT_H = 8, LT_W = 32, LT_PITCH = 36;  // pixel pitch in floats (32 channels + 4 pad: spreads the b128 reads over the banks)
 template <int K>
-__global__ void __launch_bounds__(256) thin_fwd_lds_kernel(ThinArgs a, int tiles_x, int tiles_y) {
+__global__ void __launch_bounds__(256) thin_fwd_lds_kernel(ThinArgs a, int tiles_x, int tiles_y, int ntiles) {
   __shared__ __attribute__((aligned(16))) float sx[(LT_H + 2) * (LT_W + 2) * LT_PITCH];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int i = lane & 3, q = (lane >> 2) & 7, g = lane >> 5;
-  int b = blockIdx.x;
-  const int tx = b % tiles_x;
-  b /= tiles_x;
-  const int ty = b % tiles_y, n = b / tiles_y;
-  const int y0 = ty * LT_H, x0 = tx * LT_W;
   float wr[9][4];  // A operand: w[t][4q+e][k = i]
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
     for (int e = 0; e < 4; ++e) wr[t][e] = i < K ? a.w[((int64_t)(a.flip ? 8 - t : t) * a.C + 4 * q + e) * K + i] : 0.f;
-  // stage the window: chunk c8 = tid & 7 of window pixel (tid >> 3) + 32 j
-  const float* img = a.x + (int64_t)n * a.H * a.W * a.xcs;
   constexpr int NPIX = (LT_H + 2) * (LT_W + 2), NLD = (NPIX + 31) / 32;
   float4 stage[NLD];  // all loads in flight before the first LDS store (a load-store-load chain would pay the latency NLD times)
+  // the window of a tile: chunk c8 = tid & 7 of window pixel (tid >> 3) + 32 j
+  auto load_window = [&](int tile) {
+    const int tx = tile % tiles_x;
+    tile /= tiles_x;
+    const int ty = tile % tiles_y, n = tile / tiles_y;
+    const int y0 = ty * LT_H, x0 = tx * LT_W;
+    const float* img = a.x + (int64_t)n * a.H * a.W * a.xcs;
 #pragma unroll
-  for (int j = 0; j < NLD; ++j) {
-    const int p = (tid >> 3) + 32 * j;
-    const int wy = p / (LT_W + 2), wx = p - wy * (LT_W + 2);
-    int iy = y0 + wy - 1, ix = x0 + wx - 1;
-    if (a.pad_mode) {
-      iy = reflect1(iy, a.H);
-      ix = reflect1(ix, a.W);
+    for (int j = 0; j < NLD; ++j) {
+      const int p = (tid >> 3) + 32 * j;
+      const int wy = p / (LT_W + 2), wx = p - wy * (LT_W + 2);
+      int iy = y0 + wy - 1, ix = x0 + wx - 1;
+      if (a.pad_mode) {
+        iy = reflect1(iy, a.H);
+        ix = reflect1(ix, a.W);
+      }
+      const bool ok = p < NPIX && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
+      stage[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (ok) stage[j] = *reinterpret_cast<const float4*>(img + ((int64_t)iy * a.W + ix) * a.xcs + 4 * (tid & 7));
     }
-    const bool ok = p < NPIX && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-    stage[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ok) stage[j] = *reinterpret_cast<const float4*>(img + ((int64_t)iy * a.W + ix) * a.xcs + 4 * (tid & 7));
-  }
-  if (a.in_slope != 1.f) {
+  };
+  // persistent workgroups: the loads of tile n+1 are issued before the arithmetic of tile n and land in registers while it runs
+  int tile = blockIdx.x;  // the host launches at most ntiles workgroups
+  load_window(tile);
+  while (true) {
+    if (a.in_slope != 1.f) {
 #pragma unroll
-    for (int j = 0; j < NLD; ++j) stage[j] = lrelu4(stage[j], a.in_slope);
-  }
+      for (int j = 0; j < NLD; ++j) stage[j] = lrelu4(stage[j], a.in_slope);
+    }
 #pragma unroll
-  for (int j = 0; j < NLD; ++j) {
-    const int p = (tid >> 3) + 32 * j;
-    if (p < NPIX) *reinterpret_cast<float4*>(sx + p * LT_PITCH + 4 * (tid & 7)) = stage[j];
-  }
-  __syncthreads();
-  // wave `wid` owns tile rows 2*wid, 2*wid+1; an iteration = 8 consecutive pixels of a row (2 groups x 4)
+    for (int j = 0; j < NLD; ++j) {
+      const int p = (tid >> 3) + 32 * j;
+      if (p < NPIX) *reinterpret_cast<float4*>(sx + p * LT_PITCH + 4 * (tid & 7)) = stage[j];
+    }
+    __syncthreads();
+    int b = tile;
+    const int tx = b % tiles_x;
+    b /= tiles_x;
+    const int ty = b % tiles_y, n = b / tiles_y;
+    const int y0 = ty * LT_H, x0 = tx * LT_W;
+    const int next = tile + gridDim.x;
+    if (next < ntiles) load_window(next);
+    float fin[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) fin[k] = 0.f;
+    // wave `wid` owns tile rows 2*wid, 2*wid+1; an iteration = 8 consecutive pixels of a row (2 groups x 4)
 #pragma unroll 1
-  for (int it = 0; it < 8; ++it) {
-    const int ly = 2 * wid + (it >> 2), lx = (it & 3) * 8 + g * 4 + i;
-    const float* base = sx + (ly * (LT_W + 2) + lx) * LT_PITCH + 4 * q;
-    f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+    for (int it = 0; it < 8; ++it) {
+      const int ly = 2 * wid + (it >> 2), lx = (it & 3) * 8 + g * 4 + i;
+      const float* base = sx + (ly * (LT_W + 2) + lx) * LT_PITCH + 4 * q;
+      f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      const float4 v = *reinterpret_cast<const float4*>(base + ((t / 3) * (LT_W + 2) + (t % 3)) * LT_PITCH);
-      acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wr[t][0], v.x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wr[t][1], v.y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wr[t][2], v.z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wr[t][3], v.w, acc, 0, 0, 0);
+      for (int t = 0; t < 9; ++t) {
+        const float4 v = *reinterpret_cast<const float4*>(base + ((t / 3) * (LT_W + 2) + (t % 3)) * LT_PITCH);
+        acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wr[t][0], v.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wr[t][1], v.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wr[t][2], v.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_4x4x1f32(wr[t][3], v.w, acc, 0, 0, 0);
+      }
+#pragma unroll
+      for (int m = 4; m < 32; m <<= 1)
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc[k] += __shfl_xor(acc[k], m, 64);
+      // after the reduction every chunk lane holds the totals of the iteration's pixels: lane q keeps those of iteration q and
+      // finishes them (bias, residual, activation, store) ONCE per tile with all 64 lanes busy, instead of 3 of every 8 lanes per iteration
+#pragma unroll
+      for (int k = 0; k < K; ++k) fin[k] = it == q ? acc[k] : fin[k];
     }
+    {
+      const int oy = y0 + 2 * wid + (q >> 2), ox = x0 + (q & 3) * 8 + g * 4 + i;
+      if (oy < a.H && ox < a.W) {
+        const int64_t o = ((int64_t)(n * a.H + oy) * a.W + ox) * a.ycs;
 #pragma unroll
-    for (int m = 4; m < 32; m <<= 1)
-#pragma unroll
-      for (int k = 0; k < K; ++k) acc[k] += __shfl_xor(acc[k], m, 64);
-    const int oy = y0 + ly, ox = x0 + lx;
-    if (q < K && oy < a.H && ox < a.W) {  // after the reduction every chunk lane holds the totals: lane q finishes channel q
-      const int64_t o = ((int64_t)(n * a.H + oy) * a.W + ox) * a.ycs + q;
-      float r = acc[0];
-#pragma unroll
-      for (int k = 1; k < K; ++k) r = q == k ? acc[k] : r;
-      if (a.bias) r += a.bias[q];
-      if (a.res) r += a.res[o];
-      if (a.act == 1) r = tanhf(r);
-      else if (a.act == 2) r = fmaxf(r, 0.f);
-      a.y[o] = r;
+        for (int k = 0; k < K; ++k) {
+          float r = fin[k];
+          if (a.bias) r += a.bias[k];
+          if (a.res) r += a.res[o + k];
+          if (a.act == 1) r = tanhf(r);
+          else if (a.act == 2) r = fmaxf(r, 0.f);
+          a.y[o + k] = r;
+        }
+      }
     }
+    if (next >= ntiles) break;
+    tile = next;
+    __syncthreads();  // every wave is done with sx before the next window overwrites it
   }
 }
 
@@ -580,6 +609,380 @@ __global__ void __launch_bounds__(256) thin_dgrad_mfma_kernel(ThinArgs a, float*
   }
 }
 
+// =====================================================================================
+// One-pass backward of the Output block (C = 32): dx, dW and dbias from ONE read of x and ONE read of dy.
+// Both gradients need, per input pixel q, the same 9 x K numbers
+//   G[t][k] = sum of dy[p][k] over the output pixels p whose (padded) window has q at tap t,
+//   dx[q][c] = lrelu'(x[q][c]) * sum_t,k W[t][c][k] G[t][k],      dW[t][c][k] += lrelu(x[q][c]) * G[t][k].
+// In this x-stationary form x needs no halo: a lane loads its own 16 bytes (pixel, 4-channel chunk) once, a few iterations ahead, and
+// only the small dy window (tile + 1-pixel ring, 16 bytes per pixel) goes through LDS, double-buffered.  With tanh in front
+// (yt given) the window holds dy * (1 - y^2), which replaces the separate tanh-backward pass.  Out-of-image window cells are zero,
+// which IS zero padding; with reflect padding the fold is applied where the window is read: pixels of row 1 / H-2 (column 1 /
+// W-2) add the cell two rows (columns) further out to tap row (column) 0 / 2.  Only tiles that touch those rows / columns
+// need that (FOLD): they are walked by a second, small launch of the kernel, the interior tiles read one cell per tap.
+// Arithmetic on the 4x4x1 MFMA (lane = (pixel group g, chunk q, i), 8 pixels per wave and iteration, as the forward):
+//   adjoint : A[r] = wt[t][k][4q + r], B[i] = G(pixel i)[t][k]                -> acc[r] of lane i = dx[pixel i][4q + r]
+//   weights : per pixel P of the group, A[r] = G(P)[t][k = r], B[i] = lrelu(x[P][4q + i]) -> dw[t][r] of lane i = dW[t][4q + i][r]
+// The [9][4] accumulators stay in registers over all tiles of the persistent workgroup; every workgroup writes ONE row of
+// 9*C*K + K partial sums and thin_sum_rows_kernel adds the rows in a fixed order: no atomics, nothing to zero, bit-reproducible.
+// =====================================================================================
+constexpr int BW_W = LT_W + 2, BW_CELLS = (LT_H + 2) * (LT_W + 2), BW_LD = (BW_CELLS + 255) / 256;
+constexpr int BWD_MAX_ROWS = 2048;  // upper bound of the grid (= rows of the workspace)
+
+template <int P>
+__device__ __forceinline__ float quad_bcast(float v) {  // the value of lane P of every group of 4 lanes
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), P * 0x55, 0xf, 0xf, true));
+}
+
+struct FoldFlags {
+  bool y0, y2, x0, x2;  // the pixel is in row 1 / row H-2 / column 1 / column W-2 of a reflect-padded image
+};
+__device__ __forceinline__ FoldFlags fold_flags(int pad_mode, int oy, int ox, int H, int W) {
+  FoldFlags f;
+  f.y0 = pad_mode && oy == 1, f.y2 = pad_mode && oy == H - 2, f.x0 = pad_mode && ox == 1, f.x2 = pad_mode && ox == W - 2;
+  return f;
+}
+__device__ __forceinline__ float4 sel4(bool c, float4 v) { return c ? v : make_float4(0.f, 0.f, 0.f, 0.f); }
+__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+// G[t], t = (TY, TX), of the pixel whose own window cell (row ly + 1, column lx + 1) is one row and one column past `wp`:
+// cell (ly - TY + 2, lx - TX + 2) plus the folded ones.  All offsets are compile-time constants.
+template <bool FOLD, int TY, int TX>
+__device__ __forceinline__ float4 bwd_g4(const float4* wp, FoldFlags f) {
+  constexpr int o = (2 - TY) * BW_W + (2 - TX);
+  constexpr int dr = (TY == 0 ? -2 : 2) * BW_W, dc = TX == 0 ? -2 : 2;  // the folded cell: inside the window for TY, TX != 1
+  float4 v = wp[o];
+  if constexpr (FOLD) {
+    const bool ey = TY == 0 ? f.y0 : TY == 2 ? f.y2 : false, ex = TX == 0 ? f.x0 : TX == 2 ? f.x2 : false;
+    if constexpr (TY != 1) v = add4(v, sel4(ey, wp[o + dr]));
+    if constexpr (TX != 1) v = add4(v, sel4(ex, wp[o + dc]));
+    if constexpr (TY != 1 && TX != 1) v = add4(v, sel4(ey && ex, wp[o + dr + dc]));
+  }
+  return v;
+}
+// one component of the same: w1 = the float of that component in cell `wp`
+template <bool FOLD, int TY, int TX>
+__device__ __forceinline__ float bwd_g1(const float* w1, FoldFlags f) {
+  constexpr int o = 4 * ((2 - TY) * BW_W + (2 - TX));
+  constexpr int dr = 4 * (TY == 0 ? -2 : 2) * BW_W, dc = 4 * (TX == 0 ? -2 : 2);
+  float v = w1[o];
+  if constexpr (FOLD) {
+    const bool ey = TY == 0 ? f.y0 : TY == 2 ? f.y2 : false, ex = TX == 0 ? f.x0 : TX == 2 ? f.x2 : false;
+    if constexpr (TY != 1) v += ey ? w1[o + dr] : 0.f;
+    if constexpr (TX != 1) v += ex ? w1[o + dc] : 0.f;
+    if constexpr (TY != 1 && TX != 1) v += (ey && ex) ? w1[o + dr + dc] : 0.f;
+  }
+  return v;
+}
+
+struct BwdTile {
+  int n, y0, x0;
+};
+// The tiles of an image are split into the INTERIOR rectangle tx in [ix0, ix1), ty in [iy0, iy1) and the BORDER around it (with reflect
+// padding: every tile that holds a pixel of row 1 / H-2 or column 1 / W-2; with zero padding the border is empty).  Each set is walked
+// by a launch of its own, so that the interior runs the kernel without any fold code.
+struct BwdTiling {
+  int tiles_x, tiles_y, ix0, ix1, iy0, iy1;
+  __host__ __device__ int iw() const { return ix1 - ix0; }
+  __host__ __device__ int ih() const { return iy1 - iy0; }
+  __host__ __device__ int per_image(bool border) const { return border ? tiles_x * tiles_y - iw() * ih() : iw() * ih(); }
+};
+template <bool BORDER>
+__device__ __forceinline__ BwdTile bwd_tile(int tile, const BwdTiling& g) {
+  BwdTile t;
+  const int per = g.per_image(BORDER);
+  t.n = tile / per;
+  int j = tile - t.n * per, tx, ty;
+  if (!BORDER) {
+    ty = g.iy0 + j / g.iw();
+    tx = g.ix0 + j % g.iw();
+  } else {
+    const int full = (g.tiles_y - g.ih()) * g.tiles_x;  // the tile rows above and below the interior, whole width
+    if (j < full) {
+      const int r = j / g.tiles_x;
+      tx = j - r * g.tiles_x;
+      ty = r < g.iy0 ? r : r - g.iy0 + g.iy1;
+    } else {  // left and right of the interior
+      j -= full;
+      const int side = g.tiles_x - g.iw(), r = j / side, c = j - r * side;
+      ty = g.iy0 + r;
+      tx = c < g.ix0 ? c : c - g.ix0 + g.ix1;
+    }
+  }
+  t.y0 = ty * LT_H, t.x0 = tx * LT_W;
+  return t;
+}
+
+struct BwdArgs {
+  const float* x;   // [N,H,W,32] pixel pitch xcs: the input of the LeakyReLU
+  const float* dy;  // [N,H,W,K] pixel pitch ycs
+  const float* yt;  // tanh output in dy's layout, or NULL
+  const float* wt;  // wt[9][K][32]
+  float* dx;        // layout of x
+  float* ws;        // [gridDim.x][9*32*K + K]
+  int N, H, W, xcs, ycs, pad_mode;
+  float slope;
+};
+
+template <int K>
+struct __attribute__((packed, aligned(4))) GKv {
+  float e[K];
+};
+
+// the window cells `tid + 256 l` of a tile: loads into registers (the LDS store follows one tile of arithmetic later)
+template <int K>
+__device__ __forceinline__ void bwd_win_load(const BwdArgs& a, BwdTile t, int tid, GKv<K> (&g)[BW_LD], GKv<K> (&yv)[BW_LD], bool (&inner)[BW_LD]) {
+#pragma unroll
+  for (int l = 0; l < BW_LD; ++l) {
+    const int p = tid + 256 * l;
+    const int wy = p / BW_W, wx = p - wy * BW_W;
+    const int py = t.y0 + wy - 1, px = t.x0 + wx - 1;
+    const bool ok = p < BW_CELLS && (unsigned)py < (unsigned)a.H && (unsigned)px < (unsigned)a.W;
+    inner[l] = ok && wy >= 1 && wy <= LT_H && wx >= 1 && wx <= LT_W;  // the cell belongs to this tile: it counts for dbias
+#pragma unroll
+    for (int k = 0; k < K; ++k) g[l].e[k] = 0.f, yv[l].e[k] = 0.f;
+    if (ok) {
+      const int64_t o = ((int64_t)(t.n * a.H + py) * a.W + px) * a.ycs;
+      g[l] = *reinterpret_cast<const GKv<K>*>(a.dy + o);
+      if (a.yt) yv[l] = *reinterpret_cast<const GKv<K>*>(a.yt + o);
+    }
+  }
+}
+template <int K>
+__device__ __forceinline__ void bwd_win_store(float4* win, int tid, const GKv<K> (&g)[BW_LD], const GKv<K> (&yv)[BW_LD], const bool (&inner)[BW_LD],
+                                              float (&bacc)[K]) {
+#pragma unroll
+  for (int l = 0; l < BW_LD; ++l) {
+    const int p = tid + 256 * l;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      v[k] = g[l].e[k] * (1.f - yv[l].e[k] * yv[l].e[k]);  // yv = 0 without tanh
+      bacc[k] += inner[l] ? v[k] : 0.f;
+    }
+    if (p < BW_CELLS) win[p] = make_float4(v[0], v[1], v[2], v[3]);
+  }
+}
+
+// Addresses of x / dx: a wave-uniform 64-bit part (tile, iteration: scalar registers) plus ONE 32-bit per-lane offset `xlo` that no
+// iteration changes, (2 wid * W + 4 g + i) * xcs + 4 q -- the eight iterations of a tile then cost no per-lane address arithmetic.
+__device__ __forceinline__ int64_t bwd_x_uoff(const BwdArgs& a, BwdTile t, int it) {
+  return ((int64_t)(t.n * a.H + t.y0 + (it >> 2)) * a.W + t.x0 + (it & 3) * 8) * a.xcs;
+}
+struct BwdLane {
+  int xlo;      // per-lane element offset into x / dx
+  int ry, rx;   // the lane's pixel in iteration 0 relative to the tile: (2 wid, 4 g + i)
+};
+// x of the lane's pixel in iteration `it` of tile t.  The load is UNCONDITIONAL (a pixel outside the image, or no tile at all, reads the
+// tensor's first 16 bytes; the consumer replaces it by zero): loads inside branches make the compiler wait for every load in flight at
+// the next use, which would shorten the prefetch distance to one iteration.
+__device__ __forceinline__ float4 bwd_x_load(const BwdArgs& a, BwdTile t, int it, BwdLane l, bool valid) {
+  const bool in = valid && t.y0 + l.ry + (it >> 2) < a.H && t.x0 + l.rx + (it & 3) * 8 < a.W;
+  const float* p = a.x + bwd_x_uoff(a, t, it) + l.xlo;
+  return *reinterpret_cast<const float4*>(in ? p : a.x);
+}
+
+// The 8 iterations of one tile, fully unrolled.  x runs BWD_PF iterations ahead in registers, across the tile boundary: iteration `it`
+// consumes xr[it % BWD_PF] and reloads it for iteration it + BWD_PF; the slot is a fixed register (a rotating copy would wait for the
+// load it has just issued).
+constexpr int BWD_PF = 4;
+template <int K, bool FOLD>
+__device__ __forceinline__ void bwd_tile_compute(const BwdArgs& a, const float4* win, BwdTile t, BwdTile nx, bool hasn, BwdLane l, int g, int i,
+                                                 const float (&wr)[9][K], f32x4_t (&dw)[9], float4 (&xr)[BWD_PF]) {
+  static_assert(BWD_PF == 4, "one pass of the unrolled loop = one tile row of the wave");
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const float4* wrow = win + (l.ry + h) * BW_W + l.rx;                                       // the lane's own pixel, iteration 4h
+    const float* grow = reinterpret_cast<const float*>(win + (l.ry + h) * BW_W + 4 * g) + i;  // component i, pixel 0 of the lane's group
+    const int oy = t.y0 + l.ry + h;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int it = 4 * h + j;
+      const int ox = t.x0 + l.rx + 8 * j;
+      const bool live = oy < a.H && ox < a.W;
+      const float4 xv = sel4(live, xr[j]);  // zero for pixels outside the image: they add nothing to dW
+      xr[j] = h == 0 ? bwd_x_load(a, t, it + 4, l, true) : bwd_x_load(a, nx, it - 4, l, hasn);
+      // adjoint: one accumulator chain per tap row
+      {
+        const FoldFlags f = fold_flags(a.pad_mode, oy, ox, a.H, a.W);
+        f32x4_t acc[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) acc[r] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#define BWD_TAP(TY, TX)                                                                                                                  \
+  {                                                                                                                                      \
+    const float4 gq = bwd_g4<FOLD, TY, TX>(wrow + 8 * j, f);                                                                             \
+    const float ge[4] = {gq.x, gq.y, gq.z, gq.w};                                                                                        \
+    _Pragma("unroll") for (int k = 0; k < K; ++k) acc[TY] = __builtin_amdgcn_mfma_f32_4x4x1f32(wr[TY * 3 + TX][k], ge[k], acc[TY], 0, 0, 0); \
+  }
+        BWD_TAP(0, 0) BWD_TAP(1, 0) BWD_TAP(2, 0) BWD_TAP(0, 1) BWD_TAP(1, 1) BWD_TAP(2, 1) BWD_TAP(0, 2) BWD_TAP(1, 2) BWD_TAP(2, 2)
+#undef BWD_TAP
+        if (live) {
+          const float4 o = make_float4(acc[0][0] + acc[1][0] + acc[2][0], acc[0][1] + acc[1][1] + acc[2][1], acc[0][2] + acc[1][2] + acc[2][2],
+                                       acc[0][3] + acc[1][3] + acc[2][3]);
+          *reinterpret_cast<float4*>(a.dx + bwd_x_uoff(a, t, it) + l.xlo) = lrelu_mask4(o, xv, a.slope);
+        }
+      }
+      // weight gradient: the group's 4 pixels one after the other
+      const float4 lv = lrelu4(xv, a.slope);
+#define BWD_PIX(P)                                                                                                                           \
+  {                                                                                                                                          \
+    const float b0 = quad_bcast<P>(lv.x), b1 = quad_bcast<P>(lv.y), b2 = quad_bcast<P>(lv.z), b3 = quad_bcast<P>(lv.w);                      \
+    const float b = i == 0 ? b0 : i == 1 ? b1 : i == 2 ? b2 : b3; /* lrelu(x[pixel P][4q + i]) */                                            \
+    const FoldFlags f = fold_flags(a.pad_mode, oy, t.x0 + 4 * g + 8 * j + P, a.H, a.W);                                                      \
+    BWD_WTAP(P, 0, 0) BWD_WTAP(P, 0, 1) BWD_WTAP(P, 0, 2) BWD_WTAP(P, 1, 0) BWD_WTAP(P, 1, 1) BWD_WTAP(P, 1, 2) BWD_WTAP(P, 2, 0) BWD_WTAP(P, 2, 1) \
+    BWD_WTAP(P, 2, 2)                                                                                                                        \
+  }
+#define BWD_WTAP(P, TY, TX) dw[TY * 3 + TX] = __builtin_amdgcn_mfma_f32_4x4x1f32(bwd_g1<FOLD, TY, TX>(grow + 4 * (8 * j + P), f), b, dw[TY * 3 + TX], 0, 0, 0);
+      BWD_PIX(0) BWD_PIX(1) BWD_PIX(2) BWD_PIX(3)
+#undef BWD_WTAP
+#undef BWD_PIX
+    }
+  }
+}
+
+template <int K, bool FOLD>
+// the interior kernel fits three waves per SIMD (164 VGPRs for K = 3) when the compiler is asked to; left alone it settles for two
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((!FOLD && K <= 3) ? 3 : 2))) thin_lrelu_bwd_kernel(BwdArgs a, BwdTiling tg, int ntiles, int row0) {
+  __shared__ __attribute__((aligned(16))) float4 win[2][BW_CELLS];
+  __shared__ float red[9 * 4 * 32];
+  __shared__ float lds4[4];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int i = lane & 3, q = (lane >> 2) & 7, g = lane >> 5;
+  float wr[9][K];  // A operand of the adjoint: wt[t][k][4q + i]
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int k = 0; k < K; ++k) wr[t][k] = a.wt[(t * K + k) * 32 + 4 * q + i];
+  f32x4_t dw[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) dw[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  float bacc[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) bacc[k] = 0.f;
+  GKv<K> sg[BW_LD], sy[BW_LD];
+  bool inner[BW_LD];
+  float4 xr[BWD_PF];
+
+  int tile = blockIdx.x;  // the host launches at most ntiles workgroups
+  BwdTile cur = bwd_tile<FOLD>(tile, tg);
+  bwd_win_load<K>(a, cur, tid, sg, sy, inner);
+  const BwdLane l{(2 * wid * a.W + 4 * g + i) * a.xcs + 4 * q, 2 * wid, 4 * g + i};
+#pragma unroll
+  for (int it = 0; it < BWD_PF; ++it) xr[it] = bwd_x_load(a, cur, it, l, true);
+  bwd_win_store<K>(win[0], tid, sg, sy, inner, bacc);
+  __syncthreads();
+  int pb = 0;
+  for (; tile < ntiles; tile += gridDim.x) {
+    const bool hasn = tile + (int)gridDim.x < ntiles;
+    const BwdTile nx = bwd_tile<FOLD>(hasn ? tile + gridDim.x : tile, tg);
+    if (hasn) bwd_win_load<K>(a, nx, tid, sg, sy, inner);
+    bwd_tile_compute<K, FOLD>(a, win[pb], cur, nx, hasn, l, g, i, wr, dw, xr);
+    // win[pb ^ 1] was last read in the previous tile, and every wave has passed that tile's barrier
+    if (hasn) bwd_win_store<K>(win[pb ^ 1], tid, sg, sy, inner, bacc);
+    __syncthreads();
+    pb ^= 1;
+    cur = nx;
+  }
+  // dw[t][r] of lane (g, q, i) = dW[t][4q + i][r]: over the two pixel groups, then over the waves in a fixed order, then one row of ws
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dw[t][r] += __shfl_xor(dw[t][r], 32, 64);
+  for (int w = 0; w < 4; ++w) {
+    if (wid == w && g == 0) {
+#pragma unroll
+      for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float* p = red + (t * 4 + r) * 32 + (lane & 31);
+          *p = w == 0 ? dw[t][r] : *p + dw[t][r];
+        }
+    }
+    __syncthreads();
+  }
+  constexpr int RW = 9 * 32 * K + K;
+  float* row = a.ws + (int64_t)(row0 + blockIdx.x) * RW;
+  for (int idx = tid; idx < 9 * 32 * K; idx += 256) {
+    const int t = idx / (32 * K), rem = idx - t * 32 * K, c = rem / K, k = rem - c * K;
+    row[idx] = red[(t * 4 + k) * 32 + c];
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const float s_ = block_sum_256(bacc[k], lds4);
+    if (tid == 0) row[9 * 32 * K + k] = s_;
+  }
+}
+
+// out[i] = sum over the rows of ws[rows][width] in a fixed order: 32 interleaved slices per value (each over its rows in four
+// interleaved chains, so that four loads are in flight), then the slices one after the other.  dW for i < nw, then dbias.
+__global__ void __launch_bounds__(1024) thin_sum_rows_kernel(const float* __restrict__ ws, float* __restrict__ dwf, float* __restrict__ dbias, int rows,
+                                                             int width, int nw) {
+  __shared__ float part[32][33];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int i = blockIdx.x * 32 + tx;
+  float s4[4] = {0.f, 0.f, 0.f, 0.f};
+  if (i < width) {
+    int r = ty;
+    for (; r + 96 < rows; r += 128) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) s4[u] += ws[(int64_t)(r + 32 * u) * width + i];
+    }
+    for (int u = 0; r < rows; r += 32, ++u) s4[u] += ws[(int64_t)r * width + i];
+  }
+  part[ty][tx] = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+  __syncthreads();
+  if (ty == 0 && i < width) {
+    float t = 0.f;
+#pragma unroll
+    for (int l = 0; l < 32; ++l) t += part[l][tx];
+    if (i < nw) dwf[i] = t;
+    else if (dbias) dbias[i - nw] = t;
+  }
+}
+
+// resident workgroups of a 256-thread kernel on the whole device, from what the compiler gave it (registers AND LDS)
+template <typename F>
+static int resident_grid(F kernel) {
+  int per_cu = 0, dev = 0, cus = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+  (void)hipGetLastError();
+  return per_cu * cus;
+}
+template <int K, bool FOLD>
+static int bwd_resident_grid() {
+  static const int g = resident_grid(thin_lrelu_bwd_kernel<K, FOLD>);
+  return g;
+}
+template <int K>
+static void bwd_launch(const fmi_conv_desc* d, const BwdArgs& a, int64_t rows, hipStream_t st, int* rows_used) {
+  BwdTiling tg{(d->W + LT_W - 1) / LT_W, (d->H + LT_H - 1) / LT_H, 0, 0, 0, 0};
+  if (!d->pad_mode) tg.ix1 = tg.tiles_x, tg.iy1 = tg.tiles_y;  // zero padding: nothing folds
+  else if ((d->H - 2) / LT_H > 1 && (d->W - 2) / LT_W > 1) tg.ix0 = 1, tg.ix1 = (d->W - 2) / LT_W, tg.iy0 = 1, tg.iy1 = (d->H - 2) / LT_H;
+  const int64_t n_in = (int64_t)d->N * tg.per_image(false), n_bd = (int64_t)d->N * tg.per_image(true);
+  // one round of resident workgroups per launch (the same in reproducible mode); the border takes at most a quarter of the rows
+  int64_t g_in = bwd_resident_grid<K, false>(), g_bd = bwd_resident_grid<K, true>();
+  if (g_in > n_in) g_in = n_in;
+  if (g_bd > n_bd) g_bd = n_bd;
+  if (g_in + g_bd > rows) {
+    if (g_bd > rows / 4) g_bd = n_bd ? (rows / 4 > 1 ? rows / 4 : 1) : 0;
+    if (g_in > rows - g_bd) g_in = rows - g_bd;
+  }
+  if (g_in > 0) hipLaunchKernelGGL((thin_lrelu_bwd_kernel<K, false>), dim3((unsigned)g_in), dim3(256), 0, st, a, tg, (int)n_in, 0);
+  if (g_bd > 0) hipLaunchKernelGGL((thin_lrelu_bwd_kernel<K, true>), dim3((unsigned)g_bd), dim3(256), 0, st, a, tg, (int)n_bd, (int)g_in);
+  *rows_used = (int)(g_in + g_bd);
+}
+template <int K>
+static int fwd_lds_resident_grid() {
+  static const int g = resident_grid(thin_fwd_lds_kernel<K>);
+  return g;
+}
+template <int K>
+static int wgrad_lds_resident_grid() {
+  static const int g = resident_grid(thin_wgrad_lds_kernel<K>);
+  return g;
+}
+
 bool thin_shape_ok(const fmi_conv_desc* d) {
   const int cg = d->C / 4;
   return d->dil <= 1 && (int64_t)d->N * d->H * d->W < (1ll << 31) && d->K >= 1 && d->K <= 4 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->C % 4 == 0 && cg >= 1 &&
@@ -619,8 +1022,15 @@ static int thin_fwd_impl(const fmi_conv_desc* d, const float* x, float in_slope,
     const int tiles_x = (d->W + LT_W - 1) / LT_W, tiles_y = (d->H + LT_H - 1) / LT_H;
     const int64_t nb = (int64_t)d->N * tiles_x * tiles_y;
     if (nb < (1ll << 31)) {
-      const int grid = (int)nb;
-      THIN_DISPATCH(thin_fwd_lds_kernel, a, tiles_x, tiles_y);
+      int res = 768;  // workgroups resident at once (registers and LDS): one round
+      switch (d->K) {
+        case 1: res = fwd_lds_resident_grid<1>(); break;
+        case 2: res = fwd_lds_resident_grid<2>(); break;
+        case 3: res = fwd_lds_resident_grid<3>(); break;
+        default: res = fwd_lds_resident_grid<4>(); break;
+      }
+      const int grid = (int)(nb < res ? nb : res);
+      THIN_DISPATCH(thin_fwd_lds_kernel, a, tiles_x, tiles_y, (int)nb);
       return fmi_launch_status();
     }
   }
@@ -707,11 +1117,18 @@ static int thin_wgrad_impl(const fmi_conv_desc* d, const float* x, float in_slop
   a.in_slope = in_slope;
   const int G = d->C / 4;
   const int64_t total = (int64_t)d->N * d->H * d->W;
-  if (d->C == 32) {  // halo tile through LDS, persistent workgroups (3 per CU)
+  if (d->C == 32) {  // halo tile through LDS, persistent workgroups
     const int tiles_x = (d->W + LT_W - 1) / LT_W, tiles_y = (d->H + LT_H - 1) / LT_H;
     const int64_t nt = (int64_t)d->N * tiles_x * tiles_y;
     if (nt < (1ll << 31)) {
-      const int grid = fmi_det() ? 1 : (nt < 768 ? (int)nt : 768);  // reproducible mode: one persistent workgroup walks every tile
+      int res = 512;  // workgroups resident at once: one round, every CU busy to the end
+      switch (d->K) {
+        case 1: res = wgrad_lds_resident_grid<1>(); break;
+        case 2: res = wgrad_lds_resident_grid<2>(); break;
+        case 3: res = wgrad_lds_resident_grid<3>(); break;
+        default: res = wgrad_lds_resident_grid<4>(); break;
+      }
+      const int grid = fmi_det() ? 1 : (nt < res ? (int)nt : res);  // reproducible mode: one persistent workgroup walks every tile
       THIN_DISPATCH(thin_wgrad_lds_kernel, a, dwf, dbias, tiles_x, tiles_y, (int)nt);
       return fmi_launch_status();
     }
@@ -728,4 +1145,39 @@ extern "C" int fmi_conv2d_thin_wgrad_f32(const fmi_conv_desc* d, const float* x,
 extern "C" int fmi_conv2d_thin_lrelu_wgrad_f32(const fmi_conv_desc* d, const float* x, float in_slope, const float* dy, float* dwf,
                                                float* dbias, void* stream) {
   return thin_wgrad_impl(d, x, in_slope, dy, dwf, dbias, stream);
+}
+
+/* Whole backward of the fused Output block in one pass (see the kernel).  ws: fmi_conv2d_thin_lrelu_bwd_ws_bytes(d) bytes. */
+static int bwd_rows(const fmi_conv_desc* d) {
+  const int64_t nt = (int64_t)d->N * ((d->W + LT_W - 1) / LT_W) * ((d->H + LT_H - 1) / LT_H);
+  return (int)(nt < BWD_MAX_ROWS ? nt : BWD_MAX_ROWS);
+}
+extern "C" int fmi_conv2d_thin_lrelu_bwd_ws_bytes(const fmi_conv_desc* d) {
+  if (!d || !thin_lrelu_ok(d)) return 0;
+  return bwd_rows(d) * (9 * d->C * d->K + d->K) * (int)sizeof(float);
+}
+extern "C" int fmi_conv2d_thin_lrelu_bwd_f32(const fmi_conv_desc* d, const float* x, float in_slope, const float* dy, const float* y, const float* wt,
+                                             float* dx, float* dwf, float* dbias, void* ws, int64_t ws_bytes, void* stream) {
+  if (!d || !x || !dy || !wt || !dx || !dwf || !ws) return FMI_ERR_BAD_ARG;
+  if (!thin_lrelu_ok(d) || ((uintptr_t)x & 15) || ((uintptr_t)dx & 15) || ((uintptr_t)ws & 3)) return FMI_ERR_UNSUPPORTED;
+  const int tiles_x = (d->W + LT_W - 1) / LT_W, tiles_y = (d->H + LT_H - 1) / LT_H;
+  const int64_t nt = (int64_t)d->N * tiles_x * tiles_y;
+  if (nt >= (1ll << 31)) return FMI_ERR_UNSUPPORTED;
+  const int width = 9 * d->C * d->K + d->K;
+  int64_t rows = ws_bytes / ((int64_t)width * (int64_t)sizeof(float));
+  if (rows > bwd_rows(d)) rows = bwd_rows(d);
+  if (rows < 1) return FMI_ERR_BAD_ARG;
+  const bool two_sets = d->pad_mode && (d->H - 2) / LT_H > 1 && (d->W - 2) / LT_W > 1;
+  if (two_sets && rows < 2) return FMI_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  BwdArgs a{x, dy, y, wt, dx, (float*)ws, d->N, d->H, d->W, d->x_cstride, d->y_cstride, d->pad_mode, in_slope};
+  int used = 0;
+  switch (d->K) {
+    case 1: bwd_launch<1>(d, a, rows, st, &used); break;
+    case 2: bwd_launch<2>(d, a, rows, st, &used); break;
+    case 3: bwd_launch<3>(d, a, rows, st, &used); break;
+    default: bwd_launch<4>(d, a, rows, st, &used); break;
+  }
+  hipLaunchKernelGGL(thin_sum_rows_kernel, dim3((width + 31) / 32), dim3(1024), 0, st, (const float*)ws, dwf, dbias, used, width, 9 * d->C * d->K);
+  return fmi_launch_status();
 }

@@ -477,12 +477,29 @@ class _ThinConvLReLU(torch.autograd.Function):
         x, wf, y = ctx.saved_tensors
         slope, pad_mode, act = ctx.cfg
         gy = gy.contiguous()
-        if act:
-            gy = _act_bwd(gy, y, act)
         n, h, w, c = x.shape
         k = wf.shape[2]
         d, _, _ = conv_desc(n, h, w, c, k, 3, 3, 1, 1, pad_mode)
         gx = gwf = gb = None
+        if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
+            # both gradients in one pass over x (tanh' folded into the staging of dy); the partial sums of dW / dbias meet in a
+            # fixed order, so nothing is zeroed and reproducible mode takes the same launch
+            yt = None
+            if act == ACT_TANH:
+                yt = y
+            elif act:
+                gy = _act_bwd(gy, y, act)
+            gx = torch.empty_like(x)
+            gwf = torch.empty(wf.shape, device=x.device, dtype=torch.float32)
+            if ctx.has_b and ctx.needs_input_grad[2]:
+                gb = torch.empty(k, device=x.device, dtype=torch.float32)
+            ws_bytes = lib.conv2d_thin_lrelu_bwd_ws_bytes(C.byref(d))
+            ws = torch.empty(ws_bytes // 4, device=x.device, dtype=torch.float32)
+            with _prof(f"conv_bwd|{n}x{h}x{w} {c}->{k} k3s1", 4.0 * gy.numel() * c * 9):
+                lib.conv2d_thin_lrelu_bwd_f32(C.byref(d), _p(x), slope, _p(gy), _p(yt), _p(ctx.wt), _p(gx), _p(gwf), _p(gb), _p(ws), ws_bytes, _st())
+            return gx, gwf, gb, None, None, None, None
+        if act:
+            gy = _act_bwd(gy, y, act)
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
             with _prof(f"conv_dgrad|{n}x{h}x{w} {c}->{k} k3s1", 2.0 * gy.numel() * c * 9):

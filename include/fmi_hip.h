@@ -182,6 +182,17 @@ int fmi_conv2d_thin_lrelu_dgrad_f32(const fmi_conv_desc* d, const float* dy, con
                                     void* stream);
 int fmi_conv2d_thin_lrelu_wgrad_f32(const fmi_conv_desc* d, const float* x, float in_slope, const float* dy, float* dwf, float* dbias,
                                     void* stream);
+/* Whole backward of that fused block in ONE pass over x: dx = lrelu'(x) * adjoint(dy'), dwf[9][C][K] = lrelu(x)^T dy', dbias[k] = sum dy'
+ * (dbias may be NULL), with dy' = dy * (1 - y * y) when y (the tanh output, layout of dy) is given and dy' = dy when y is NULL -- the
+ * separate tanh-backward pass disappears.  pad_mode = reflect includes the fold of the padded gradient, as fmi_conv2d_thin_dgrad_f32.
+ * dwf and dbias are WRITTEN, not accumulated: nothing has to be zeroed.  The sum over workgroups goes through ws (one row of
+ * 9*C*K + K partial sums per workgroup, added in a fixed order by a finishing launch): no atomics, the result is bit-reproducible in
+ * either mode.  ws: device memory, fmi_conv2d_thin_lrelu_bwd_ws_bytes(d) =
+ *   min(N * ceil(H / 8) * ceil(W / 32), 2048) * (9*C*K + K) * 4 bytes (0 for a shape the entry does not take); a smaller ws (at least
+ * one row) only lowers the number of workgroups.  Same shapes as fmi_conv2d_thin_lrelu_supported; x and dx 16-byte aligned. */
+int fmi_conv2d_thin_lrelu_bwd_ws_bytes(const fmi_conv_desc* d);
+int fmi_conv2d_thin_lrelu_bwd_f32(const fmi_conv_desc* d, const float* x, float in_slope, const float* dy, const float* y, const float* wt,
+                                  float* dx, float* dwf, float* dbias, void* ws, int64_t ws_bytes, void* stream);
 /* adjoint of a thin-INPUT 3x3 convolution (C <= 4, K = 4..64 a power of two, stride 1, pad 1, zeros): dx = thin-output convolution of
  * dy with flipped taps -- the input gradient of VGG16's first layer (loss.py:45-65); fmi_conv2d_dgrad_f32 routes to it by itself */
 int fmi_conv2d_thin_input_dgrad_f32(const fmi_conv_desc* d, const float* dy, const float* wt, float* dx, void* stream);
