@@ -103,6 +103,8 @@ SIGNATURES = {
     "fmi_maxpool_f32": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "fmi_maxpool_bwd_f32": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "fmi_argmax_channels_f32": [vp, vp, i64, i32, vp],
+    "fmi_image_tail_f32": [vp, vp, vp, vp, i32, i32, f32, f32, vp],
+    "fmi_planes_to_u8_f32": [vp, vp, i32, i32, i32, i32, f32, f32, vp],
     "fmi_instnorm_stats_bf16": [vp, vp, vp, i32, i32, i32, f32, vp, i64, vp],
     "fmi_instnorm_apply_bf16": [vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
     "fmi_instnorm_bwd_reduce_bf16": [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, i64, vp],

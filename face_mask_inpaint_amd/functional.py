@@ -1085,6 +1085,56 @@ def argmax_channels(x_nhwc: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _no_grad_input(t, what):
+    if t.requires_grad and torch.is_grad_enabled():
+        raise FmiError(f"{what} is inference only (no backward): call it under torch.no_grad() or detach the input")
+    return t.detach()
+
+
+def image_tail(image_nhwc: torch.Tensor, want=("pooled", "unit", "u8"), shift: float = 1.0, scale: float = 0.5) -> dict:
+    """the decoder's NHWC fp32 image [N, S, S, 3] (S in 256 / 512 / 1024) -> the outputs named in ``want``, from one read of the image
+    (fmi_image_tail_f32): ``pooled`` NCHW [N, 3, 256, 256] = AdaptiveAvgPool2d((256, 256)) (psp.py:33,113-114), ``unit`` = (pooled + 1) / 2
+    (psp_inference.py:116-117), ``u8`` HWC uint8 [N, 256, 256, 3] = tensor2im's arithmetic ((pooled + shift) * scale, clamp to [0, 1],
+    * 255, truncation: psp_inference.py:106-112 with (1, 0.5), gradio_serve.py:45-51 with (0, 1)), bit-identical to numpy float32 on
+    ``pooled``.  Inference only.  Other sizes: FmiError (use adaptive_avg_pool)."""
+    x = _no_grad_input(image_nhwc, "image_tail")
+    _chk(x)
+    want = tuple(want)
+    if not want or any(w not in ("pooled", "unit", "u8") for w in want):
+        raise FmiError(f"image_tail: want is a non-empty subset of ('pooled', 'unit', 'u8'), got {want}")
+    if x.dim() != 4 or x.shape[3] != 3 or x.shape[1] != x.shape[2]:
+        raise FmiError(f"image_tail: expected [N, S, S, 3], got {tuple(x.shape)}")
+    n, s = x.shape[0], x.shape[1]
+    out = {}
+    for k in ("pooled", "unit"):
+        if k in want:
+            out[k] = torch.empty((n, 3, 256, 256), device=x.device, dtype=torch.float32)
+    if "u8" in want:
+        out["u8"] = torch.empty((n, 256, 256, 3), device=x.device, dtype=torch.uint8)
+    _L().image_tail_f32(_p(x), _p(out.get("pooled")), _p(out.get("unit")), _p(out.get("u8")), n, s, float(shift), float(scale), _st())
+    return out
+
+
+def planes_to_u8(x_nchw: torch.Tensor, shift: float = 0.0, scale: float = 1.0) -> torch.Tensor:
+    """NCHW fp32 [N, C, H, W] with C = 3 or 1 (replicated) -> HWC uint8 [N, H, W, 3] by tensor2im's arithmetic (see image_tail); any
+    H, W -- the conversion of gradio_serve.py:59-63 at the source image's own size.  Inference only."""
+    x = _no_grad_input(x_nchw, "planes_to_u8").contiguous()
+    _chk(x)
+    n, c, h, w = x.shape
+    out = torch.empty((n, h, w, 3), device=x.device, dtype=torch.uint8)
+    _L().planes_to_u8_f32(_p(x), _p(out), n, c, h, w, float(shift), float(scale), _st())
+    return out
+
+
+def mask_to_u8(mask: torch.Tensor, shift: float = 1.0, scale: float = 0.5) -> torch.Tensor:
+    """detected mask [N, H, W] fp32 {0, 1} -> HWC uint8 [N, H, W, 3], the channel replicated: tensor2im(mask.repeat((3, 1, 1))) of
+    psp_inference.py:183-184.  With the defaults -- the (x + 1) / 2 inside psp_inference.tensor2im -- 0 maps to 127 and 1 to 255, as in
+    the reference's saved mask_<id>.jpg; (0, 1) is gradio_serve's form (0 -> 0, 1 -> 255)."""
+    if mask.dim() != 3:
+        raise FmiError(f"mask_to_u8: expected [N, H, W], got {tuple(mask.shape)}")
+    return planes_to_u8(mask.unsqueeze(1), shift, scale)
+
+
 class _MaxPool2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

@@ -65,8 +65,8 @@ class pSp(nn.Module):
         else:
             codes = self.encoder(x, ref=ref, mask=src_mask)
             if self.opts.start_from_latent_avg and self.latent_avg is not None:
-                avg = self.latent_avg.to(codes.device)
-                codes = FF.add(codes, (avg.repeat(codes.shape[0], 1) if self.opts.learn_in_w else avg.repeat(codes.shape[0], 1, 1)).contiguous())
+                avg = self.latent_avg.to(codes.device)  # [n_styles, 512], or the [512] of mean_latent broadcast over the styles as torch's + does
+                codes = FF.add(codes, (avg.repeat(codes.shape[0], 1) if self.opts.learn_in_w else avg.repeat(codes.shape[0], 1, 1)).expand_as(codes).contiguous())
         if latent_mask is not None:
             for i in latent_mask:
                 if inject_latent is not None:
@@ -78,6 +78,23 @@ class pSp(nn.Module):
         if resize:  # self.face_pool = AdaptiveAvgPool2d((256, 256)): any decoder output size (replication below 256, psp.py:33,113-114)
             images = FF.to_nchw(FF.adaptive_avg_pool(FF.to_nhwc(images), 256, 256))
         return (images, result_latent) if return_latents else images
+
+    @torch.no_grad()
+    def infer(self, x, ref=None, src_mask=None, want=("pooled",), shift=1.0, scale=0.5):
+        """the call of the inference harness (psp_inference.py:95-100: resize=True, randomize_noise=False, return_latents=True) without
+        gradients: encoder -> + latent_avg -> decoder, whose NHWC image goes straight into the fused tail (FF.image_tail: face_pool,
+        the SSIM operand and tensor2im's uint8 picture from one read).  Returns (dict with the entries of ``want``, W+ codes).  Decoder
+        sizes the tail kernel does not cover (not 256 / 512 / 1024) are pooled as in ``forward``; they give ``pooled`` only."""
+        codes = self.encoder(x, ref=ref, mask=src_mask)
+        if self.opts.start_from_latent_avg and self.latent_avg is not None:
+            avg = self.latent_avg.to(codes.device)
+            codes = FF.add(codes, (avg.repeat(codes.shape[0], 1) if self.opts.learn_in_w else avg.repeat(codes.shape[0], 1, 1)).expand_as(codes).contiguous())
+        image, latent = self.decoder([codes], input_is_latent=True, randomize_noise=False, return_latents=True, image_nhwc=True)
+        if image.shape[1] in (256, 512, 1024):
+            return FF.image_tail(image.contiguous(), want=want, shift=shift, scale=scale), latent
+        if tuple(want) != ("pooled",):
+            raise FF.FmiError(f"pSp.infer: a {image.shape[1]}^2 decoder output gives 'pooled' only, not {tuple(want)}")
+        return {"pooled": FF.to_nchw(FF.adaptive_avg_pool(image, 256, 256)).contiguous()}, latent
 
     def set_opts(self, opts):
         self.opts = opts

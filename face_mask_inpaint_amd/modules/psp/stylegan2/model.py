@@ -299,7 +299,8 @@ class Generator(nn.Module):
         return self.style(input)
 
     def forward(self, styles, return_latents=False, return_features=False, inject_index=None, truncation=1, truncation_latent=None,
-                input_is_latent=False, noise=None, randomize_noise=True):
+                input_is_latent=False, noise=None, randomize_noise=True, image_nhwc=False):
+        """image_nhwc (this build's extra, default off): the image is returned as the NHWC tensor ToRGB produced, not as its NCHW view"""
         if not input_is_latent:
             styles = [self.style(s) for s in styles]
         if noise is None:
@@ -329,7 +330,7 @@ class Generator(nn.Module):
             out = conv2.nhwc(out, lat(i + 1), noise=noise2)
             skip = to_rgb.nhwc(out, lat(i + 2), skip)
             i += 2
-        image = FF.to_nchw(skip)
+        image = skip if image_nhwc else FF.to_nchw(skip)
         if return_latents:
             return image, latent
         if return_features:

@@ -103,12 +103,16 @@ class DevicePreprocessor:
                 raise FmiError("a batch is preprocessed in one launch: uint8 arrays of one common size")
         return np.ascontiguousarray(np.stack(arrays))
 
-    def images(self, arrays: Sequence[np.ndarray], scale: float = 1.0, normalise: bool = False, also_plain: bool = False):
+    def images(self, arrays: Sequence[np.ndarray], scale: float = 1.0, normalise: bool = False, also_plain: bool = False, size=None):
         """decoded uint8 [H][W][3] (or [H][W]) arrays -> float32 [N][C][H'][W'], BICUBIC-resized by ``scale``, / 255 (, Normalize).
+        size: (width, height) of the result instead of ``scale`` -- Pillow's ``resize(size, BICUBIC)`` from any aspect ratio
+        (gradio_serve.py:31-43 resizes every upload to 256 x 256)
         also_plain: returns (normalised, plain [0, 1]) from the one resized image (the gt_img / raw_gt_img pair of dataloader.py:249-254)"""
         host = self._stack([a if a.ndim == 3 else a[..., None] for a in arrays])
         n, h, w, c = host.shape
-        nw, nh = scaled_size(w, h, scale)
+        nw, nh = scaled_size(w, h, scale) if size is None else (int(size[0]), int(size[1]))
+        if nw <= 0 or nh <= 0:
+            raise ValueError("the resized images would have no pixel")
         lib, st = _lib.lib(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         with torch.cuda.device(self.device):
             cur = torch.from_numpy(host).to(self.device)

@@ -439,6 +439,21 @@ int fmi_adaptive_avgpool_bwd_f32(const float* gy, float* gx, int N, int H, int W
  * (may be NULL) = window position of the first maximum; the backward scatters with atomics, caller zeroes gx */
 int fmi_maxpool_f32(const float* x, float* y, int32_t* argmax, int N, int H, int W, int C, int k, int stride, void* stream);
 int fmi_maxpool_bwd_f32(const float* gy, const int32_t* argmax, float* gx, int N, int H, int W, int C, int k, int stride, void* stream);
+/* The image tail of pSp inference, from ONE read of the decoder's image x [N][S][S][3] (NHWC fp32, what ToRGB returns; S = 256 f,
+ * f in {1, 2, 4}).  Each output may be NULL (not wanted), at least one is given:
+ *   pooled [N][3][256][256] fp32 = nn.AdaptiveAvgPool2d((256, 256)) (modules/psp/psp.py:33,113-114 face_pool): every window summed
+ *          row-major, one multiply by 1 / f^2 -- independent of the launch shape; a plain transposition for f = 1;
+ *   unit   [N][3][256][256] fp32 = (pooled + 1) / 2, the operand of SSIM / MS-SSIM in psp_inference.py:116-117 (evaluate);
+ *   u8     [N][256][256][3] uint8 = tensor2im (psp_inference.py:106-112 with (shift, scale) = (1, 0.5); gradio_serve.py:45-51 with
+ *          (0, 1)): t = (pooled + shift) * scale, t < 0 -> 0, t > 1 -> 1, t * 255, truncation; every step one rounded fp32 operation
+ *          (never contracted into an FMA), so it equals numpy float32 on ``pooled`` bit for bit.  NaN -> 0 (outside the contract).
+ * x, pooled, unit 16-byte and u8 4-byte aligned, else FMI_ERR_BAD_ARG; any other S is FMI_ERR_UNSUPPORTED (callers keep
+ * fmi_avgpool_f32 / fmi_adaptive_avgpool_f32 for those). */
+int fmi_image_tail_f32(const float* x, float* pooled, float* unit, uint8_t* u8, int N, int S, float shift, float scale, void* stream);
+/* The same uint8 conversion for planar input: x [N][C][H][W] fp32 -> u8 [N][H][W][3], any H, W.  C = 3 (the resized image of
+ * gradio_serve.py:59-63) or C = 1 with the channel replicated (the detected mask: psp_inference.py:183-184
+ * tensor2im(mask.repeat((3, 1, 1))), gradio_serve.py:60); other C are FMI_ERR_UNSUPPORTED. */
+int fmi_planes_to_u8_f32(const float* x, uint8_t* u8, int N, int C, int H, int W, float shift, float scale, void* stream);
 /* out[p] = (float) argmax_c x[p][c] (first maximum wins, NaN is the maximum): PICNet_inference.py:100-101
  * mask_detector(src, 'train').argmax(1).float(); bit exact */
 int fmi_argmax_channels_f32(const float* x, float* out, int64_t pixels, int C, void* stream);
