@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libfmi_hip.so")
 
 c_f = C.c_void_p  # device float*
-i32, i64, f32, vp = C.c_int, C.c_int64, C.c_float, C.c_void_p
+i32, i64, f32, f64, vp = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_void_p
 
 
 class ConvDesc(C.Structure):
@@ -136,6 +136,10 @@ SIGNATURES = {
     "fmi_reduce_loss_f32": [i32, vp, vp, i64, f32, f32, vp, vp],
     "fmi_reduce_loss_bwd_f32": [i32, vp, vp, i64, f32, f32, vp, vp, vp],
     "fmi_ssim_f32": [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp],
+    "fmi_seg_ce_dice_fwd_f32": [vp, vp, i32, i64, i32, f64, vp, vp, vp, i64, vp],
+    "fmi_seg_ce_dice_bwd_f32": [vp, vp, i32, i64, i32, f64, vp, vp, vp, vp],
+    "fmi_seg_dice_score_f32": [vp, vp, i32, i32, i64, i32, f64, vp, vp, i64, vp],
+    "fmi_plane_sums_f32": [vp, vp, i32, i64, vp, vp, i64, vp],
     "fmi_cx_channel_mean_f32": [vp, vp, i64, i32, vp],
     "fmi_cx_normalise_f32": [vp, vp, vp, vp, i64, i32, vp],
     "fmi_cx_normalise_bwd_f32": [vp, vp, vp, vp, i64, i32, vp],

@@ -25,7 +25,14 @@ static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b;
 static inline bool fmi_det() { return false; }          // the launch-decomposition switches have no meaning in the emulation
 
 #else  // ------------------------------- device build -------------------------------
+#ifdef FMI_HOST_THREADS
+// The same branch compiled with g++ for kernels that FMI_HOST_EMU's single-threaded loops cannot drive -- workgroup reductions with
+// wave shuffles, LDS and __syncthreads (csrc/segloss.hip; tests/test_host_mask_detector_train.py): host_threads.h stands in for the HIP
+// runtime header only (one OS thread per work-item), so every helper below is the one the device build uses.
+#include "host_threads.h"
+#else
 #include <hip/hip_runtime.h>
+#endif
 #include <stdlib.h>
 
 #define FMI_WAVE 64

@@ -1573,6 +1573,86 @@ def mse_to_const(a, c0):
     return _ReduceLoss.apply(2, a.contiguous(), None, float(c0), 1.0 / a.numel())
 
 
+def _seg_args(logits_nhwc, target, what):
+    """checked (logits, target, kind, N, HW, C) of the segmentation loss / metric: logits NHWC fp32 [N, H, W, C], target [N, H, W] int64
+    (the dataset's map; kind 0) or fp32 (kind 1); both 16-byte aligned for the kernels' vector loads"""
+    for t in (logits_nhwc, target):
+        if not t.is_cuda:
+            raise FmiError("face_mask_inpaint_amd ops need device tensors (there is no CPU fallback)")
+    if logits_nhwc.dim() != 4 or logits_nhwc.dtype != torch.float32:
+        raise FmiError(f"{what}: logits are NHWC fp32 [N, H, W, C], got {tuple(logits_nhwc.shape)} {logits_nhwc.dtype}")
+    if target.dtype not in (torch.int64, torch.float32):
+        raise FmiError(f"{what}: the target is an int64 or fp32 map, got {target.dtype}")
+    n, h, w, c = logits_nhwc.shape
+    if tuple(target.shape) != (n, h, w):
+        raise FmiError(f"{what}: target {tuple(target.shape)} does not match logits {tuple(logits_nhwc.shape)}")
+    if not 2 <= c <= 8:
+        raise FmiError(f"{what}: 2 <= C <= 8 classes, got {c}")
+    x, t = logits_nhwc.contiguous(), target.detach().contiguous()
+    if x.data_ptr() % 16:
+        x = x.clone()
+    if t.data_ptr() % 16:
+        t = t.clone()
+    return x, t, (0 if t.dtype == torch.int64 else 1), n, h * w, c
+
+
+class _SegCeDice(torch.autograd.Function):
+    """train_mask_detector.py:131-134 on NHWC logits: 2 launches forward (sums + finish), 1 backward; nothing per pixel is saved"""
+
+    @staticmethod
+    def forward(ctx, x, t, kind, eps):
+        p, c = x.numel() // x.shape[-1], x.shape[-1]
+        out3 = torch.empty(3, device=x.device, dtype=torch.float32)
+        sums = torch.empty(1 + 3 * c, device=x.device, dtype=torch.float64)
+        part = torch.empty(1024 * (1 + 3 * c), device=x.device, dtype=torch.float64)
+        _L().seg_ce_dice_fwd_f32(_p(x), _p(t), kind, p, c, eps, _p(out3), _p(sums), _p(part), part.numel(), _st())
+        ctx.save_for_backward(x, t, sums)
+        ctx.cfg = (kind, eps)
+        ce, dice, loss = out3.unbind(0)
+        ctx.mark_non_differentiable(ce, dice)
+        return loss, ce, dice
+
+    @staticmethod
+    def backward(ctx, g, _gce, _gdice):
+        x, t, sums = ctx.saved_tensors
+        kind, eps = ctx.cfg
+        gx = torch.empty_like(x)
+        g = g.to(torch.float32).contiguous()
+        _L().seg_ce_dice_bwd_f32(_p(x), _p(t), kind, x.numel() // x.shape[-1], x.shape[-1], eps, _p(sums), _p(g), _p(gx), _st())
+        return gx, None, None, None
+
+
+def seg_ce_dice_loss(logits_nhwc, target, eps=1e-6):
+    """(loss, ce, dice), three 0-dim device tensors: nn.CrossEntropyLoss()(logits, t) + dice_loss(softmax(logits, 1), one_hot(t, C), multiclass=True)
+    with t = (target > 0) -- the training objective of train_mask_detector.py:127-134 from one pass over the NHWC logits.  ``loss`` is
+    differentiable with respect to the logits; ``ce`` and ``dice`` are its two terms for logging.  No host synchronisation."""
+    x, t, kind, _, _, _ = _seg_args(logits_nhwc, target, "seg_ce_dice_loss")
+    return _SegCeDice.apply(x, t, kind, float(eps))
+
+
+def seg_dice_score(logits_nhwc, target, eps=1e-6):
+    """0-dim device tensor: the validation metric of train_mask_detector.evaluate (:34-35,47-49) for one batch --
+    multiclass_dice_coeff(one_hot(logits.argmax(C))[:, 1:], one_hot(target > 0)[:, 1:], reduce_batch_first=False).  No gradient."""
+    x, t, kind, n, hw, c = _seg_args(logits_nhwc.detach(), target, "seg_dice_score")
+    out = torch.empty((), device=x.device, dtype=torch.float32)
+    part = torch.empty(n * 64 * 3 * (c - 1), device=x.device, dtype=torch.float64)
+    _L().seg_dice_score_f32(_p(x), _p(t), kind, n, hw, c, float(eps), _p(out), _p(part), part.numel(), _st())
+    return out
+
+
+def plane_sums(a, b, planes):
+    """fp64 [planes, 3] = (sum a b, sum a, sum b) over each of ``planes`` equal contiguous parts of two fp32 device tensors: the
+    torch.dot / torch.sum calls of dice_coeff (modules/loss.py:157-158).  No gradient."""
+    a, b = _no_grad_input(a, "plane_sums").contiguous(), _no_grad_input(b, "plane_sums").contiguous()
+    _chk(a, b)
+    if a.shape != b.shape or a.numel() == 0 or a.numel() % planes:
+        raise FmiError(f"plane_sums: {tuple(a.shape)} / {tuple(b.shape)} do not split into {planes} equal planes")
+    out = torch.empty((planes, 3), device=a.device, dtype=torch.float64)
+    part = torch.empty(planes * (256 if planes == 1 else 64) * 3, device=a.device, dtype=torch.float64)
+    _L().plane_sums_f32(_p(a), _p(b), planes, a.numel() // planes, _p(out), _p(part), part.numel(), _st())
+    return out
+
+
 class _L2NormRows(torch.autograd.Function):
     """y = x / (||x|| + eps) over the last dimension"""
 

@@ -1,5 +1,8 @@
-"""Host-side mirror of modules/loss.py: VGGLoss (loss.py:16-65) and GANOptimizer (loss.py:68-144) with the
-reference's signatures and return values; dice_* helpers belong to the mask-detector trainer and are out of scope.
+"""Host-side mirror of modules/loss.py: VGGLoss (loss.py:16-65), GANOptimizer (loss.py:68-144) and the UNet losses dice_coeff /
+multiclass_dice_coeff / dice_loss (loss.py:148-186) with the reference's signatures and return values.  The dice_* helpers are the
+general form (any two equal-shaped fp32 device tensors, values only): the sums come from one kernel (FF.plane_sums) and the rest is
+[planes]-sized bookkeeping on the device.  The mask-detector trainer does not go through them: its objective and its gradient are
+FF.seg_ce_dice_loss, its validation metric FF.seg_dice_score.
 """
 from __future__ import annotations
 
@@ -227,3 +230,47 @@ class GANOptimizer(nn.Module):
         style_loss = self.style_loss(gen_img, src_img, src_mask) * self.lambda_style
         cx_loss = self.contextual_loss(gen_img, ref_img, src_mask) * self.lambda_cx
         return D_loss, G_loss + perc_loss + style_loss + cx_loss
+
+
+######################## Unet Losses #########################################
+def _dice_from_sums(sums, epsilon):
+    """[..., 3] fp64 (inter, sum input, sum target) -> dice_coeff's value per entry (loss.py:157-162); the `sets_sum == 0` branch is a
+    torch.where on the device instead of the reference's .item()"""
+    inter, sets_sum = sums[..., 0], sums[..., 1] + sums[..., 2]
+    sets_sum = torch.where(sets_sum == 0, 2 * inter, sets_sum)
+    return (2 * inter + epsilon) / (sets_sum + epsilon)
+
+
+def dice_coeff(input, target, reduce_batch_first=False, epsilon=1e-6):
+    """Average of Dice coefficient for all batches, or for a single mask (loss.py:148-168) -> 0-dim fp32 device tensor"""
+    assert input.size() == target.size()
+    if input.dim() == 2 and reduce_batch_first:
+        raise ValueError(f'Dice: asked to reduce batch but got tensor without batch dimension (shape {input.shape})')
+    if input.dim() == 2 or reduce_batch_first:
+        return _dice_from_sums(FF.plane_sums(input, target, 1)[0], epsilon).float()
+    # the reference recurses over the leading dimensions down to single [H, W] masks and calls itself there with the DEFAULT epsilon
+    # (loss.py:167); nested means over equal-sized groups are the mean over all masks
+    planes = input.numel() // (input.shape[-1] * input.shape[-2])
+    return _dice_from_sums(FF.plane_sums(input, target, planes), 1e-6).mean().float()
+
+
+def multiclass_dice_coeff(input, target, reduce_batch_first=False, epsilon=1e-6):
+    """Average of Dice coefficient for all classes (loss.py:171-179): dice_coeff(input[:, c], target[:, c], ...) averaged over c, for
+    input / target [N, C, ...] of any rank the reference's recursion takes"""
+    assert input.size() == target.size()
+    n, c = input.shape[0], input.shape[1]
+    if input.dim() == 3 or reduce_batch_first:
+        if input.dim() == 3 and reduce_batch_first:  # input[:, c] is 2-D: a single mask without a batch dimension (loss.py:151-154)
+            raise ValueError(f'Dice: asked to reduce batch but got tensor without batch dimension (shape {input[:, 0].shape})')
+        sums = FF.plane_sums(input, target, n * c).view(n, c, 3).sum(0)  # one mask per class over everything else
+        return _dice_from_sums(sums, epsilon).mean().float()
+    # per class the mean over single [H, W] masks with the default epsilon (loss.py:164-168); equal-sized groups: the mean over all
+    planes = input.numel() // (input.shape[-1] * input.shape[-2])
+    return _dice_from_sums(FF.plane_sums(input, target, planes), 1e-6).mean().float()
+
+
+def dice_loss(input, target, multiclass=False):
+    """Dice loss (objective to minimize) between 0 and 1 (loss.py:182-186)"""
+    assert input.size() == target.size()
+    fn = multiclass_dice_coeff if multiclass else dice_coeff
+    return 1 - fn(input, target, reduce_batch_first=True)

@@ -518,6 +518,35 @@ int fmi_ssim_valid_f32(const float* img1, const float* img2, const float* window
 int fmi_avgpool2_pad_f32(const float* x, float* y, int planes, int H, int W, int pad_h, int pad_w, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The mask-detector trainer's loss and metric (csrc/segloss.hip).  logits: NHWC fp32 [P][C], P = N * H * W, 2 <= C <= 8 (any other C is
+ * FMI_ERR_BAD_ARG; C = 2 is MaskDetector's).  target: target_kind 0 = the dataset's int64 map, 1 = an fp32 map; the class of a pixel is
+ * (target > 0) -- the `(true_masks > 0)` of train_mask_detector.py:127 is applied in the kernel.  logits / target / dlogits 16-byte
+ * aligned.  ws_part: fp64 scratch for the per-workgroup partial rows, added in a fixed order by a finishing launch (no atomics, nothing
+ * to zero, bit-reproducible in either mode).
+ * ---------------------------------------------------------------------- */
+/* train_mask_detector.py:131-134: nn.CrossEntropyLoss()(logits, t) + dice_loss(softmax(logits, 1).float(), one_hot(t, C).permute(0, 3, 1, 2)
+ * .float(), multiclass=True) with modules/loss.py:148-186, from one pass over logits and target.  out3 = (ce, dice, ce + dice) with
+ * ce = mean_p -log p_t and dice = 1 - mean_c (2 I_c + eps) / (sum p_c + sum t_c + eps), dice_coeff's `sets_sum == 0 -> 2 * inter`
+ * branch (loss.py:159-160) evaluated on the device.  sums[1 + 3 C] (fp64, kept for the backward) = sum -log p_t, then I_c = sum p_c t_c,
+ * sum p_c, sum t_c per class.  ws_doubles >= 1024 * (1 + 3 C). */
+int fmi_seg_ce_dice_fwd_f32(const float* logits, const void* target, int target_kind, int64_t P, int C, double eps, float* out3,
+                            double* sums, double* ws_part, int64_t ws_doubles, void* stream);
+/* the backward of the above (autograd through train_mask_detector.py:131-137) in one pass that recomputes the softmax:
+ * dlogits[p][k] = g p_k (h_k - sum_j p_j h_j) + g (p_k - t_k) / P,  h_c = -(1 / C) (2 t_c (U_c + eps) - (2 I_c + eps)) / (U_c + eps)^2,
+ * U_c = sum p_c + sum t_c; gout is a DEVICE scalar (the upstream gradient of ce + dice), sums is what the forward left */
+int fmi_seg_ce_dice_bwd_f32(const float* logits, const void* target, int target_kind, int64_t P, int C, double eps, const double* sums,
+                            const float* gout, float* dlogits, void* stream);
+/* the validation metric of evaluate() (train_mask_detector.py:34-35,47-49): multiclass_dice_coeff(one_hot(argmax)[:, 1:], one_hot(t)[:, 1:],
+ * reduce_batch_first=False) -- per sample the argmax over classes (first maximum wins, as torch.argmax), dice_coeff per (sample, class
+ * 1 .. C-1) including its empty branch ((0 + eps) / (0 + eps) = 1), mean over classes, mean over samples -> out[0].
+ * logits [N][HW][C]; ws_doubles >= N * 64 * 3 * (C - 1); N <= 65535. */
+int fmi_seg_dice_score_f32(const float* logits, const void* target, int target_kind, int N, int64_t HW, int C, double eps, float* out,
+                           double* ws_part, int64_t ws_doubles, void* stream);
+/* out3[plane] = (sum a b, sum a, sum b) in fp64 over planes of n elements of two fp32 tensors: the torch.dot / torch.sum calls of
+ * dice_coeff (modules/loss.py:157-158) for arbitrary inputs.  ws_doubles >= planes * (planes == 1 ? 256 : 64) * 3; planes <= 65535. */
+int fmi_plane_sums_f32(const float* a, const float* b, int planes, int64_t n, double* out3, double* ws_part, int64_t ws_doubles, void* stream);
+
+/* ------------------------------------------------------------------------
  * Contextual loss (external_function.py:231-274), x,y NHWC features [N,P,C].
  * ---------------------------------------------------------------------- */
 int fmi_cx_channel_mean_f32(const float* y, float* mu /*[C] zeroed*/, int64_t rows, int C, void* stream);
