@@ -875,8 +875,9 @@ class _ConvTranspose2d(torch.autograd.Function):
 
 class _ConvTransposePair(torch.autograd.Function):
     """ConvTranspose2d(x1, W1) + ConvTranspose2d(x2, W2) + bias, both kernel 3 / stride 2 / padding 1 / output_padding 1, in ONE launch
-    (fmi_conv_transpose2d_pair_f32: ResBlockDecoder's main path and bypass, base_function.py:297-305).  The backward is the two single
-    ConvTranspose2d backwards on the shared gradient."""
+    (fmi_conv_transpose2d_pair_f32: ResBlockDecoder's main path and bypass, base_function.py:297-305).  The backward is one launch too
+    where fmi_conv_transpose2d_pair_bwd_f32 takes the shape (32 output channels, all gradients wanted), else the two single ConvTranspose2d
+    backwards on the shared gradient."""
 
     @staticmethod
     def forward(ctx, x1, wf1, wt1, x2, wf2, wt2, bias, w3_1, w3_2):
@@ -898,6 +899,22 @@ class _ConvTransposePair(torch.autograd.Function):
 
         x1, wf1, x2, wf2 = ctx.saved_tensors
         gy = gy.contiguous()
+        n, h, w, cs1 = x1.shape
+        cs2, cb = x2.shape[3], wf1.shape[1]
+        need = ctx.needs_input_grad
+        wf3a, wf3b = ctx.w3s[0][0], ctx.w3s[1][0]
+        if need[0] and need[1] and need[3] and need[4] and wf3a is not None and wf3b is not None and gy.data_ptr() % 16 == 0:
+            lib = _L()
+            d, _, _ = conv_desc(n, ctx.HW[0], ctx.HW[1], cb, cs1, 3, 3, 2, 1)
+            if lib.conv_transpose2d_pair_bwd_supported(C.byref(d), cs1, cs2):  # the whole backward from one read of gy (csrc/convt3x3_bwd.hip)
+                gx1, gx2, gwf1, gwf2 = torch.empty_like(x1), torch.empty_like(x2), torch.empty_like(wf1), torch.empty_like(wf2)
+                gb = torch.empty(cb, device=gy.device, dtype=torch.float32) if (ctx.has_bias and need[6]) else None
+                ws_bytes = lib.conv_transpose2d_pair_bwd_ws_bytes(C.byref(d), cs1, cs2)
+                ws = torch.empty(ws_bytes // 4, device=gy.device, dtype=torch.float32)
+                with _prof(f"convT_pair_bwd|{n}x{h}x{w} {cs1}+{cs2}->{cb}", 2 * 2.0 * (x1.numel() + x2.numel()) * cb * 9):
+                    lib.conv_transpose2d_pair_bwd_f32(C.byref(d), _p(x1), _p(x2), cs2, _p(gy), C.c_void_p(wf3a.data_ptr()), C.c_void_p(wf3b.data_ptr()),
+                                                      _p(gx1), _p(gx2), _p(gwf1), _p(gwf2), _p(gb), _p(ws), ws_bytes, _st())
+                return gx1, gwf1, None, gx2, gwf2, None, gb, None, None
         outs = []
         for x, wf, w3, ix, iw in ((x1, wf1, ctx.w3s[0], 0, 1), (x2, wf2, ctx.w3s[1], 3, 4)):
             ns = types.SimpleNamespace(saved_tensors=(x, wf), cfg=(3, 3, 2, 1), has=(False, False), HW=ctx.HW, wf3=w3[0], x3=None,

@@ -143,6 +143,17 @@ int fmi_conv2d_fwd_f32(const fmi_conv_desc* d, const float* x, const float* wf, 
  * fmi_conv2d_dgrad_f32 calls (the second with the first's result as residual). */
 int fmi_conv_transpose2d_pair_f32(const fmi_conv_desc* d, const float* x1, const float* x2, int K2, const void* w3b, const float* bias,
                                   float* y, void* stream);
+/* Whole backward of fmi_conv_transpose2d_pair_f32 from one read of dy (csrc/convt3x3_bwd.hip): dx1 / dx2 (layouts of x1 / x2),
+ * dwf1 [9][C][K] / dwf2 [9][C][K2] and dbias [C] are WRITTEN (no atomics, nothing to zero, bit-identical from run to run in either
+ * reproducibility mode); each of the five may be NULL.  d as for the forward (d->C = 32 output channels, d->K = x1's channels), dense
+ * tensors, K and K2 in {32, 64}; wf3a / wf3b: the packs' wf3 piece images.  ws: device memory of
+ * fmi_conv_transpose2d_pair_bwd_ws_bytes(d, K, K2) bytes, contents irrelevant.  Null descriptor or required pointer, a short workspace
+ * or a pointer off 16-byte alignment: FMI_ERR_BAD_ARG; any other geometry: FMI_ERR_UNSUPPORTED (_supported says 0). */
+int fmi_conv_transpose2d_pair_bwd_supported(const fmi_conv_desc* d, int K, int K2);
+int fmi_conv_transpose2d_pair_bwd_ws_bytes(const fmi_conv_desc* d, int K, int K2);
+int fmi_conv_transpose2d_pair_bwd_f32(const fmi_conv_desc* d, const float* x1, const float* x2, int K2, const float* dy, const void* wf3a,
+                                      const void* wf3b, float* dx1, float* dx2, float* dwf1, float* dwf2, float* dbias, void* ws,
+                                      int64_t ws_bytes, void* stream);
 int fmi_conv2d_dgrad_f32(const fmi_conv_desc* d, const float* dy, const float* wt, const float* bias,
                          const float* residual, float* dx, int batch_w, int64_t w_bstride, void* stream);
 /* Adjoint of  act(x) -> conv : dx = conv_adjoint(dy, wt) * act'(x), act' = (mask > 0 ? 1 : mask_slope); mask = x or act(x), dx's layout.
