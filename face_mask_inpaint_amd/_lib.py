@@ -141,6 +141,8 @@ SIGNATURES = {
     "fmi_seg_ce_dice_bwd_f32": [vp, vp, i32, i64, i32, f64, vp, vp, vp, vp],
     "fmi_seg_dice_score_f32": [vp, vp, i32, i32, i64, i32, f64, vp, vp, i64, vp],
     "fmi_plane_sums_f32": [vp, vp, i32, i64, vp, vp, i64, vp],
+    "fmi_psp_pixel_head_fwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp],
+    "fmi_psp_pixel_head_bwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "fmi_cx_channel_mean_f32": [vp, vp, i64, i32, vp],
     "fmi_cx_normalise_f32": [vp, vp, vp, vp, i64, i32, vp],
     "fmi_cx_normalise_bwd_f32": [vp, vp, vp, vp, i64, i32, vp],

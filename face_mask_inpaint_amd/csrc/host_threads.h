@@ -22,6 +22,10 @@ struct dim3 {
 struct float4 { float x, y, z, w; };
 struct longlong2 { long long x, y; };
 static inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
+// the separately rounded fp32 operations (build without -ffast-math / FMA contraction, as the tests do)
+static inline float __fmul_rn(float a, float b) { return a * b; }
+static inline float __fadd_rn(float a, float b) { return a + b; }
+static inline float __fsub_rn(float a, float b) { return a - b; }
 typedef void* hipStream_t;
 static thread_local dim3 threadIdx, blockIdx;
 static dim3 gridDim, blockDim;

@@ -1670,6 +1670,86 @@ def plane_sums(a, b, planes):
     return out
 
 
+class _PspPixelHead(torch.autograd.Function):
+    """criteria/__init__.py:58-65,80-87 from the planar images: 2 launches forward (pass + finish), 1 backward; nothing per pixel is saved.
+    y_hat is contiguous or channels-last (``hwc``: what pSp.forward's pool returns); its gradient comes back in the same layout"""
+
+    @staticmethod
+    def forward(ctx, y_hat, y, ref, mask, hwc):
+        n, _, h, w = y_hat.shape
+        inner = ref is not None and mask is not None
+        dev = y_hat.device
+        pair_out = torch.empty((2 * n, h, w, 3), device=dev, dtype=torch.float32)
+        pair_in = torch.empty((2 * n, h, w, 3), device=dev, dtype=torch.float32) if inner else None
+        out2 = torch.empty(2, device=dev, dtype=torch.float32)
+        part = torch.empty(n * 64 * 2, device=dev, dtype=torch.float64)
+        _L().psp_pixel_head_fwd_f32(_p(y_hat), _p(y), _p(ref), _p(mask), _p(pair_out), _p(pair_in), None, _p(out2), n, h, w, hwc, _p(part),
+                                    part.numel(), _st())
+        ctx.save_for_backward(y_hat, y, ref, mask)
+        ctx.hwc = hwc
+        ctx.set_materialize_grads(False)
+        l2, l2_ref = out2.unbind(0)
+        if not inner:
+            return pair_out, None, l2, None
+        return pair_out, pair_in, l2, l2_ref
+
+    @staticmethod
+    def backward(ctx, g_out, g_in, g_l2, g_l2_ref):
+        y_hat, y, ref, mask = ctx.saved_tensors
+        if g_out is None and g_in is None and g_l2 is None and g_l2_ref is None:
+            return None, None, None, None, None
+        n, _, h, w = y_hat.shape
+        g_out = g_out.to(torch.float32).contiguous() if g_out is not None else None
+        g_in = g_in.to(torch.float32).contiguous() if g_in is not None else None
+        zero = None
+        if g_l2 is None or g_l2_ref is None:
+            zero = torch.zeros((), device=y_hat.device, dtype=torch.float32)
+        g2 = torch.stack([zero if g is None else g.to(torch.float32).reshape(()) for g in (g_l2, g_l2_ref)])  # the DEVICE pair
+        d = torch.empty_like(y_hat)  # y_hat's own strides
+        _L().psp_pixel_head_bwd_f32(_p(y_hat), _p(y), _p(ref), _p(mask), _p(g_out), _p(g_in), _p(g2), _p(d), n, h, w, ctx.hwc, _st())
+        return d, None, None, None, None
+
+
+def psp_pixel_head(y_hat, y, ref=None, mask=None):
+    """the pixel side of pSpLoss.__call__ (criteria/__init__.py:58-65,80-87) from one pass over the planar images: y_hat, y, ref
+    [N, 3, H, W] fp32 and mask [N, H, W] fp32 (ref / mask may be None) -> ``(pair_out, pair_in | None, l2, l2_ref | None)``:
+
+      pair_out [2N, H, W, 3]  cat(to_nhwc(y_hat * (1 - mask)), to_nhwc(y * (1 - mask))) -- the batch LPIPS.forward_pair_nhwc takes
+      pair_in  [2N, H, W, 3]  cat(to_nhwc(y_hat * mask), to_nhwc(ref * mask)); None unless ref and mask are both given
+      l2, l2_ref              F.mse_loss of the two halves of each pair, 0-dim device tensors (l2_ref None with pair_in)
+
+    With mask None the outer pair is the plain images.  y_hat may be contiguous or channels-last in memory (what pSp.forward returns: read
+    as it is, no transposition); any other striding is copied.  Differentiable with respect to y_hat only; no host synchronisation."""
+    ts = dict(y_hat=y_hat, y=y, ref=ref, mask=mask)
+    if y_hat is None or y is None:
+        raise FmiError("psp_pixel_head: y_hat and y are required")
+    for name, t in ts.items():
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise FmiError("psp_pixel_head: face_mask_inpaint_amd ops need device tensors (there is no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise FmiError(f"psp_pixel_head: {name} is fp32, got {t.dtype}")
+        if name != "y_hat" and t.requires_grad and torch.is_grad_enabled():
+            raise FmiError(f"psp_pixel_head is differentiable with respect to y_hat only: detach {name}")
+    if y_hat.dim() != 4 or y_hat.shape[1] != 3 or y_hat.numel() == 0:
+        raise FmiError(f"psp_pixel_head: y_hat is [N, 3, H, W], got {tuple(y_hat.shape)}")
+    n, _, h, w = y_hat.shape
+    for name in ("y", "ref"):
+        if ts[name] is not None and ts[name].shape != y_hat.shape:
+            raise FmiError(f"psp_pixel_head: {name} {tuple(ts[name].shape)} does not match y_hat {tuple(y_hat.shape)}")
+    if mask is not None and tuple(mask.shape) != (n, h, w):
+        raise FmiError(f"psp_pixel_head: mask is [N, H, W] = {(n, h, w)}, got {tuple(mask.shape)}")
+    det = lambda t: None if t is None else t.detach().contiguous()
+    hwc = 0
+    if not y_hat.is_contiguous():
+        if y_hat.permute(0, 2, 3, 1).is_contiguous():
+            hwc = 1
+        else:
+            y_hat = y_hat.contiguous()
+    return _PspPixelHead.apply(y_hat, det(y), det(ref), det(mask), hwc)
+
+
 class _L2NormRows(torch.autograd.Function):
     """y = x / (||x|| + eps) over the last dimension"""
 

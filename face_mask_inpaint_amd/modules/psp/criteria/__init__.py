@@ -9,6 +9,7 @@ import torch
 from torch import nn
 
 from .... import functional as FF
+from ...._lib import FmiError
 from ...loss import VGGLoss
 from . import id_loss
 from .lpips.lpips import LPIPS
@@ -37,6 +38,9 @@ class pSpLoss(nn.Module):
         # True: loss_dict holds detached device tensors instead of python floats -- no host synchronisation inside __call__, so a
         # whole training step can be captured in a HIP graph; the caller converts after the replay (the reference converts in place)
         self.defer_logs = False
+        # True: the pixel side of __call__ (the masked products, both L2 terms and the NHWC batches LPIPS consumes) comes from
+        # FF.psp_pixel_head -- one pass over the planar images forward, one backward -- instead of to_nhwc / mask_mul / mse_loss / cat
+        self.fused_head = False
         if self.lpips_lambda > 0:  # the reference builds it on lpips_lambda alone and uses it for lpips_lambda_ref too (:29-30,82-85)
             self.lpips_loss = LPIPS(net_type="alex").eval()
         if self.id_lambda > 0:
@@ -49,7 +53,50 @@ class pSpLoss(nn.Module):
     def _log(self, v):
         return v.detach() if self.defer_logs else float(v.detach())
 
+    def _call_fused(self, x, y, y_hat, latent, latent_avg=None, ref=None, mask=None):
+        """__call__ with the pixel head fused: same terms, same order, same loss_dict keys"""
+        loss_dict, loss, id_logs = {}, 0.0, None
+        if ref is not None and mask is None:
+            raise FmiError("pSpLoss: ref needs a mask (criteria/__init__.py:80-81 multiplies both by it)")
+        n = y_hat.shape[0]
+        pair_out, pair_in, l2, l2_ref = FF.psp_pixel_head(y_hat, y, ref, mask)
+        if self.id_lambda > 0:
+            self.id_loss.defer_logs = self.defer_logs
+            loss_id, sim_improvement, id_logs = self.id_loss(y_hat, y, x)
+            loss_dict["loss_id"] = self._log(loss_id)
+            loss_dict["id_improve"] = sim_improvement if self.defer_logs else float(sim_improvement)
+            loss = loss_id * self.id_lambda
+        if self.l2_lambda > 0:
+            loss_dict["loss_l2"] = self._log(l2)
+            loss = loss + l2 * self.l2_lambda
+        if self.lpips_lambda > 0:
+            loss_lpips = self.lpips_loss.forward_pair_nhwc(pair_out)
+            loss_dict["loss_lpips"] = self._log(loss_lpips)
+            loss = loss + loss_lpips * self.lpips_lambda
+        if self.style_lambda > 0 and mask is not None:
+            with torch.no_grad():  # logged only in the reference (criteria/__init__.py:74-76)
+                loss_dict["loss_style"] = self._log(self.vgg_loss(FF.to_nchw(pair_out[:n]), x, lossType="style") * self.style_lambda)
+        if ref is not None:
+            if self.lpips_lambda_ref > 0:
+                loss_lpips_ref = self.lpips_loss.forward_pair_nhwc(pair_in)
+                loss_dict["loss_lpips_ref"] = self._log(loss_lpips_ref)
+                loss = loss + loss_lpips_ref * self.lpips_lambda_ref
+            if self.l2_lambda_ref > 0:
+                loss_dict["loss_l2_ref"] = self._log(l2_ref)
+                loss = loss + l2_ref * self.l2_lambda_ref
+            if self.cx_lambda > 0:
+                with torch.no_grad():  # logged only (criteria/__init__.py:88-90)
+                    loss_dict["loss_context"] = self._log(self.vgg_loss(FF.to_nchw(pair_in[:n]), FF.to_nchw(pair_in[n:]), lossType="contextual") * self.cx_lambda)
+        if self.w_norm_lambda > 0 and latent_avg is not None:
+            loss_w_norm = self.w_norm_loss(latent, latent_avg.to(latent.device))
+            loss_dict["loss_w_norm"] = self._log(loss_w_norm)
+            loss = loss + loss_w_norm * self.w_norm_lambda
+        loss_dict["loss"] = self._log(loss) if torch.is_tensor(loss) else float(loss)
+        return loss, loss_dict, id_logs
+
     def __call__(self, x, y, y_hat, latent, latent_avg=None, ref=None, mask=None):
+        if self.fused_head:
+            return self._call_fused(x, y, y_hat, latent, latent_avg, ref, mask)
         loss_dict, loss, id_logs = {}, 0.0, None
         m = mask.contiguous() if mask is not None else None  # [N,H,W]
         yh = FF.to_nhwc(y_hat)

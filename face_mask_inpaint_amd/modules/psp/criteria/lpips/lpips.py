@@ -40,3 +40,16 @@ class LPIPS(nn.Module):
             v = FF.lpips_layer(f[:n], f[n:], lin[1].weight.view(-1), 1.0 / (hw * n))
             total = v if total is None else total + v
         return total
+
+    def forward_pair_nhwc(self, pair: torch.Tensor):
+        """``forward`` from the trunk call on, for an already-built NHWC batch [2N, H, W, 3]: images 0 .. N-1 are x, N .. 2N-1 are y
+        (what FF.psp_pixel_head returns)"""
+        n = pair.shape[0] // 2
+        feats = self.net.nhwc(pair)
+        total = None
+        for f, lin in zip(feats, self.lin):
+            hw = f.shape[1] * f.shape[2]
+            # (fx - fy)^2 -> 1x1 lin conv -> mean over (H, W) -> sum over the batch, / N   (lpips.py:33-36)
+            v = FF.lpips_layer(f[:n], f[n:], lin[1].weight.view(-1), 1.0 / (hw * n))
+            total = v if total is None else total + v
+        return total

@@ -558,6 +558,35 @@ int fmi_seg_dice_score_f32(const float* logits, const void* target, int target_k
 int fmi_plane_sums_f32(const float* a, const float* b, int planes, int64_t n, double* out3, double* ws_part, int64_t ws_doubles, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The pixel head of pSpLoss.__call__ (csrc/psploss.hip; modules/psp/criteria/__init__.py:58-65,80-87).  y_hat, y, ref: planar fp32
+ * [N][3][H][W] as pSp.forward and the dataloader hand them over (ref may be NULL); mask [N][H][W] fp32 (may be NULL).  m = mask,
+ * im = 1 - m (one rounded subtraction); with a NULL mask im = 1.  The inner pair (the `ref` side, :80-87) exists only when ref AND mask
+ * are given; without them it is skipped, its sum is 0 and a non-NULL pair_in / g_pair_in is FMI_ERR_BAD_ARG.  N <= 65535.
+ * y_hat_hwc = 1: y_hat (and d_y_hat) is [N][H][W][3] in memory -- the channels-last tensor pSp.forward's face_pool returns, read without
+ * a transposition; 0: planar; anything else is FMI_ERR_BAD_ARG.  The arithmetic and the outputs do not depend on it.
+ * All pointers 4-byte aligned (sums / ws_part 8), else FMI_ERR_BAD_ARG; when H * W % 4 == 0 and every tensor is 16-byte aligned a thread
+ * takes four pixels with 16-byte loads and stores, otherwise one pixel.
+ * ---------------------------------------------------------------------- */
+/* forward, one pass; every output may be NULL (not wanted), at least one is given:
+ *   pair_out [2N][H][W][3] NHWC: images 0 .. N-1 = y_hat im, N .. 2N-1 = y im -- the batch LPIPS.forward builds with
+ *            cat(to_nhwc(x), to_nhwc(y)) from the operands of :59-60,64-65; every product one rounded fp32 multiply (bit exact);
+ *   pair_in  [2N][H][W][3]: y_hat m, then ref m (:80-81);
+ *   sums     fp64[2] = sum (y_hat im - y im)^2, sum (y_hat m - ref m)^2: the difference in fp32, squared and accumulated in fp64;
+ *   out2     fp32[2] = sums / (3 N H W): the two F.mse_loss values of :59-60,86.
+ * ws_part: fp64 scratch of ws_doubles >= N * 64 * 2 entries (needed when sums or out2 is wanted): per-workgroup partial rows, added in
+ * a fixed order by a finishing launch -- no atomics, nothing to zero, bit-reproducible whether or not fmi_set_deterministic is on. */
+int fmi_psp_pixel_head_fwd_f32(const float* y_hat, const float* y, const float* ref, const float* mask, float* pair_out, float* pair_in,
+                               double* sums, float* out2, int N, int H, int W, int y_hat_hwc, double* ws_part, int64_t ws_doubles, void* stream);
+/* backward with respect to y_hat, one pass and one launch that recomputes the products from the same four inputs (nothing per pixel is
+ * saved).  g_pair_out, g_pair_in [2N][H][W][3] (either may be NULL = zero; only images 0 .. N-1 of each reach y_hat); g2: a DEVICE array
+ * of two floats, the upstream gradients of out2 (no host read).  With count = 3 N H W:
+ *   d_y_hat [N][3][H][W] = im (g_pair_out + g2[0] 2 (y_hat im - y im) / count) + m (g_pair_in + g2[1] 2 (y_hat m - ref m) / count)
+ * with the differences evaluated as im (y_hat - y) and m (y_hat - ref): the same value, one rounding of the difference instead of one per
+ * product, so every entry is within 8 * 2^-24 of the sum of the magnitudes of its four terms. */
+int fmi_psp_pixel_head_bwd_f32(const float* y_hat, const float* y, const float* ref, const float* mask, const float* g_pair_out,
+                               const float* g_pair_in, const float* g2, float* d_y_hat, int N, int H, int W, int y_hat_hwc, void* stream);
+
+/* ------------------------------------------------------------------------
  * Contextual loss (external_function.py:231-274), x,y NHWC features [N,P,C].
  * ---------------------------------------------------------------------- */
 int fmi_cx_channel_mean_f32(const float* y, float* mu /*[C] zeroed*/, int64_t rows, int C, void* stream);
