@@ -143,6 +143,8 @@ SIGNATURES = {
     "fmi_plane_sums_f32": [vp, vp, i32, i64, vp, vp, i64, vp],
     "fmi_psp_pixel_head_fwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp],
     "fmi_psp_pixel_head_bwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "fmi_gan_image_head_fwd_f32": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp],
+    "fmi_gan_image_head_bwd_f32": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "fmi_cx_channel_mean_f32": [vp, vp, i64, i32, vp],
     "fmi_cx_normalise_f32": [vp, vp, vp, vp, i64, i32, vp],
     "fmi_cx_normalise_bwd_f32": [vp, vp, vp, vp, i64, i32, vp],

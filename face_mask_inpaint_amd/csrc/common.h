@@ -105,4 +105,29 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
   return base + idx;
 }
+
+// ---- bilinear, align_corners=True (same source-index arithmetic as ATen's upsample_bilinear2d); pool.hip and ganhead.hip ----
+struct Lerp {
+  int i0, i1;
+  float l0, l1;
+};
+__device__ __forceinline__ Lerp lerp_of(int o, int in, int out) {
+  const float scale = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
+  const float r = scale * (float)o;
+  Lerp l;
+  l.i0 = (int)r;
+  l.i1 = l.i0 + (l.i0 < in - 1 ? 1 : 0);
+  l.l1 = r - (float)l.i0;
+  l.l0 = 1.f - l.l1;
+  return l;
+}
+// reproducible form of the adjoint: every INPUT pixel gathers from the output pixels whose interpolation footprint contains it, in a
+// fixed order (gx is written, not accumulated).  Candidates: outputs around i / scale, tested with the forward's own lerp_of.
+__device__ __forceinline__ void resize_cands(int i, int in, int out, int& lo, int& hi) {
+  const float inv = in > 1 ? (float)(out - 1) / (float)(in - 1) : 0.f;
+  lo = (int)((float)(i - 1) * inv) - 2;
+  hi = (int)((float)(i + 1) * inv) + 2;
+  if (lo < 0) lo = 0;
+  if (hi > out - 1) hi = out - 1;
+}
 #endif

@@ -198,21 +198,7 @@ extern "C" int fmi_maxpool2_bwd_f32(const float* x, const float* gy, float* gx, 
   return fmi_launch_status();
 }
 
-// ---- bilinear, align_corners=True (same source-index arithmetic as ATen's upsample_bilinear2d) ----
-struct Lerp {
-  int i0, i1;
-  float l0, l1;
-};
-__device__ __forceinline__ Lerp lerp_of(int o, int in, int out) {
-  const float scale = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
-  const float r = scale * (float)o;
-  Lerp l;
-  l.i0 = (int)r;
-  l.i1 = l.i0 + (l.i0 < in - 1 ? 1 : 0);
-  l.l1 = r - (float)l.i0;
-  l.l0 = 1.f - l.l1;
-  return l;
-}
+// ---- bilinear, align_corners=True: Lerp / lerp_of / resize_cands live in common.h (shared with ganhead.hip) ----
 __global__ void __launch_bounds__(256) resize_kernel(const float* __restrict__ x, float* __restrict__ y, int H, int W, int C,
                                                      int OH, int OW, const float* __restrict__ mean,
                                                      const float* __restrict__ stdv, int64_t total) {
@@ -251,15 +237,6 @@ __global__ void __launch_bounds__(256) resize_bwd_kernel(const float* __restrict
     atomicAdd(b + ((int64_t)ly.i1 * W + lx.i0) * C, ly.l1 * lx.l0 * g);
     atomicAdd(b + ((int64_t)ly.i1 * W + lx.i1) * C, ly.l1 * lx.l1 * g);
   }
-}
-// reproducible form of the adjoint: every INPUT pixel gathers from the output pixels whose interpolation footprint contains it, in a
-// fixed order (gx is written, not accumulated).  Candidates: outputs around i / scale, tested with the forward's own lerp_of.
-__device__ __forceinline__ void resize_cands(int i, int in, int out, int& lo, int& hi) {
-  const float inv = in > 1 ? (float)(out - 1) / (float)(in - 1) : 0.f;
-  lo = (int)((float)(i - 1) * inv) - 2;
-  hi = (int)((float)(i + 1) * inv) + 2;
-  if (lo < 0) lo = 0;
-  if (hi > out - 1) hi = out - 1;
 }
 __global__ void __launch_bounds__(256) resize_bwd_gather_kernel(const float* __restrict__ gy, float* __restrict__ gx, int H, int W, int C,
                                                                 int OH, int OW, const float* __restrict__ stdv, int64_t total) {

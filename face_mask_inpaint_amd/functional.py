@@ -1750,6 +1750,91 @@ def psp_pixel_head(y_hat, y, ref=None, mask=None):
     return _PspPixelHead.apply(y_hat, det(y), det(ref), det(mask), hwc)
 
 
+class _GanImageHead(torch.autograd.Function):
+    """loss.py:48-51,84-95,115 from the planar images: 2 launches forward (pass + finish), 1 backward; nothing per pixel is saved.
+    gen is contiguous or channels-last (``hwc``: what ReferenceFill.forward returns); its gradient comes back in the same layout"""
+
+    @staticmethod
+    def forward(ctx, gen, gt, src, ref, mask, mean, std, oh, ow, hwc):
+        n, _, h, w = gen.shape
+        dev = gen.device
+        x_in = torch.empty((3 * n, oh, ow, 3), device=dev, dtype=torch.float32)
+        y_in = torch.empty((3 * n, oh, ow, 3), device=dev, dtype=torch.float32)
+        l1 = torch.empty((), device=dev, dtype=torch.float32)
+        part = torch.empty(n * 64, device=dev, dtype=torch.float64)
+        _L().gan_image_head_fwd_f32(_p(gen), _p(gt), _p(src), _p(ref), _p(mask), _p(mean), _p(std), _p(x_in), _p(y_in), _p(l1), n, h, w, oh, ow, hwc,
+                                    _p(part), part.numel(), _st())
+        ctx.save_for_backward(gen, gt, mask, std)
+        ctx.geom = (oh, ow, hwc)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(y_in)
+        return x_in, y_in, l1
+
+    @staticmethod
+    def backward(ctx, g_x, _g_y, g_l1):
+        gen, gt, mask, std = ctx.saved_tensors
+        if g_x is None and g_l1 is None:
+            return (None,) * 10
+        n, _, h, w = gen.shape
+        oh, ow, hwc = ctx.geom
+        g_x = g_x.to(torch.float32).contiguous() if g_x is not None else None
+        g_l1 = g_l1.to(torch.float32).reshape(()).contiguous() if g_l1 is not None else None
+        d = torch.empty_like(gen)  # gen's own strides
+        _L().gan_image_head_bwd_f32(_p(gen), _p(gt), _p(mask), _p(std), _p(g_x), _p(g_l1), _p(d), n, h, w, oh, ow, hwc, _st())
+        return (d,) + (None,) * 9
+
+
+def gan_image_head(gen, gt, src, ref, mask, mean, std, vgg_size=224):
+    """the image side of GANOptimizer.__call__ (loss.py:48-51,84-95,115) from one pass over the images: gen, gt, src, ref [N, 3, H, W]
+    fp32, mask [N, H, W] fp32, mean / std of three entries -> ``(x_in, y_in, l1)``:
+
+      x_in [3N, OH, OW, 3]  norm(R(gen)), norm(R(gen * (1 - mask))), norm(R(gen * mask)) -- the batch VGGLoss.forward_multi_prepared takes
+      y_in [3N, OH, OW, 3]  norm(R(gt)), norm(R(src)), norm(R(ref * mask)); carries no gradient
+      l1                    mean |gen - gt|, a 0-dim device tensor (the L1 term of generator_loss)
+
+    R is the bilinear resize (align_corners=True) to ``(OH, OW) = (vgg_size, vgg_size)`` when ``W > vgg_size``, else nothing
+    (``(OH, OW) = (H, W)``): loss.py:48.  gen may be contiguous or channels-last in memory (what ReferenceFill.forward returns: read as
+    it is); any other striding is copied.  Differentiable with respect to gen only; no host synchronisation.  Refused while the
+    current stream is being captured (torch.cuda.graph)."""
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        # not supported: the head has never been shown to run inside a captured stream (no test captures it, and the trainer it serves
+        # replays nothing: ReduceLROnPlateau changes lr, which a captured FusedAdam bakes in) -- refuse instead of promising it
+        raise FmiError("gan_image_head: not supported under stream capture (torch.cuda.graph); use GANOptimizer.fused_head = False there")
+    ts = dict(gen=gen, gt=gt, src=src, ref=ref, mask=mask, mean=mean, std=std)
+    for name, t in ts.items():
+        if not torch.is_tensor(t):
+            raise FmiError(f"gan_image_head: {name} is a tensor, got {type(t).__name__}")
+    if gen.dim() != 4 or gen.shape[1] != 3 or gen.numel() == 0:
+        raise FmiError(f"gan_image_head: gen is [N, 3, H, W], got {tuple(gen.shape)}")
+    n, _, h, w = gen.shape
+    for name in ("gt", "src", "ref"):
+        if ts[name].shape != gen.shape:
+            raise FmiError(f"gan_image_head: {name} {tuple(ts[name].shape)} does not match gen {tuple(gen.shape)}")
+    if tuple(mask.shape) != (n, h, w):
+        raise FmiError(f"gan_image_head: mask is [N, H, W] = {(n, h, w)}, got {tuple(mask.shape)}")
+    if mean.numel() != 3 or std.numel() != 3:
+        raise FmiError("gan_image_head: mean and std have three entries")
+    for name, t in ts.items():
+        if t.dtype != torch.float32:
+            raise FmiError(f"gan_image_head: {name} is fp32, got {t.dtype}")
+        if not t.is_cuda:
+            raise FmiError("gan_image_head: face_mask_inpaint_amd ops need device tensors (there is no CPU fallback)")
+        if name != "gen" and t.requires_grad and torch.is_grad_enabled():
+            raise FmiError(f"gan_image_head is differentiable with respect to gen only: detach {name}")
+    vgg_size = int(vgg_size)
+    if vgg_size <= 0:
+        raise FmiError(f"gan_image_head: vgg_size {vgg_size}")
+    oh, ow = (vgg_size, vgg_size) if w > vgg_size else (h, w)
+    det = lambda t: t.detach().contiguous()
+    hwc = 0
+    if not gen.is_contiguous():
+        if gen.permute(0, 2, 3, 1).is_contiguous():
+            hwc = 1
+        else:
+            gen = gen.contiguous()
+    return _GanImageHead.apply(gen, det(gt), det(src), det(ref), det(mask), det(mean).view(3), det(std).view(3), oh, ow, hwc)
+
+
 class _L2NormRows(torch.autograd.Function):
     """y = x / (||x|| + eps) over the last dimension"""
 

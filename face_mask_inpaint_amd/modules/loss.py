@@ -108,12 +108,17 @@ class VGGLoss(torch.nn.Module):
         inputs share ONE VGG pass with gradient (batch k*N) and the targets ONE pass without (the three losses of
         GANOptimizer are 6 VGG passes of batch N in the reference, loss.py:84-95): larger GEMM M fills the GPU at the
         28x28 / 56x56 layers, and the launch count drops 3x."""
-        self._prepare()
-        k = len(triples)
-        n = triples[0][0].shape[0]
         x = torch.cat([self._input(t[0]) for t in triples], 0)
         with torch.no_grad():
             y = torch.cat([self._input(t[1]) for t in triples], 0)
+        return self.forward_multi_prepared(x, y, [t[2] for t in triples])
+
+    def forward_multi_prepared(self, x, y, loss_types):
+        """``forward_multi`` from its block loop onward: x, y [k*N, H, W, 3] NHWC are the resized and normalised operands of the k
+        losses stacked along the batch (what ``forward_multi`` builds, or FF.gan_image_head in one pass); y carries no gradient"""
+        self._prepare()
+        k = len(loss_types)
+        n = x.shape[0] // k
         losses = [0.0] * k
         for i in range(len(self.blocks)):
             x = self._block(i, x)
@@ -122,7 +127,7 @@ class VGGLoss(torch.nn.Module):
             _, h, w, c = x.shape
             dim = c * h * w
             xparts, yparts = x.split(n, 0), y.split(n, 0)  # contiguous batch slices; the backward of split is one cat
-            for j, (_, _, lossType) in enumerate(triples):
+            for j, lossType in enumerate(loss_types):
                 xs, ys = xparts[j], yparts[j]
                 if lossType == "perceptual":
                     losses[j] = losses[j] + FF.l1_loss(xs, ys) / dim
@@ -151,6 +156,9 @@ class GANOptimizer(nn.Module):
         self.lambda_cx = 1
         self.lambda_g = lambda_g
         self.early_d = None  # None: automatic (on when the optimisers are DataParallelOptimizer); True / False force it
+        self.fused_head = False  # True: the VGG operands and the L1 term come from FF.gan_image_head (one pass) instead of composed ops
+
+    LOSS_TYPES = ("perceptual", "style", "contextual")  # the row blocks of FF.gan_image_head's x_in / y_in
 
     @staticmethod
     def _masked(img, mask, invert):
@@ -170,13 +178,18 @@ class GANOptimizer(nn.Module):
         D_fake_loss = self.gan_loss(netD(fake.detach()), False, True)
         return (D_real_loss + D_fake_loss) * 0.5
 
-    def generator_loss(self, netD, real, fake, freeze=True):
+    def generator_loss(self, netD, real, fake, freeze=True, l1=None):
+        """``l1``: the L1 term already computed (FF.gan_image_head) instead of FF.l1_loss here"""
         if freeze:
             base_function._freeze(netD)
         D_fake = netD(fake)
         loss_ad_g = self.gan_loss(D_fake, True, False) * self.lambda_g
-        loss_l1_g = FF.l1_loss(FF.to_nhwc(fake), FF.to_nhwc(real))
+        loss_l1_g = FF.l1_loss(FF.to_nhwc(fake), FF.to_nhwc(real)) if l1 is None else l1
         return loss_ad_g + loss_l1_g
+
+    def _head(self, src_img, gt_img, ref_img, gen_img, src_mask):
+        """(x_in, y_in, l1) of the three VGG losses and the L1 term in one pass over the images (csrc/ganhead.hip)"""
+        return FF.gan_image_head(gen_img, gt_img, src_img, ref_img, src_mask, self.vgg_loss.mean, self.vgg_loss.std)
 
     def __call__(self, discriminator, src_img, gt_img, ref_img, gen_img, src_mask):
         # The reference leaves D trainable here (freeze=False) and then discards the D gradients this backward
@@ -185,15 +198,22 @@ class GANOptimizer(nn.Module):
         d_params = [p for p in discriminator.parameters() if p.requires_grad]
         for p in d_params:
             p.requires_grad_(False)
+        head = self._head(src_img, gt_img, ref_img, gen_img, src_mask) if self.fused_head else None
         try:
-            G_loss = self.generator_loss(discriminator, gt_img, gen_img, freeze=False)
+            if head is None:
+                G_loss = self.generator_loss(discriminator, gt_img, gen_img, freeze=False)
+            else:
+                G_loss = self.generator_loss(discriminator, gt_img, gen_img, freeze=False, l1=head[2])
         finally:
             for p in d_params:
                 p.requires_grad_(True)
-        perc, sty, cx = self.vgg_loss.forward_multi([
-            (gen_img, gt_img, "perceptual"),                                                     # loss.py:84-85
-            (self._masked(gen_img, src_mask, True), src_img, "style"),                           # loss.py:87-89 "Yes inverse"
-            (self._masked(gen_img, src_mask, False), self._masked(ref_img, src_mask, False), "contextual")])  # loss.py:91-95
+        if head is not None:
+            perc, sty, cx = self.vgg_loss.forward_multi_prepared(head[0], head[1], self.LOSS_TYPES)
+        else:
+            perc, sty, cx = self.vgg_loss.forward_multi([
+                (gen_img, gt_img, "perceptual"),                                                     # loss.py:84-85
+                (self._masked(gen_img, src_mask, True), src_img, "style"),                           # loss.py:87-89 "Yes inverse"
+                (self._masked(gen_img, src_mask, False), self._masked(ref_img, src_mask, False), "contextual")])  # loss.py:91-95
         perc_loss, style_loss, cx_loss = perc * self.lambda_perc, sty * self.lambda_style, cx * self.lambda_cx
         G_loss = G_loss + perc_loss + style_loss + cx_loss
         early_d = self.early_d if self.early_d is not None else hasattr(self.optimizer_D, "launch")
@@ -225,6 +245,11 @@ class GANOptimizer(nn.Module):
 
     def calc_loss(self, discriminator, src_img, gt_img, ref_img, gen_img, src_mask):
         D_loss = self.discriminator_loss(discriminator, gt_img, gen_img)
+        if self.fused_head:
+            x_in, y_in, l1 = self._head(src_img, gt_img, ref_img, gen_img, src_mask)
+            G_loss = self.generator_loss(discriminator, gt_img, gen_img, freeze=False, l1=l1)
+            perc, sty, cx = self.vgg_loss.forward_multi_prepared(x_in, y_in, self.LOSS_TYPES)
+            return D_loss, G_loss + perc * self.lambda_perc + sty * self.lambda_style + cx * self.lambda_cx
         G_loss = self.generator_loss(discriminator, gt_img, gen_img, freeze=False)
         perc_loss = self.perceptual_loss(gt_img, gen_img) * self.lambda_perc
         style_loss = self.style_loss(gen_img, src_img, src_mask) * self.lambda_style

@@ -587,6 +587,35 @@ int fmi_psp_pixel_head_bwd_f32(const float* y_hat, const float* y, const float* 
                                const float* g_pair_in, const float* g2, float* d_y_hat, int N, int H, int W, int y_hat_hwc, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The image head of GANOptimizer.__call__ (csrc/ganhead.hip; modules/loss.py:48-51,84-95,115).  gen: fp32 [N][3][H][W], planar
+ * (gen_hwc = 0) or [N][H][W][3] in memory (gen_hwc = 1: the channels-last tensor ReferenceFill.forward returns, read without a
+ * transposition; d_gen has the same layout); anything else is FMI_ERR_BAD_ARG.  gt, src, ref planar [N][3][H][W]; mask [N][H][W] fp32;
+ * mean, stdv: DEVICE arrays of three floats.  m = mask, im = 1 - m (one rounded subtraction); every product one rounded multiply,
+ * taken BEFORE the resize as loss.py:87-95 does.  R: bilinear resize to [OH][OW] with align_corners=True -- the source-index arithmetic
+ * and the expression of fmi_resize_bilinear_f32; (OH, OW) == (H, W) is the no-resize case of loss.py:48 (R is then the identity, bit
+ * for bit).  norm(v) = (v - mean[c]) / stdv[c] (loss.py:50-51).  N <= 65535.  All pointers 4-byte aligned (ws_part 8), else
+ * FMI_ERR_BAD_ARG; 16-byte accesses where the bases are 16-byte aligned and the row length is a multiple of four, one pixel otherwise.
+ * ---------------------------------------------------------------------- */
+/* forward, one pass and a finishing launch:
+ *   x_in [3N][OH][OW][3] NHWC: images 0 .. N-1 = norm(R(gen)), N .. 2N-1 = norm(R(gen im)), 2N .. 3N-1 = norm(R(gen m));
+ *   y_in [3N][OH][OW][3]:      norm(R(gt)), norm(R(src)), norm(R(ref m)) -- the operands VGGLoss.forward hands its first block for the
+ *                              perceptual, style and contextual terms (loss.py:84-95), in that order;
+ *   l1   fp32[1] = mean |gen - gt| over N 3 H W (loss.py:115): the difference in fp32, accumulated in fp64.
+ * ws_part: fp64 scratch of ws_doubles >= N * 64 entries: one partial row per workgroup, added in a fixed order by the finishing launch
+ * -- no atomics, nothing to zero, bit-reproducible whether or not fmi_set_deterministic is on. */
+int fmi_gan_image_head_fwd_f32(const float* gen, const float* gt, const float* src, const float* ref, const float* mask, const float* mean,
+                               const float* stdv, float* x_in, float* y_in, float* l1, int N, int H, int W, int OH, int OW, int gen_hwc,
+                               double* ws_part, int64_t ws_doubles, void* stream);
+/* backward with respect to gen, one launch that recomputes the products (nothing per pixel is saved).  gx [3N][OH][OW][3]: the gradient
+ * of x_in (NULL = zero); g_l1: a DEVICE scalar, the gradient of l1 (NULL = zero; no host read).  With gk = images kN .. kN + N-1 of gx:
+ *   d_gen = g_l1 sign(gen - gt) / (3 N H W) + Rt(g0 / stdv) + im Rt(g1 / stdv) + m Rt(g2 / stdv)
+ * Rt, the adjoint of R, in gather form: every input pixel sums its contributing output pixels in a fixed order (the scheme of
+ * fmi_resize_bilinear_bwd_f32 in reproducible mode), so d_gen is written, not accumulated: no atomics, no zero fill, the same bits in
+ * either mode. */
+int fmi_gan_image_head_bwd_f32(const float* gen, const float* gt, const float* mask, const float* stdv, const float* gx, const float* g_l1,
+                               float* d_gen, int N, int H, int W, int OH, int OW, int gen_hwc, void* stream);
+
+/* ------------------------------------------------------------------------
  * Contextual loss (external_function.py:231-274), x,y NHWC features [N,P,C].
  * ---------------------------------------------------------------------- */
 int fmi_cx_channel_mean_f32(const float* y, float* mu /*[C] zeroed*/, int64_t rows, int C, void* stream);
