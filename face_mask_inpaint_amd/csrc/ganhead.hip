@@ -7,73 +7,17 @@
 // gather form: every input pixel sums its contributing output pixels in a fixed order, so d_gen is written, not accumulated -- no
 // atomics, no zero fill, bit-reproducible in either mode.  Bandwidth kernels: a thread takes four neighbouring output pixels of a row
 // (three 16-byte stores per stream) on the forward, four neighbouring input pixels on the backward, or one pixel when the row length is
-// not a multiple of four or a base is not 16-byte aligned.  |gen - gt| is accumulated in fp64 and reduced wave shuffle -> LDS -> one
-// partial row per workgroup; a finishing launch adds the rows in a fixed order (the scheme of psploss.hip / segloss.hip).
+// not a multiple of four or a base is not 16-byte aligned.  |gen - gt| is accumulated in fp64, reduced to one partial row per workgroup and
+// finished by a second launch in a fixed order (the scheme, its helpers and the RGB pixel I/O: head.h).
 // Every product is one rounded fp32 multiply and 1 - m one rounded subtraction.  The file is compiled without FMA contraction (the pragma
-// below, ahead of common.h): lerp_of's l1 = r - i0 is then taken from the ROUNDED r = scale * o, the value its index i0 = (int)r comes
-// from, in the forward and in the backward alike -- fused, scale * o - i0 moves a weight by up to half an ulp of r (4e-6 at 224), and
+// below, ahead of the includes so that it covers them): lerp_of's l1 = r - i0 is then taken from the ROUNDED r = scale * o, the value its
+// index i0 = (int)r comes from, in the forward and in the backward alike -- fused, scale * o - i0 moves a weight by up to half an ulp of r (4e-6 at 224), and
 // nothing would guarantee the two directions the same choice.
 #pragma clang fp contract(off)
 #include "common.h"
+#include "head.h"
 
 namespace {
-
-constexpr int GAN_GX_MAX = 64;  // workgroups (= partial rows) per sample of the forward
-
-// RGB of pixel p of sample n: from three planes, or from an interleaved [N][H][W][3] image (hwc)
-__device__ __forceinline__ void load_rgb(const float* __restrict__ x, bool hwc, int64_t n, int64_t hw, int64_t p, float* v) {
-  if (hwc) {
-    const float* q = x + (n * hw + p) * 3;
-    v[0] = q[0], v[1] = q[1], v[2] = q[2];
-  } else {
-    const float* q = x + n * 3 * hw + p;
-    v[0] = q[0], v[1] = q[hw], v[2] = q[2 * hw];
-  }
-}
-
-// PX pixels x RGB into a[c][j]: four pixels are three 16-byte loads in either layout
-template <int PX>
-__device__ __forceinline__ void load_run(const float* __restrict__ x, bool hwc, int64_t n, int64_t hw, int64_t p, float (*a)[PX]) {
-  if (PX == 4) {
-    if (hwc) {
-      const float4* q = reinterpret_cast<const float4*>(x + (n * hw + p) * 3);
-      float t[12];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const float4 u = q[k];
-        t[4 * k] = u.x, t[4 * k + 1] = u.y, t[4 * k + 2] = u.z, t[4 * k + 3] = u.w;
-      }
-#pragma unroll
-      for (int j = 0; j < PX; ++j)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) a[c][j] = t[j * 3 + c];
-    } else {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float4 u = *reinterpret_cast<const float4*>(x + (n * 3 + c) * hw + p);
-        a[c][0] = u.x, a[c][1] = u.y, a[c][2] = u.z, a[c][3] = u.w;
-      }
-    }
-  } else {
-    float t[3];
-    load_rgb(x, hwc, n, hw, p, t);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) a[c][0] = t[c];
-  }
-}
-
-// 3 PX interleaved values to element e of an NHWC image
-template <int PX>
-__device__ __forceinline__ void store_hwc(float* __restrict__ x, int64_t e, const float* v) {
-  if (PX == 4) {
-    float4* q = reinterpret_cast<float4*>(x + e);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) q[k] = make_float4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) x[e + k] = v[k];
-  }
-}
 
 // the interpolation of resize_kernel (pool.hip): two rounded operations per lerp level
 __device__ __forceinline__ float bilerp(const Lerp& ly, const Lerp& lx, float v00, float v01, float v10, float v11) {
@@ -87,8 +31,8 @@ __device__ __forceinline__ double l1_share(const float* __restrict__ gen, const 
   const int64_t per = hw / PX;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per; i += (int64_t)gridDim.x * 256) {
     float a[3][PX], b[3][PX];
-    load_run<PX>(gen, hwc, n, hw, i * PX, a);
-    load_run<PX>(gt, false, n, hw, i * PX, b);
+    load_rgb_run<PX>(gen, hwc, n, hw, i * PX, a);
+    load_rgb_run<PX>(gt, false, n, hw, i * PX, b);
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
@@ -151,22 +95,9 @@ __global__ void __launch_bounds__(256) gan_head_fwd_kernel(const float* __restri
     }
   }
   if (part) {
-    __shared__ double red[4];
     double acc = l1_vec ? l1_share<4>(gen, gt, hwc, n, hw) : l1_share<1>(gen, gt, hwc, n, hw);
-    acc = wave_sum_d(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[n * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    block_rows_out<1>(&acc, part, n * gridDim.x + blockIdx.x);
   }
-}
-
-// one workgroup: thread t adds rows t, t + 256, ... in order, then the block in a fixed order
-__global__ void __launch_bounds__(256) gan_head_finish_kernel(const double* __restrict__ part, int64_t rows, double count, float* __restrict__ l1) {
-  __shared__ double red[4];
-  double s = 0.0;
-  for (int64_t r = threadIdx.x; r < rows; r += 256) s += part[r];
-  s = block_sum_256_d(s, red);
-  if (threadIdx.x == 0) l1[0] = (float)(s / count);
 }
 
 // does output index o of an axis read input index i?  (its weights: l0 if i0 == i, l1 if i1 == i -- both at the clamped last index)
@@ -201,14 +132,9 @@ __global__ void __launch_bounds__(256) gan_head_bwd_kernel(const float* __restri
     const int iy = (int)(i / runs), ix0 = (int)(i % runs) * PX;
     const int64_t p = (int64_t)iy * W + ix0;
     float a[3][PX], b[3][PX], m[PX], d[3][PX];
-    load_run<PX>(gen, hwc, n, hw, p, a);
-    load_run<PX>(gt, false, n, hw, p, b);
-    if (PX == 4) {
-      const float4 u = *reinterpret_cast<const float4*>(mask + n * hw + p);
-      m[0] = u.x, m[1] = u.y, m[2] = u.z, m[3] = u.w;
-    } else {
-      m[0] = mask[n * hw + p];
-    }
+    load_rgb_run<PX>(gen, hwc, n, hw, p, a);
+    load_rgb_run<PX>(gt, false, n, hw, p, b);
+    load_px<PX>(mask, n * hw + p, m);
     int ylo = 0, yhi = -1;
     if (gx) contributors(iy, H, OH, ylo, yhi);  // the rows: once for the run
 #pragma unroll
@@ -240,33 +166,12 @@ __global__ void __launch_bounds__(256) gan_head_bwd_kernel(const float* __restri
         d[c][j] = ((sgn * t_l1 + s[0][c]) + im * s[1][c]) + m[j] * s[2][c];
       }
     }
-    if (hwc) {  // the gradient in gen's own layout
-      float o[3 * PX];
-#pragma unroll
-      for (int j = 0; j < PX; ++j)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o[j * 3 + c] = d[c][j];
-      store_hwc<PX>(d_gen, (n * hw + p) * 3, o);
-    } else {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        if (PX == 4)
-          *reinterpret_cast<float4*>(d_gen + (n * 3 + c) * hw + p) = make_float4(d[c][0], d[c][1], d[c][2], d[c][3]);
-        else
-          d_gen[(n * 3 + c) * hw + p] = d[c][0];
-      }
-    }
+    store_rgb_run<PX>(d_gen, hwc, n, hw, p, d);  // the gradient in gen's own layout
   }
 }
 
-inline bool gan_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool gan_al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-inline int gan_gx(int64_t per, int cap) {
-  int64_t g = ceil_div64(per, 256);
-  return (int)(g < 1 ? 1 : g > cap ? cap : g);
-}
 // workgroups per sample of the forward: enough for the larger of its two loops
-inline int gan_fwd_gx(int64_t per_out, int64_t per_in) { return gan_gx(per_out > per_in ? per_out : per_in, GAN_GX_MAX); }
+inline int gan_fwd_gx(int64_t per_out, int64_t per_in) { return rows_for(per_out > per_in ? per_out : per_in, ROWS_PER_PLANE); }
 
 }  // namespace
 
@@ -277,11 +182,11 @@ extern "C" int fmi_gan_image_head_fwd_f32(const float* gen, const float* gt, con
   if ((gen_hwc != 0 && gen_hwc != 1) || N <= 0 || N > 65535 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return FMI_ERR_BAD_ARG;
   const void* all[] = {gen, gt, src, ref, mask, mean, stdv, x_in, y_in, l1};
   for (const void* q : all)
-    if (!gan_al4(q)) return FMI_ERR_BAD_ARG;
+    if (!al4(q)) return FMI_ERR_BAD_ARG;
   if (reinterpret_cast<uintptr_t>(ws_part) & 7) return FMI_ERR_BAD_ARG;
   const int64_t hw = (int64_t)H * W, ohw = (int64_t)OH * OW;
-  const bool vec_out = (OW & 3) == 0 && gan_al16(x_in) && gan_al16(y_in);
-  const bool vec_in = (hw & 3) == 0 && gan_al16(gen) && gan_al16(gt);
+  const bool vec_out = (OW & 3) == 0 && al16(x_in) && al16(y_in);
+  const bool vec_in = (hw & 3) == 0 && al16(gen) && al16(gt);
   const int64_t per = vec_out ? ohw >> 2 : ohw;
   const int gx = gan_fwd_gx(per, vec_in ? hw >> 2 : hw);
   if (ws_doubles < (int64_t)N * gx) return FMI_ERR_BAD_ARG;  // one partial row per workgroup
@@ -292,7 +197,8 @@ extern "C" int fmi_gan_image_head_fwd_f32(const float* gen, const float* gt, con
   else
     hipLaunchKernelGGL(gan_head_fwd_kernel<1>, grid, block, 0, (hipStream_t)stream, gen, gt, src, ref, mask, mean, stdv, x_in, y_in, ws_part, N, H, W, OH, OW,
                        per, gen_hwc != 0, vec_in);
-  hipLaunchKernelGGL(gan_head_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ws_part, (int64_t)N * gx, 3.0 * (double)N * (double)hw, l1);
+  hipLaunchKernelGGL(rows_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ws_part, (int64_t)N * gx, 1, 3.0 * (double)N * (double)hw,
+                     (double*)nullptr, l1);
   return fmi_launch_status();
 }
 
@@ -302,11 +208,11 @@ extern "C" int fmi_gan_image_head_bwd_f32(const float* gen, const float* gt, con
   if ((gen_hwc != 0 && gen_hwc != 1) || N <= 0 || N > 65535 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return FMI_ERR_BAD_ARG;
   const void* all[] = {gen, gt, mask, stdv, gx, g_l1, d_gen};
   for (const void* q : all)
-    if (!gan_al4(q)) return FMI_ERR_BAD_ARG;
+    if (!al4(q)) return FMI_ERR_BAD_ARG;
   const int64_t hw = (int64_t)H * W;
-  const bool vec = (W & 3) == 0 && gan_al16(gen) && gan_al16(gt) && gan_al16(mask) && gan_al16(d_gen);
+  const bool vec = (W & 3) == 0 && al16(gen) && al16(gt) && al16(mask) && al16(d_gen);
   const int64_t per = vec ? hw >> 2 : hw;
-  const dim3 grid(gan_gx(per, 1024), N), block(256);
+  const dim3 grid(rows_for(per, 1024), N), block(256);
   const double count = 3.0 * (double)N * (double)hw;
   if (vec)
     hipLaunchKernelGGL(gan_head_bwd_kernel<4>, grid, block, 0, (hipStream_t)stream, gen, gt, mask, stdv, gx, g_l1, d_gen, N, H, W, OH, OW, per, count, gen_hwc != 0);

@@ -1,6 +1,7 @@
 // Loss reductions: L1 / MSE / LSGAN sums, the Gram-matrix style-loss gradient, and the contextual loss
 // (external_function.py:231-274) forward/backward tails that sit around the cosine-similarity GEMM.
 #include "common.h"
+#include "head.h"
 
 // ---- sum reductions -----------------------------------------------------------------------------
 template <int KIND>
@@ -430,7 +431,7 @@ extern "C" int fmi_lpips_layer_bwd_f32(const float* fx, const float* fy, const f
 // ---- SSIM / MS-SSIM in the form of the trainers' metric package (pytorch_msssim, absent offline: train_reference_fill.py:207-209,
 // train_psp.py:176-178, PICNet_inference.py:130-131): Gaussian window WITHOUT padding ("valid" filtering), per plane the means of the
 // ssim map and of its contrast-structure factor cs; between the scales of MS-SSIM a 2 x 2 mean pool with zero padding of odd sizes.
-// Every workgroup writes its partial sums (fp64) and a second launch adds them in a fixed order: results are reproducible.
+// Every workgroup writes its partial sums (fp64) and a second launch adds them in a fixed order (head.h): results are reproducible.
 __global__ void __launch_bounds__(256) ssim_valid_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ g,
                                                          int ws, int H, int W, float C1, float C2, double* __restrict__ part) {
   __shared__ double red[4];
@@ -471,25 +472,16 @@ __global__ void __launch_bounds__(256) ssim_valid_kernel(const float* __restrict
     part[((int64_t)plane * gridDim.x + blockIdx.x) * 2 + 1] = acc_c;
   }
 }
-__global__ void ssim_valid_sum_kernel(const double* __restrict__ part, int gx, int planes, double inv_count, float* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= planes * 2) return;
-  const int plane = i >> 1, which = i & 1;
-  double s = 0.0;
-  for (int j = 0; j < gx; ++j) s += part[((int64_t)plane * gx + j) * 2 + which];
-  out[i] = (float)(s * inv_count);
-}
 extern "C" int fmi_ssim_valid_f32(const float* img1, const float* img2, const float* window1d, int ws, int planes, int H, int W, float C1,
                                   float C2, float* out_plane2, double* ws_part, int64_t ws_doubles, void* stream) {
   if (!img1 || !img2 || !window1d || !out_plane2 || !ws_part || ws <= 0 || ws > 63 || planes <= 0 || planes > 65535 || H < ws || W < ws)
     return FMI_ERR_BAD_ARG;
   const int64_t px = (int64_t)(H - ws + 1) * (W - ws + 1);
-  int gx = (int)((px + 255) / 256);
-  if (gx > 64) gx = 64;
+  const int gx = rows_for(px, ROWS_PER_PLANE);
   if (ws_doubles < (int64_t)planes * gx * 2) return FMI_ERR_BAD_ARG;
   hipLaunchKernelGGL(ssim_valid_kernel, dim3(gx, planes), dim3(256), 0, (hipStream_t)stream, img1, img2, window1d, ws, H, W, C1, C2, ws_part);
-  hipLaunchKernelGGL(ssim_valid_sum_kernel, dim3((planes * 2 + 255) / 256), dim3(256), 0, (hipStream_t)stream, ws_part, gx, planes, 1.0 / (double)px,
-                     out_plane2);
+  hipLaunchKernelGGL(plane_rows_finish_kernel<float>, dim3((planes * 2 + 255) / 256), dim3(256), 0, (hipStream_t)stream, ws_part, gx, planes, 2,
+                     1.0 / (double)px, out_plane2);
   return fmi_launch_status();
 }
 // 2 x 2 mean pool, stride 2, zero padding ph / pw (0 or 1) counted in the divisor (avg_pool2d's count_include_pad default)

@@ -4,76 +4,13 @@
 // (cat(y_hat (1 - m), y (1 - m)) and cat(y_hat m, ref m), [2N][H][W][3]) and the two F.mse_loss values; and its backward in one pass
 // that recomputes the products (nothing per pixel is saved).  Bandwidth kernels: a thread takes four neighbouring pixels of a sample
 // (one 16-byte load per plane, three 16-byte stores per interleaved output) or, when H * W % 4 != 0 or a base is not 16-byte aligned,
-// one pixel.  The sums of squares are accumulated in fp64 and reduced wave shuffle -> LDS -> one partial row per workgroup; a finishing
-// launch adds the rows in a fixed order (the scheme of segloss.hip): no atomics, nothing to zero, bit-reproducible in either mode.
+// one pixel.  The sums of squares are accumulated in fp64, reduced to one partial row per workgroup and finished by a second launch
+// in a fixed order (the scheme, its helpers and the RGB pixel I/O: head.h): no atomics, nothing to zero, bit-reproducible in either mode.
 // Every product is one rounded fp32 multiply and 1 - m one rounded subtraction (never contracted), so the batches equal torch's bit for bit.
 #include "common.h"
+#include "head.h"
 
 namespace {
-
-constexpr int HEAD_GX_MAX = 64;  // workgroups (= partial rows) per sample of the forward
-
-// v[k] (k < 2) of every thread -> part[row][k]: wave shuffle, LDS, the four waves added in a fixed order
-__device__ __forceinline__ void head_rows_out(double* v, double* __restrict__ part, int64_t row) {
-  __shared__ double red[4][2];
-  v[0] = wave_sum_d(v[0]), v[1] = wave_sum_d(v[1]);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = v[0], red[threadIdx.x >> 6][1] = v[1];
-  __syncthreads();
-  if (threadIdx.x < 2) part[row * 2 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-}
-
-// PX pixels of one plane starting at element e
-template <int PX>
-__device__ __forceinline__ void load_px(const float* __restrict__ x, int64_t e, float* v) {
-  if (PX == 4) {
-    const float4 t = *reinterpret_cast<const float4*>(x + e);
-    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-  } else {
-    v[0] = x[e];
-  }
-}
-// 3 PX interleaved values to / from element e of an NHWC image
-template <int PX>
-__device__ __forceinline__ void store_hwc(float* __restrict__ x, int64_t e, const float* v) {
-  if (PX == 4) {
-    float4* q = reinterpret_cast<float4*>(x + e);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) q[k] = make_float4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) x[e + k] = v[k];
-  }
-}
-template <int PX>
-__device__ __forceinline__ void load_hwc(const float* __restrict__ x, int64_t e, float* v) {
-  if (PX == 4) {
-    const float4* q = reinterpret_cast<const float4*>(x + e);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float4 t = q[k];
-      v[4 * k] = t.x, v[4 * k + 1] = t.y, v[4 * k + 2] = t.z, v[4 * k + 3] = t.w;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) v[k] = x[e + k];
-  }
-}
-
-// PX pixels x RGB of y_hat into a[c][j]: from three planes, or from an interleaved [N][H][W][3] image (hwc)
-template <int PX>
-__device__ __forceinline__ void load_yh(const float* __restrict__ yh, bool hwc, int64_t n, int64_t hw, int64_t p, float (*a)[PX]) {
-  if (hwc) {
-    float t[3 * PX];
-    load_hwc<PX>(yh, (n * hw + p) * 3, t);
-#pragma unroll
-    for (int j = 0; j < PX; ++j)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) a[c][j] = t[j * 3 + c];
-  } else {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) load_px<PX>(yh, (n * 3 + c) * hw + p, a[c]);
-  }
-}
 
 // grid (gx, N); per = work items of a sample (H W / 4 groups of four pixels, or H W pixels); part (may be NULL: no sums wanted)
 template <int PX>
@@ -93,7 +30,7 @@ __global__ void __launch_bounds__(256) psp_head_fwd_kernel(const float* __restri
 #pragma unroll
       for (int j = 0; j < PX; ++j) im[j] = __fsub_rn(1.f, m[j]);
     }
-    load_yh<PX>(yh, yh_hwc, n, hw, p, a);
+    load_rgb_run<PX>(yh, yh_hwc, n, hw, p, a);
 #pragma unroll
     for (int c = 0; c < 3; ++c) load_px<PX>(y, (n * 3 + c) * hw + p, b[c]);
     float oa[3 * PX], ob[3 * PX];
@@ -128,22 +65,7 @@ __global__ void __launch_bounds__(256) psp_head_fwd_kernel(const float* __restri
       }
     }
   }
-  if (part) head_rows_out(acc, part, n * gridDim.x + blockIdx.x);
-}
-
-// one workgroup: thread t adds rows t, t + 256, ... in order, then the block in a fixed order
-__global__ void __launch_bounds__(256) psp_head_finish_kernel(const double* __restrict__ part, int64_t rows, double count, double* __restrict__ sums,
-                                                              float* __restrict__ out2) {
-  __shared__ double red[4];
-  for (int k = 0; k < 2; ++k) {
-    double s = 0.0;
-    for (int64_t r = threadIdx.x; r < rows; r += 256) s += part[r * 2 + k];
-    s = block_sum_256_d(s, red);
-    if (threadIdx.x == 0) {
-      if (sums) sums[k] = s;
-      if (out2) out2[k] = (float)(s / count);
-    }
-  }
+  if (part) block_rows_out<2>(acc, part, n * gridDim.x + blockIdx.x);
 }
 
 // grid (gx, N); s[k] = g2[k] * 2 / count.  The differences are taken in their factored form im (y_hat - y) and m (y_hat - ref) -- the same
@@ -169,7 +91,7 @@ __global__ void __launch_bounds__(256) psp_head_bwd_kernel(const float* __restri
 #pragma unroll
       for (int j = 0; j < PX; ++j) im[j] = __fsub_rn(1.f, m[j]);
     }
-    load_yh<PX>(yh, yh_hwc, n, hw, p, a);
+    load_rgb_run<PX>(yh, yh_hwc, n, hw, p, a);
 #pragma unroll
     for (int c = 0; c < 3; ++c) load_px<PX>(y, (n * 3 + c) * hw + p, b[c]);
     if (g_pair_out) load_hwc<PX>(g_pair_out, (n * hw + p) * 3, go);
@@ -192,29 +114,8 @@ __global__ void __launch_bounds__(256) psp_head_bwd_kernel(const float* __restri
           d[c][j] += m[j] * (gi[j * 3 + c] + s1 * diff);
         }
     }
-    if (yh_hwc) {  // the gradient in y_hat's own layout
-#pragma unroll
-      for (int j = 0; j < PX; ++j)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) go[j * 3 + c] = d[c][j];
-      store_hwc<PX>(d_yh, (n * hw + p) * 3, go);
-    } else {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        if (PX == 4)
-          *reinterpret_cast<float4*>(d_yh + (n * 3 + c) * hw + p) = make_float4(d[c][0], d[c][1], d[c][2], d[c][3]);
-        else
-          d_yh[(n * 3 + c) * hw + p] = d[c][0];
-      }
-    }
+    store_rgb_run<PX>(d_yh, yh_hwc, n, hw, p, d);  // the gradient in y_hat's own layout
   }
-}
-
-inline bool head_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool head_al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-inline int head_gx(int64_t per, int cap) {
-  int64_t g = ceil_div64(per, 256);
-  return (int)(g < 1 ? 1 : g > cap ? cap : g);
 }
 
 }  // namespace
@@ -226,13 +127,13 @@ extern "C" int fmi_psp_pixel_head_fwd_f32(const float* y_hat, const float* y, co
   if (pair_in && (!ref || !mask)) return FMI_ERR_BAD_ARG;  // the inner pair needs both
   const void* all[] = {y_hat, y, ref, mask, pair_out, pair_in, out2};
   for (const void* q : all)
-    if (!head_al4(q)) return FMI_ERR_BAD_ARG;
+    if (!al4(q)) return FMI_ERR_BAD_ARG;
   if ((reinterpret_cast<uintptr_t>(sums) & 7) || (reinterpret_cast<uintptr_t>(ws_part) & 7)) return FMI_ERR_BAD_ARG;
   const int64_t hw = (int64_t)H * W;
   bool vec = (hw & 3) == 0;
-  for (const void* q : all) vec = vec && head_al16(q);
+  for (const void* q : all) vec = vec && al16(q);
   const int64_t per = vec ? hw >> 2 : hw;
-  const int gx = head_gx(per, HEAD_GX_MAX);
+  const int gx = rows_for(per, ROWS_PER_PLANE);
   const bool want_sums = sums || out2;
   if (want_sums && (!ws_part || ws_doubles < (int64_t)N * gx * 2)) return FMI_ERR_BAD_ARG;
   double* part = want_sums ? ws_part : nullptr;
@@ -242,7 +143,7 @@ extern "C" int fmi_psp_pixel_head_fwd_f32(const float* y_hat, const float* y, co
   else
     hipLaunchKernelGGL(psp_head_fwd_kernel<1>, grid, block, 0, (hipStream_t)stream, y_hat, y, ref, mask, pair_out, pair_in, part, N, hw, per, y_hat_hwc != 0);
   if (want_sums)
-    hipLaunchKernelGGL(psp_head_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, part, (int64_t)N * gx, 3.0 * (double)N * (double)hw, sums, out2);
+    hipLaunchKernelGGL(rows_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, part, (int64_t)N * gx, 2, 3.0 * (double)N * (double)hw, sums, out2);
   return fmi_launch_status();
 }
 
@@ -252,13 +153,13 @@ extern "C" int fmi_psp_pixel_head_bwd_f32(const float* y_hat, const float* y, co
   if (g_pair_in && (!ref || !mask)) return FMI_ERR_BAD_ARG;
   const void* all[] = {y_hat, y, ref, mask, g_pair_out, g_pair_in, g2, d_y_hat};
   for (const void* q : all)
-    if (!head_al4(q)) return FMI_ERR_BAD_ARG;
+    if (!al4(q)) return FMI_ERR_BAD_ARG;
   const int64_t hw = (int64_t)H * W;
   bool vec = (hw & 3) == 0;
   for (const void* q : all)
-    if (q != g2) vec = vec && head_al16(q);
+    if (q != g2) vec = vec && al16(q);
   const int64_t per = vec ? hw >> 2 : hw;
-  const dim3 grid(head_gx(per, 1024), N), block(256);
+  const dim3 grid(rows_for(per, 1024), N), block(256);
   const double count = 3.0 * (double)N * (double)hw;
   if (vec)
     hipLaunchKernelGGL(psp_head_bwd_kernel<4>, grid, block, 0, (hipStream_t)stream, y_hat, y, ref, mask, g_pair_out, g_pair_in, g2, d_y_hat, count, hw, per, y_hat_hwc != 0);

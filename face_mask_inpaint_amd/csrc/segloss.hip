@@ -1,16 +1,15 @@
 // The mask-detector trainer's loss and validation metric on NHWC logits [P][C] (train_mask_detector.py:24-58,127-134 with
 // modules/loss.py:148-186): CrossEntropyLoss + dice_loss(softmax, one_hot) forward and backward, the argmax Dice score of `evaluate`,
 // and per-plane (sum a b, sum a, sum b) for the general dice_* helpers.  Bandwidth kernels: 16-byte loads, four pixels per thread and
-// iteration, fp64 accumulation; wave shuffle -> LDS -> one partial row per workgroup, and a finishing launch that adds the rows in a
-// fixed order (the scheme of norm.hip and ssim_valid_kernel): no atomics, nothing to zero, bit-reproducible in either mode.
+// iteration, fp64 accumulation, reduced to one partial row per workgroup and finished by a second launch in a fixed order (the scheme
+// and its helpers: head.h): no atomics, nothing to zero, bit-reproducible in either mode.
 // The target is the dataset's int64 map (kind 0) or an fp32 map (kind 1); `> 0` (train_mask_detector.py:127) is applied here, so the
 // class of a pixel is 0 or 1 whatever C is, as one_hot((mask > 0).long(), C) has it.
 #include <math.h>
 #include "common.h"
+#include "head.h"
 
 namespace {
-
-constexpr int SEG_ROWS_MAX = 1024;  // workgroups (= partial rows) of the sum kernels
 
 __device__ __forceinline__ int cls_at(const void* t, int kind, int64_t p) {
   return kind == 0 ? (reinterpret_cast<const int64_t*>(t)[p] > 0 ? 1 : 0) : (reinterpret_cast<const float*>(t)[p] > 0.f ? 1 : 0);
@@ -61,25 +60,6 @@ __device__ __forceinline__ int argmax_px(const float* x) {
   return bi;
 }
 
-// v[0 .. NV) of every thread -> part[row][0 .. NV): wave shuffle, LDS, the four waves added in a fixed order
-template <int NV>
-__device__ __forceinline__ void block_rows_out(double* v, double* __restrict__ part, int64_t row) {
-  __shared__ double red[4][NV];
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = wave_sum_d(v[k]);
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) red[threadIdx.x >> 6][k] = v[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < NV) part[row * NV + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-}
-// sum of column k of part[rows][nv]: thread t adds rows t, t + 256, ... in order, then the block in a fixed order
-__device__ __forceinline__ double column_sum(const double* __restrict__ part, int64_t rows, int nv, int k, double* lds4) {
-  double s = 0.0;
-  for (int64_t r = threadIdx.x; r < rows; r += 256) s += part[r * nv + k];
-  return block_sum_256_d(s, lds4);
-}
 // dice_coeff (modules/loss.py:156-162) from the three sums; the `sets_sum == 0 -> 2 * inter` branch without a host read
 __device__ __forceinline__ double dice_of(double inter, double sets_sum, double eps) {
   if (sets_sum == 0.0) sets_sum = 2.0 * inter;
@@ -289,20 +269,6 @@ __global__ void __launch_bounds__(256) plane_sums_kernel(const float* __restrict
   }
   block_rows_out<3>(acc, part, (int64_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
-__global__ void plane_sums_finish_kernel(const double* __restrict__ part, int gx, int planes, double* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= planes * 3) return;
-  const int plane = i / 3, k = i - plane * 3;
-  double s = 0.0;
-  for (int r = 0; r < gx; ++r) s += part[((int64_t)plane * gx + r) * 3 + k];
-  out[i] = s;
-}
-
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline int rows_for(int64_t groups, int cap) {
-  int64_t g = ceil_div64(groups, 256);
-  return (int)(g < 1 ? 1 : g > cap ? cap : g);
-}
 
 }  // namespace
 
@@ -321,7 +287,7 @@ extern "C" int fmi_seg_ce_dice_fwd_f32(const float* logits, const void* target, 
                                        double* sums, double* ws_part, int64_t ws_doubles, void* stream) {
   if (!logits || !target || !out3 || !sums || !ws_part || P <= 0 || C < 2 || C > 8 || (target_kind != 0 && target_kind != 1)) return FMI_ERR_BAD_ARG;
   if (!al16(logits) || !al16(target)) return FMI_ERR_BAD_ARG;
-  const int rows = rows_for(P >> 2, SEG_ROWS_MAX);
+  const int rows = rows_for(P >> 2, ROWS_SEG_LOSS);
   if (ws_doubles < (int64_t)rows * (1 + 3 * C)) return FMI_ERR_BAD_ARG;
 #define CALL(CC) hipLaunchKernelGGL(seg_loss_fwd_kernel<CC>, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, target, target_kind, P, ws_part)
   SEG_DISPATCH_C(CALL)
@@ -348,7 +314,7 @@ extern "C" int fmi_seg_dice_score_f32(const float* logits, const void* target, i
     return FMI_ERR_BAD_ARG;
   if (!al16(logits) || !al16(target)) return FMI_ERR_BAD_ARG;
   const bool vec = (HW & 3) == 0;
-  const int gx = rows_for(vec ? HW >> 2 : HW, 64);
+  const int gx = rows_for(vec ? HW >> 2 : HW, ROWS_PER_PLANE);
   if (ws_doubles < (int64_t)N * gx * 3 * (C - 1)) return FMI_ERR_BAD_ARG;
   const dim3 grid(gx, N), block(256);
 #define CALL(CC)                                                                                                                        \
@@ -366,12 +332,12 @@ extern "C" int fmi_plane_sums_f32(const float* a, const float* b, int planes, in
                                   void* stream) {
   if (!a || !b || !out3 || !ws_part || planes <= 0 || planes > 65535 || n <= 0) return FMI_ERR_BAD_ARG;
   const bool vec = (n & 3) == 0 && al16(a) && al16(b);
-  const int gx = rows_for(vec ? n >> 2 : n, planes == 1 ? 256 : 64);
+  const int gx = rows_for(vec ? n >> 2 : n, planes == 1 ? ROWS_ONE_PLANE : ROWS_PER_PLANE);
   if (ws_doubles < (int64_t)planes * gx * 3) return FMI_ERR_BAD_ARG;
   if (vec)
     hipLaunchKernelGGL(plane_sums_kernel<true>, dim3(gx, planes), dim3(256), 0, (hipStream_t)stream, a, b, n, ws_part);
   else
     hipLaunchKernelGGL(plane_sums_kernel<false>, dim3(gx, planes), dim3(256), 0, (hipStream_t)stream, a, b, n, ws_part);
-  hipLaunchKernelGGL(plane_sums_finish_kernel, dim3((planes * 3 + 255) / 256), dim3(256), 0, (hipStream_t)stream, ws_part, gx, planes, out3);
+  hipLaunchKernelGGL(plane_rows_finish_kernel<double>, dim3((planes * 3 + 255) / 256), dim3(256), 0, (hipStream_t)stream, ws_part, gx, planes, 3, 1.0, out3);
   return fmi_launch_status();
 }

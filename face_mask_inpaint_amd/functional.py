@@ -1590,6 +1590,18 @@ def mse_to_const(a, c0):
     return _ReduceLoss.apply(2, a.contiguous(), None, float(c0), 1.0 / a.numel())
 
 
+# Caps of the partial rows (= workgroups) a sum kernel writes: csrc/head.h's ROWS_PER_PLANE, ROWS_ONE_PLANE and ROWS_SEG_LOSS.  The entries
+# refuse a workspace smaller than rows x values (FMI_ERR_BAD_ARG): change both sides together.
+_ROWS_PER_PLANE = 64   # per sample or plane: seg_dice_score, plane_sums (planes > 1), psp / gan head forward, ssim_valid
+_ROWS_ONE_PLANE = 256  # plane_sums over a single plane
+_ROWS_SEG_LOSS = 1024  # seg_ce_dice forward, over the whole batch
+
+
+def _rows_ws(device, rows, nv):
+    """the fp64 workspace of a partial-row reduction (csrc/head.h): ``rows`` rows of ``nv`` sums; the kernels write before they read it"""
+    return torch.empty(rows * nv, device=device, dtype=torch.float64)
+
+
 def _seg_args(logits_nhwc, target, what):
     """checked (logits, target, kind, N, HW, C) of the segmentation loss / metric: logits NHWC fp32 [N, H, W, C], target [N, H, W] int64
     (the dataset's map; kind 0) or fp32 (kind 1); both 16-byte aligned for the kernels' vector loads"""
@@ -1621,7 +1633,7 @@ class _SegCeDice(torch.autograd.Function):
         p, c = x.numel() // x.shape[-1], x.shape[-1]
         out3 = torch.empty(3, device=x.device, dtype=torch.float32)
         sums = torch.empty(1 + 3 * c, device=x.device, dtype=torch.float64)
-        part = torch.empty(1024 * (1 + 3 * c), device=x.device, dtype=torch.float64)
+        part = _rows_ws(x.device, _ROWS_SEG_LOSS, 1 + 3 * c)
         _L().seg_ce_dice_fwd_f32(_p(x), _p(t), kind, p, c, eps, _p(out3), _p(sums), _p(part), part.numel(), _st())
         ctx.save_for_backward(x, t, sums)
         ctx.cfg = (kind, eps)
@@ -1652,7 +1664,7 @@ def seg_dice_score(logits_nhwc, target, eps=1e-6):
     multiclass_dice_coeff(one_hot(logits.argmax(C))[:, 1:], one_hot(target > 0)[:, 1:], reduce_batch_first=False).  No gradient."""
     x, t, kind, n, hw, c = _seg_args(logits_nhwc.detach(), target, "seg_dice_score")
     out = torch.empty((), device=x.device, dtype=torch.float32)
-    part = torch.empty(n * 64 * 3 * (c - 1), device=x.device, dtype=torch.float64)
+    part = _rows_ws(x.device, n * _ROWS_PER_PLANE, 3 * (c - 1))
     _L().seg_dice_score_f32(_p(x), _p(t), kind, n, hw, c, float(eps), _p(out), _p(part), part.numel(), _st())
     return out
 
@@ -1665,9 +1677,32 @@ def plane_sums(a, b, planes):
     if a.shape != b.shape or a.numel() == 0 or a.numel() % planes:
         raise FmiError(f"plane_sums: {tuple(a.shape)} / {tuple(b.shape)} do not split into {planes} equal planes")
     out = torch.empty((planes, 3), device=a.device, dtype=torch.float64)
-    part = torch.empty(planes * (256 if planes == 1 else 64) * 3, device=a.device, dtype=torch.float64)
+    part = _rows_ws(a.device, planes * (_ROWS_ONE_PLANE if planes == 1 else _ROWS_PER_PLANE), 3)
     _L().plane_sums_f32(_p(a), _p(b), planes, a.numel() // planes, _p(out), _p(part), part.numel(), _st())
     return out
+
+
+def _head_operand(what, wrt, name, t, fp32_first=False):
+    """the refusals an image head makes of each operand: a device tensor, fp32, and no gradient wanted unless it is ``wrt``.  Each head
+    keeps the order it has always reported two faults in: psp_pixel_head the device first, gan_image_head (``fp32_first``) the type"""
+    no_device = not torch.is_tensor(t) or not t.is_cuda
+    no_fp32 = torch.is_tensor(t) and t.dtype != torch.float32
+    if no_device and not (fp32_first and no_fp32):
+        raise FmiError(f"{what}: face_mask_inpaint_amd ops need device tensors (there is no CPU fallback)")
+    if no_fp32:
+        raise FmiError(f"{what}: {name} is fp32, got {t.dtype}")
+    if name != wrt and t.requires_grad and torch.is_grad_enabled():
+        raise FmiError(f"{what} is differentiable with respect to {wrt} only: detach {name}")
+
+
+def _rgb_layout(x):
+    """[N, 3, H, W] -> (tensor, hwc): as it is if contiguous (hwc 0) or channels-last in memory (hwc 1: read and written as it lies, no
+    transposition), a contiguous copy of any other striding"""
+    if x.is_contiguous():
+        return x, 0
+    if x.permute(0, 2, 3, 1).is_contiguous():
+        return x, 1
+    return x.contiguous(), 0
 
 
 class _PspPixelHead(torch.autograd.Function):
@@ -1682,7 +1717,7 @@ class _PspPixelHead(torch.autograd.Function):
         pair_out = torch.empty((2 * n, h, w, 3), device=dev, dtype=torch.float32)
         pair_in = torch.empty((2 * n, h, w, 3), device=dev, dtype=torch.float32) if inner else None
         out2 = torch.empty(2, device=dev, dtype=torch.float32)
-        part = torch.empty(n * 64 * 2, device=dev, dtype=torch.float64)
+        part = _rows_ws(dev, n * _ROWS_PER_PLANE, 2)
         _L().psp_pixel_head_fwd_f32(_p(y_hat), _p(y), _p(ref), _p(mask), _p(pair_out), _p(pair_in), None, _p(out2), n, h, w, hwc, _p(part),
                                     part.numel(), _st())
         ctx.save_for_backward(y_hat, y, ref, mask)
@@ -1724,14 +1759,8 @@ def psp_pixel_head(y_hat, y, ref=None, mask=None):
     if y_hat is None or y is None:
         raise FmiError("psp_pixel_head: y_hat and y are required")
     for name, t in ts.items():
-        if t is None:
-            continue
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise FmiError("psp_pixel_head: face_mask_inpaint_amd ops need device tensors (there is no CPU fallback)")
-        if t.dtype != torch.float32:
-            raise FmiError(f"psp_pixel_head: {name} is fp32, got {t.dtype}")
-        if name != "y_hat" and t.requires_grad and torch.is_grad_enabled():
-            raise FmiError(f"psp_pixel_head is differentiable with respect to y_hat only: detach {name}")
+        if t is not None:
+            _head_operand("psp_pixel_head", "y_hat", name, t)
     if y_hat.dim() != 4 or y_hat.shape[1] != 3 or y_hat.numel() == 0:
         raise FmiError(f"psp_pixel_head: y_hat is [N, 3, H, W], got {tuple(y_hat.shape)}")
     n, _, h, w = y_hat.shape
@@ -1741,12 +1770,7 @@ def psp_pixel_head(y_hat, y, ref=None, mask=None):
     if mask is not None and tuple(mask.shape) != (n, h, w):
         raise FmiError(f"psp_pixel_head: mask is [N, H, W] = {(n, h, w)}, got {tuple(mask.shape)}")
     det = lambda t: None if t is None else t.detach().contiguous()
-    hwc = 0
-    if not y_hat.is_contiguous():
-        if y_hat.permute(0, 2, 3, 1).is_contiguous():
-            hwc = 1
-        else:
-            y_hat = y_hat.contiguous()
+    y_hat, hwc = _rgb_layout(y_hat)
     return _PspPixelHead.apply(y_hat, det(y), det(ref), det(mask), hwc)
 
 
@@ -1761,7 +1785,7 @@ class _GanImageHead(torch.autograd.Function):
         x_in = torch.empty((3 * n, oh, ow, 3), device=dev, dtype=torch.float32)
         y_in = torch.empty((3 * n, oh, ow, 3), device=dev, dtype=torch.float32)
         l1 = torch.empty((), device=dev, dtype=torch.float32)
-        part = torch.empty(n * 64, device=dev, dtype=torch.float64)
+        part = _rows_ws(dev, n * _ROWS_PER_PLANE, 1)
         _L().gan_image_head_fwd_f32(_p(gen), _p(gt), _p(src), _p(ref), _p(mask), _p(mean), _p(std), _p(x_in), _p(y_in), _p(l1), n, h, w, oh, ow, hwc,
                                     _p(part), part.numel(), _st())
         ctx.save_for_backward(gen, gt, mask, std)
@@ -1815,23 +1839,13 @@ def gan_image_head(gen, gt, src, ref, mask, mean, std, vgg_size=224):
     if mean.numel() != 3 or std.numel() != 3:
         raise FmiError("gan_image_head: mean and std have three entries")
     for name, t in ts.items():
-        if t.dtype != torch.float32:
-            raise FmiError(f"gan_image_head: {name} is fp32, got {t.dtype}")
-        if not t.is_cuda:
-            raise FmiError("gan_image_head: face_mask_inpaint_amd ops need device tensors (there is no CPU fallback)")
-        if name != "gen" and t.requires_grad and torch.is_grad_enabled():
-            raise FmiError(f"gan_image_head is differentiable with respect to gen only: detach {name}")
+        _head_operand("gan_image_head", "gen", name, t, fp32_first=True)
     vgg_size = int(vgg_size)
     if vgg_size <= 0:
         raise FmiError(f"gan_image_head: vgg_size {vgg_size}")
     oh, ow = (vgg_size, vgg_size) if w > vgg_size else (h, w)
     det = lambda t: t.detach().contiguous()
-    hwc = 0
-    if not gen.is_contiguous():
-        if gen.permute(0, 2, 3, 1).is_contiguous():
-            hwc = 1
-        else:
-            gen = gen.contiguous()
+    gen, hwc = _rgb_layout(gen)
     return _GanImageHead.apply(gen, det(gt), det(src), det(ref), det(mask), det(mean).view(3), det(std).view(3), oh, ow, hwc)
 
 

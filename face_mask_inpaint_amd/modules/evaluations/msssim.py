@@ -15,7 +15,7 @@ import ctypes as C
 import torch
 
 from ... import _lib
-from ...functional import FmiError, _chk, _p, _st
+from ...functional import _ROWS_PER_PLANE, FmiError, _chk, _p, _rows_ws, _st
 from .ssim import gaussian
 
 MS_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
@@ -25,7 +25,7 @@ def _plane_stats(a, b, win, c1, c2):
     """[N*C][2] = (mean ssim, mean cs) per plane of NCHW tensors"""
     n, c, h, w = a.shape
     out = torch.empty((n * c, 2), device=a.device, dtype=torch.float32)
-    part = torch.empty(n * c * 64 * 2, device=a.device, dtype=torch.float64)
+    part = _rows_ws(a.device, n * c * _ROWS_PER_PLANE, 2)
     _lib.lib().ssim_valid_f32(_p(a), _p(b), _p(win), win.numel(), n * c, h, w, c1, c2, _p(out), C.c_void_p(part.data_ptr()), part.numel(), _st())
     return out
 
