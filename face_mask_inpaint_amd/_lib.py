@@ -87,6 +87,10 @@ SIGNATURES = {
     "fmi_softmax_rows_bwd_f32": [vp, vp, vp, i64, i32, vp],
     "fmi_attention_fwd_f32": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "fmi_attention_bwd_f32": [vp] * 12 + [i32] * 5 + [vp],
+    "fmi_attention_fwd_image_bytes": [i32, i32, i32, i32, i32, C.POINTER(i64)],
+    "fmi_attention_fwd_pieces_f32": [vp] * 4 + [i64] + [vp] * 3 + [i32] * 5 + [vp],
+    "fmi_attention_bwd_image_bytes": [i32, i32, i32, i32, i32, C.POINTER(i64)],
+    "fmi_attention_bwd_pieces_f32": [vp] * 10 + [i64] + [vp] * 3 + [i32] * 5 + [vp],
     "fmi_eltwise_f32": [i32, vp, vp, vp, i64, f32, vp],
     "fmi_axpy_dev_f32": [vp, vp, vp, vp, i64, vp],
     "fmi_dot_f32": [vp, vp, i64, f32, vp, vp],
@@ -177,7 +181,7 @@ SIGNATURES = {
 STATUS = {0: "ok", 1: "bad argument", 2: "unsupported shape/mode", 3: "kernel launch failed"}
 
 
-PREDICATES = {"fmi_debug_bf16_tile": [i32], "fmi_set_deterministic": [i32], "fmi_get_deterministic": [], "fmi_conv2d_thin_supported": [PD], "fmi_conv2d_bf16_supported": [PD], "fmi_conv2d_thin_lrelu_supported": [PD], "fmi_conv2d_thin_lrelu_bwd_ws_bytes": [PD], "fmi_conv_transpose2d_pair_bwd_supported": [PD, i32, i32], "fmi_conv_transpose2d_pair_bwd_ws_bytes": [PD, i32, i32]}
+PREDICATES = {"fmi_debug_bf16_tile": [i32], "fmi_set_deterministic": [i32], "fmi_get_deterministic": [], "fmi_conv2d_thin_supported": [PD], "fmi_conv2d_bf16_supported": [PD], "fmi_conv2d_thin_lrelu_supported": [PD], "fmi_conv2d_thin_lrelu_bwd_ws_bytes": [PD], "fmi_conv_transpose2d_pair_bwd_supported": [PD, i32, i32], "fmi_conv_transpose2d_pair_bwd_ws_bytes": [PD, i32, i32], "fmi_attention_fwd_uses_pieces": [i32] * 5, "fmi_attention_bwd_uses_pieces": [i32] * 5}
 
 
 class FmiError(RuntimeError):

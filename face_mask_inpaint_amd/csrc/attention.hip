@@ -188,7 +188,9 @@ __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_kernel(const float* __res
 // =====================================================================================================
 // Forward on the bf16 matrix pipe (x6.h): the same flash structure, every product as six bf16 MFMAs of K = 16 on exact three-way
 // splits of the fp32 operands.
-//  * the K / V tile of 32 keys is split ONCE, on its way from the staging registers into LDS, into three bf16 images each:
+//  * the K / V tile of 32 keys is split into three bf16 images each -- on its way from the staging registers into LDS (IMG = false: the
+//    two- and four-wave forms, D = 16), or once per pass into the key-tile image that the eight-wave form streams by LDS-DMA (IMG = true,
+//    AttKImg below; T16384 d64 C256 b8: 5.64 ms with the cutting pass against 5.91, profiles/attn_pieces.txt):
 //      K pieces  [32 keys][D bf16],  row pitch 2 D + 16 bytes: the A fragment (key = lane, 8 consecutive d) is one ds_read_b128;
 //      V pieces  [32 keys][CT bf16], row pitch 2 CT + 64 bytes: the A fragment of O^T += V^T P^T (channel = lane, keys in the
 //                reduction) is two ds_read_b64_tr_b16 -- the hardware transposes a 4-key x 16-channel block per 16 lanes;
@@ -198,15 +200,56 @@ __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_kernel(const float* __res
 //  * per 32-key tile and wave: 6 x (D / 16 + 2 NCT) MFMAs (120 at D = 64, C = 256: 3 840 matrix-pipe cycles against 10 240 for the
 //    160 fp32 MFMAs), ~110 VALU instructions for the K / V split and 88 for P.
 // =====================================================================================================
-template <int D, int NCT, int NW>
+// ---- key-tile image (IMG instantiations): the K / V pieces of every 32-key tile, cut ONCE per pass by attn_cut_ktile_kernel instead of
+// once per workgroup (T / 256 times), in exactly the bytes of one LDS stage:
+//      [0, 3 KIMG)            K pieces [3][32 keys][2 D + 16 bytes]   (the last 16 bytes of a row are padding)
+//      [3 KIMG, 3 KIMG + 3 VIMG)  V pieces [3][32 keys][2 CT + 64 bytes], V = [V1 | V2]   (the last 64 bytes of a row are padding)
+//      .. BLK                 padding to whole KiB
+// Padding is never written and never read.  Block b = n (T / 32) + tile starts at byte b * BLK; a tile load is BLK / 1024
+// global_load_lds_dwordx4 per workgroup, issued at the top of the iteration BEFORE the one that consumes it: no staging registers, no
+// split and no ds_write in the loop.
+template <int D, int CT>
+struct AttKImg {
+  static constexpr int KP = 2 * D + 16, VP = 2 * CT + 64, KIMG = 32 * KP, VIMG = 32 * VP;
+  static constexpr int BLK = (3 * KIMG + 3 * VIMG + 1023) / 1024 * 1024;
+};
+// 8 consecutive fp32 values -> one 16-byte chunk in each of the three piece images (`step` bytes apart)
+__device__ __forceinline__ void att_cut8(const float* __restrict__ src, unsigned char* __restrict__ dst, int step) {
+  const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
+  uint32_t w[3][4];
+  split3_pair(a.x, a.y, w[0][0], w[1][0], w[2][0]);
+  split3_pair(a.z, a.w, w[0][1], w[1][1], w[2][1]);
+  split3_pair(b.x, b.y, w[0][2], w[1][2], w[2][2]);
+  split3_pair(b.z, b.w, w[0][3], w[1][3], w[2][3]);
+#pragma unroll
+  for (int pc = 0; pc < 3; ++pc) *reinterpret_cast<uint4*>(dst + pc * step) = make_uint4(w[pc][0], w[pc][1], w[pc][2], w[pc][3]);
+}
+template <int D, int CT>
+__global__ void __launch_bounds__(256) attn_cut_ktile_kernel(const float* __restrict__ q, const float* __restrict__ v1,
+                                                             const float* __restrict__ v2, unsigned char* __restrict__ img, int C1, int C2) {
+  typedef AttKImg<D, CT> I;
+  const int64_t row0 = (int64_t)blockIdx.x * 32;
+  unsigned char* blk = img + (int64_t)blockIdx.x * I::BLK;
+  for (int f = threadIdx.x; f < 32 * (D / 8); f += 256) {
+    const int row = f / (D / 8), ch = f % (D / 8);
+    att_cut8(q + (row0 + row) * D + 8 * ch, blk + row * I::KP + 16 * ch, I::KIMG);
+  }
+  for (int f = threadIdx.x; f < 32 * (CT / 8); f += 256) {
+    const int row = f / (CT / 8), ch = f % (CT / 8), c = 8 * ch;
+    const float* src = (c < C1) ? v1 + (row0 + row) * C1 + c : v2 + (row0 + row) * C2 + (c - C1);
+    att_cut8(src, blk + 3 * I::KIMG + row * I::VP + 16 * ch, I::VIMG);
+  }
+}
+
+template <int D, int NCT, int NW, bool IMG>
 __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_x6_kernel(const float* __restrict__ q, const float* __restrict__ v1,
-                                                                 const float* __restrict__ v2, float* __restrict__ o1,
-                                                                 float* __restrict__ o2, float* __restrict__ lse, int T, int C1,
-                                                                 int C2) {
+                                                                 const float* __restrict__ v2, const unsigned char* __restrict__ img,
+                                                                 float* __restrict__ o1, float* __restrict__ o2, float* __restrict__ lse,
+                                                                 int T, int C1, int C2) {
   constexpr int CT = NCT * 32;
   constexpr int KP = 2 * D + 16, VP = 2 * CT + 64;          // row pitches (bytes)
   constexpr int KIMG = 32 * KP, VIMG = 32 * VP;             // one piece image
-  constexpr int STAGE = 3 * KIMG + 3 * VIMG;                // bytes per stage
+  constexpr int STAGE = IMG ? AttKImg<D, CT>::BLK : 3 * KIMG + 3 * VIMG;   // bytes per stage
   constexpr int NTH = NW * 64;
   constexpr int NKL = (8 * D + NTH - 1) / NTH;              // float4 loads per thread for a K tile
   constexpr int NVL = (8 * CT) / NTH;                       // float4 loads per thread for a V tile
@@ -276,13 +319,41 @@ __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_x6_kernel(const float* __
   const uint32_t vlane = (uint32_t)((4 * lh + (i16 >> 2)) * VP + (16 * ((lane >> 4) & 1) + 4 * (i16 & 3)) * 2);
   const uint32_t klane = (uint32_t)(l31 * KP + 16 * lh);
 
-  att_gload<D, CT, NKL, NVL, NTH>(rk, rv, qb, v1b, v2b, C1, C2, 0, tid);
-  lstore(0);
+  // IMG: key tile k0's block goes global -> LDS stage `st` directly, wave w taking the KiB chunks w, w + NW, ..
+  const unsigned char* imgl = IMG ? img + (int64_t)n * (T / 32) * STAGE + lane * 16 : nullptr;
+  const int widu = __builtin_amdgcn_readfirstlane(wid);
+  auto dma_tile = [&](int k0, int st) {
+    constexpr int NCH = STAGE / 1024;
+    const unsigned char* src = imgl + (int64_t)(k0 >> 5) * STAGE + widu * 1024;
+    const uint32_t dst = lds0 + (uint32_t)(st * STAGE) + (uint32_t)widu * 1024u;
+#pragma unroll
+    for (int c = 0; c < (NCH + NW - 1) / NW; ++c) {
+      if (NW * c + NW - 1 < NCH || NW * c + widu < NCH) {
+        unsigned keep;
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep)
+                     : "v"(src + c * (NW * 1024)), "s"(dst + (uint32_t)(c * (NW * 1024)))
+                     : "memory");
+      }
+    }
+  };
+  if constexpr (IMG) {
+    dma_tile(0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  } else {
+    att_gload<D, CT, NKL, NVL, NTH>(rk, rv, qb, v1b, v2b, C1, C2, 0, tid);
+    lstore(0);
+  }
   __syncthreads();
   int buf = 0;
   for (int k0 = 0; k0 < T; k0 += 32) {
-    // unconditional prefetch (the last iteration re-reads its own tile): a conditional one sends rk/rv to scratch
-    att_gload<D, CT, NKL, NVL, NTH>(rk, rv, qb, v1b, v2b, C1, C2, k0 + 32 < T ? k0 + 32 : k0, tid);
+    if constexpr (IMG) {
+      // stage buf ^ 1 was read in the iteration before; every wave passed the barrier that ended it (the last iteration re-reads its own tile)
+      dma_tile(k0 + 32 < T ? k0 + 32 : k0, buf ^ 1);
+    } else {
+      // unconditional prefetch (the last iteration re-reads its own tile): a conditional one sends rk/rv to scratch
+      att_gload<D, CT, NKL, NVL, NTH>(rk, rv, qb, v1b, v2b, C1, C2, k0 + 32 < T ? k0 + 32 : k0, tid);
+    }
     const uint32_t kimg = lds0 + (uint32_t)(buf * STAGE) + klane;
     const uint32_t vimg = lds0 + (uint32_t)(buf * STAGE + 3 * KIMG) + vlane;
     // S^T[key][query] for 32 keys x this wave's 32 queries
@@ -349,7 +420,10 @@ __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_x6_kernel(const float* __
         acc[c] = mfma_x6(vp, pp, acc[c]);
       }
     }
-    lstore(buf ^ 1);
+    if constexpr (IMG)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's chunks of the next tile have landed (issued a whole tile ago)
+    else
+      lstore(buf ^ 1);
     __syncthreads();
     buf ^= 1;
   }
@@ -389,11 +463,11 @@ extern "C" int fmi_attention_fwd_f32(const float* q, const float* v1, const floa
     constexpr int lds_bytes = 2 * 3 * 32 * ((2 * DD + 16) + (2 * NN * 32 + 64));                                               \
     static fmi_attr_flags attr_set{}; int attr_set_dev;\
     if (fmi_attr_needed(attr_set, attr_set_dev)) {                                                                                                          \
-      if (hipFuncSetAttribute((const void*)attn_fwd_x6_kernel<DD, NN, WW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) \
+      if (hipFuncSetAttribute((const void*)attn_fwd_x6_kernel<DD, NN, WW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) \
         return FMI_ERR_LAUNCH;                                                                                                \
       fmi_attr_mark(attr_set, attr_set_dev);                                                                                                        \
     }                                                                                                                         \
-    hipLaunchKernelGGL((attn_fwd_x6_kernel<DD, NN, WW>), grid, block, lds_bytes, st, q, v1, v2, o1, o2, lse, T, C1, C2);       \
+    hipLaunchKernelGGL((attn_fwd_x6_kernel<DD, NN, WW, false>), grid, block, lds_bytes, st, q, v1, v2, (const unsigned char*)nullptr, o1, o2, lse, T, C1, C2); \
   } while (0)
 #else
 #define ATT_LAUNCH1(DD, NN, WW) hipLaunchKernelGGL((attn_fwd_kernel<DD, NN, WW>), grid, block, 0, st, q, v1, v2, o1, o2, lse, T, C1, C2)
@@ -822,7 +896,12 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_kernel(const float* __restri
 // =====================================================================================================
 // Backward, second structure, on the bf16 matrix pipe (x6.h).  Same roles as attn_bwd2_kernel (a wave owns 32 keys with all value
 // channels; the query tile staged in LDS feeds the four key blocks of the workgroup), every product as six bf16 MFMAs of K = 16:
-//  * the query tile (Q_i, gO_i) is cut into its three bf16 pieces ONCE, on the way from the staging registers into LDS:
+//  * the query tile (Q_i, gO_i) is cut into its three bf16 pieces on the way from the staging registers into LDS (IMG = false, reached through
+//    fmi_attention_bwd_f32) or, IMG = true (fmi_attention_bwd_pieces_f32, what the library's callers dispatch to), once per pass by
+//    attn_cut_qtile_kernel into the query-tile image (AttQImg below), whose blocks go global -> LDS by LDS-DMA: the copy of tile i + 1 is
+//    issued behind a barrier that follows every wave's last read of tile i (the transposed Q reads of the dK phase), runs under the rest of
+//    dK and the dQ phase, and is waited for in front of the barrier that ends the tile.  Three barriers a tile instead of two, no split, no
+//    ds_write and no staging registers (212 VGPRs instead of 240): 15.16 ms against 16.11 at T16384 d64 C256 b8, cutting pass included.
 //      gO pieces [32 q][CT], 16-byte chunks XOR-swizzled (chunk ^ (((q & 3) << 2) | ((q >> 2) & 3)) inside each 256-byte window) so
 //      that the SAME image serves the row fragments of dP = gO V^T (ds_read_b128) and the transposed fragments of dV^T = gO^T P
 //      (ds_read_b64_tr_b16), both conflict-free;
@@ -852,12 +931,52 @@ extern "C" int fmi_debug_attn_stamps(unsigned long long* host16) {
 #else
 #define ATT_STAMP(i)
 #endif
-template <int D, int NCT>
+// ---- query-tile image: the bf16 pieces of gO = [gO1 | gO2] and Q, cut ONCE per backward pass instead of once per workgroup (T / 128 times)
+// and stored in exactly the bytes the kernel below keeps in LDS, one block per 32 query rows:
+//      [0, 3 GIMG)        gO pieces [3][32 q][2 CT bytes], the 16-byte chunks of a row XOR-swizzled as in Gs (below)
+//      [3 GIMG, LSE)      Q pieces  [3][32 q][192 bytes]; bytes 2 D .. 191 of a row are padding, never written and never read
+//      [LSE, LSE + 256)   lse[32], delta[32] of the rows (fp32)
+//      [LSE + 256, BLK)   padding to whole KiB, never written and never read
+// so a tile load is BLK / 1024 global_load_lds_dwordx4 per workgroup (1 KiB per wave instruction, lane-linear in LDS: pitch and swizzle
+// are applied here, on the global side).  Block b = n (T / 32) + tile starts at byte b * BLK.
+template <int D, int CT>
+struct AttQImg {
+  static constexpr int GP = 2 * CT, GIMG = 32 * GP, QP = 192, QIMG = 32 * QP;
+  static constexpr int LSE = 3 * GIMG + 3 * QIMG;
+  static constexpr int BLK = (LSE + 256 + 1023) / 1024 * 1024;
+  static_assert(2 * D <= QP, "Q row fits its pitch");
+};
+__device__ __forceinline__ int att_swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
+// one workgroup per block (32 rows of the flattened [N T] row axis; T % 32 == 0).  Pure bandwidth: 4 B read, 6 B written per element.
+template <int D, int CT>
+__global__ void __launch_bounds__(256) attn_cut_qtile_kernel(const float* __restrict__ q, const float* __restrict__ g1,
+                                                             const float* __restrict__ g2, const float* __restrict__ lse,
+                                                             const float* __restrict__ delta, unsigned char* __restrict__ img, int C1, int C2) {
+  typedef AttQImg<D, CT> I;
+  const int64_t row0 = (int64_t)blockIdx.x * 32;
+  unsigned char* blk = img + (int64_t)blockIdx.x * I::BLK;
+  for (int f = threadIdx.x; f < 32 * (CT / 8); f += 256) {
+    const int row = f / (CT / 8), ch = f % (CT / 8), c = 8 * ch;
+    const float* src = (c < C1) ? g1 + (row0 + row) * C1 + c : g2 + (row0 + row) * C2 + (c - C1);
+    att_cut8(src, blk + row * I::GP + 16 * ((ch & ~15) | ((ch ^ att_swz(row)) & 15)), I::GIMG);
+  }
+  for (int f = threadIdx.x; f < 32 * (D / 8); f += 256) {
+    const int row = f / (D / 8), ch = f % (D / 8);
+    att_cut8(q + (row0 + row) * D + 8 * ch, blk + 3 * I::GIMG + row * I::QP + 16 * ch, I::QIMG);
+  }
+  if (threadIdx.x < 64) {
+    const int r = threadIdx.x & 31;
+    reinterpret_cast<float*>(blk + I::LSE)[threadIdx.x] = threadIdx.x < 32 ? lse[row0 + r] : delta[row0 + r];
+  }
+}
+
+template <int D, int NCT, bool IMG>
 __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __restrict__ q, const float* __restrict__ v1,
                                                               const float* __restrict__ v2, const float* __restrict__ g1,
                                                               const float* __restrict__ g2, const float* __restrict__ lse,
-                                                              const float* __restrict__ delta, float* __restrict__ gv1,
-                                                              float* __restrict__ gv2, float* __restrict__ gq, int T, int C1, int C2, int kb0) {
+                                                              const float* __restrict__ delta, const unsigned char* __restrict__ img,
+                                                              float* __restrict__ gv1, float* __restrict__ gv2, float* __restrict__ gq,
+                                                              int T, int C1, int C2, int kb0) {
   constexpr int CT = NCT * 32, LDQ = D + 1, NDT = D / 32;
   constexpr int NQL = (8 * D) / 256 > 0 ? (8 * D) / 256 : 1, NVL = (8 * CT) / 256;
   constexpr int GP = 2 * CT, GIMG = 32 * GP;   // gO piece image: row pitch, bytes per piece
@@ -869,7 +988,8 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __res
   unsigned char* Qs = Gs + 3 * GIMG;                              // [3][32][QP]
   float* lse_i = reinterpret_cast<float*>(Qs + 3 * QIMG);         // [32]
   float* del_i = lse_i + 32;                                      // [32]
-  unsigned char* Ks = reinterpret_cast<unsigned char*>(del_i + 32);  // [4][3][32][KP]  each wave's key block as bf16 pieces: B operand of S (row reads) and of dQ = dS K (transposed reads)
+  // IMG: Gs .. del_i are one block of the query-tile image (AttQImg), copied as it stands; its last KiB holds lse / delta and padding
+  unsigned char* Ks = reinterpret_cast<unsigned char*>(del_i + 32) + (IMG ? AttQImg<D, CT>::BLK - AttQImg<D, CT>::LSE - 256 : 0);  // [4][3][32][KP]  each wave's key block as bf16 pieces: B operand of S (row reads) and of dQ = dS K (transposed reads)
   unsigned char* Ts = Ks + 4 * 3 * KIMG;                          // [4][WSLOT]  per wave: the transposed dS pieces [3][32][64 B], then (same bytes) its query-side partial tiles
   // a wave's partial dQ tiles [NDT][16][64] overwrite its own dS^T image once its transposed reads are done; the other waves read them between
   // the two barriers that follow, and the image is rewritten only after the second one.  (LDS float atomics instead of partial tiles: ~250
@@ -921,6 +1041,24 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __res
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc_dk[c][r] = 0.f;
 
+  // IMG: tile i0's block of the image goes global -> LDS directly, wave w taking the KiB chunks w, w + 4, ..; no staging registers
+  const unsigned char* imgl = IMG ? img + (int64_t)n * (T / 32) * AttQImg<D, CT>::BLK + lane * 16 : nullptr;
+  const int widu = __builtin_amdgcn_readfirstlane(wid);
+  auto dma_tile = [&](int i0) {
+    constexpr int NCH = AttQImg<D, CT>::BLK / 1024;
+    const unsigned char* src = imgl + (int64_t)(i0 >> 5) * AttQImg<D, CT>::BLK + widu * 1024;
+    const uint32_t dst = lds0 + (uint32_t)widu * 1024u;
+#pragma unroll
+    for (int c = 0; c < (NCH + 3) / 4; ++c) {
+      if (4 * c + 3 < NCH || 4 * c + widu < NCH) {
+        unsigned keep;
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep)
+                     : "v"(src + c * 4096), "s"(dst + (uint32_t)(c * 4096))
+                     : "memory");
+      }
+    }
+  };
   float4 rq[NQL], rg[NVL];
   float rl = 0.f, rd = 0.f;
   auto gload = [&](int i0) {
@@ -940,7 +1078,7 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __res
     rl = lseb[i0 + (tid & 31)];
     rd = delb[i0 + (tid & 31)];
   };
-  auto swz = [](int row) { return ((row & 3) << 2) | ((row >> 2) & 3); };
+  auto swz = [](int row) { return att_swz(row); };
   auto lstore = [&]() {
 #pragma unroll
     for (int i = 0; i < NQL; ++i) {
@@ -1019,8 +1157,13 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __res
   const uint32_t t_tr = lds0 + t_base + (uint32_t)((8 * lh + tq) * 64);          // key rows 16 s + 8 lh + tq (+ 4): + 8 * ((4 gb + tp) ^ swizzle of that row)
   const int t_rx = (4 * lh) | (tq >> 1);                                         // ((row >> 1) & 7) of the first row; the row 4 further: + 2
 
-  gload(0);
-  lstore();
+  if constexpr (IMG) {
+    dma_tile(0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  } else {
+    gload(0);
+    lstore();
+  }
   __syncthreads();
   for (int i0 = 0; i0 < T; i0 += 32) {
     ATT_STAMP(0);
@@ -1205,14 +1348,26 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __res
 #pragma unroll
       for (int c = 0; c < NDT; ++c) pin3(aq1[c]);
     ATT_STAMP(4);
-      gload(i0 + 32 < T ? i0 + 32 : i0);
+      if constexpr (IMG) {
+        // aq1 was this wave's last read of the query tile (the dQ phase reads Ks and Ts only).  Once every wave is here the next tile's
+        // block may overwrite Gs / Qs / lse_i / del_i; the copy (the last tile re-reads its own block) runs under the remaining dK
+        // MFMAs and the whole dQ phase and is waited for before the barrier that ends the tile
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        dma_tile(i0 + 32 < T ? i0 + 32 : i0);
 #pragma unroll
-      for (int c = 0; c < NDT; ++c) acc_dk[c] = mfma_x6(aq1[c], ds1, acc_dk[c]);
+        for (int c = 0; c < NDT; ++c) acc_dk[c] = mfma_x6(aq1[c], ds1, acc_dk[c]);
+      } else {
+        gload(i0 + 32 < T ? i0 + 32 : i0);
 #pragma unroll
-      for (int g = 0; g < 6 * NDT; ++g) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+        for (int c = 0; c < NDT; ++c) acc_dk[c] = mfma_x6(aq1[c], ds1, acc_dk[c]);
+#pragma unroll
+        for (int g = 0; g < 6 * NDT; ++g) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);
+          __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+        }
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -1274,7 +1429,10 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __res
   #pragma unroll
         for (int w = 0; w < 4; ++w) part[rr][w] = reinterpret_cast<const float*>(Ts + w * WSLOT)[(wid * NDT * 4 + rr) * 64 + lane];
     ATT_STAMP(9);
-      lstore();
+      if constexpr (IMG)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's chunks of the next tile's block have landed (issued a dQ phase ago)
+      else
+        lstore();
     ATT_STAMP(10);
   #pragma unroll
       for (int rr = 0; rr < NDT * 4; ++rr) {
@@ -1359,14 +1517,14 @@ extern "C" int fmi_attention_bwd_f32(const float* q, const float* v1, const floa
     if (FMI_X6) {                                                                                                        \
       static fmi_attr_flags attr_setx{}; int attr_setx_dev;\
       if (fmi_attr_needed(attr_setx, attr_setx_dev)) {                                                                   \
-        if (hipFuncSetAttribute((const void*)attn_bwd2_x6_kernel<DD, NN>, hipFuncAttributeMaxDynamicSharedMemorySize,    \
+        if (hipFuncSetAttribute((const void*)attn_bwd2_x6_kernel<DD, NN, false>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                 (int)lds2x(DD, NN * 32)) != hipSuccess)                                                  \
           return FMI_ERR_LAUNCH;                                                                                         \
         fmi_attr_mark(attr_setx, attr_setx_dev);                                                                         \
       }                                                                                                                  \
       for (int kb = 0; kb < (det ? (int)grid2.x : 1); ++kb)                                                              \
-        hipLaunchKernelGGL((attn_bwd2_x6_kernel<DD, NN>), det ? dim3(1, grid2.y) : grid2, block, lds2x(DD, NN * 32), st, q, v1, v2, go1, go2, \
-                           lse, (const float*)delta_scratch, gv1, gv2, gq_zeroed, T, C1, C2, kb);                        \
+        hipLaunchKernelGGL((attn_bwd2_x6_kernel<DD, NN, false>), det ? dim3(1, grid2.y) : grid2, block, lds2x(DD, NN * 32), st, q, v1, v2, go1, go2, \
+                           lse, (const float*)delta_scratch, (const unsigned char*)nullptr, gv1, gv2, gq_zeroed, T, C1, C2, kb); \
       return fmi_launch_status();                                                                                        \
     }                                                                                                                    \
     static fmi_attr_flags attr_set2{}; int attr_set2_dev;\
@@ -1411,3 +1569,125 @@ extern "C" int fmi_attention_bwd_f32(const float* q, const float* v1, const floa
   return fmi_launch_status();
 }
 
+
+// =====================================================================================================
+// Backward on the query-tile image (AttQImg): the same second-structure kernel, its gO / Q pieces cut once per pass by
+// attn_cut_qtile_kernel and streamed by LDS-DMA.  fmi_attention_bwd_uses_pieces is the shape dispatch (the shapes the second structure
+// takes above); the entry point itself accepts every shape the kernel can run, so a test may call it below the fill-the-GPU threshold.
+// =====================================================================================================
+static bool att_pieces_shape(int T, int D, int C1, int C2) {
+  const int nct = (C1 + C2) / 32;
+  return FMI_X6 && T > 0 && T % 128 == 0 && C1 > 0 && C2 >= 0 && C1 % 32 == 0 && C2 % 32 == 0 && (D == 32 || D == 64) && (nct == 4 || nct == 8);
+}
+extern "C" int fmi_attention_bwd_uses_pieces(int N, int T, int D, int C1, int C2) {
+  return N > 0 && N <= 65535 && att_pieces_shape(T, D, C1, C2) && (int64_t)(T / 128) * N >= 128;
+}
+// bytes of the backward's query-tile image (0: the shape has none)
+extern "C" int fmi_attention_bwd_image_bytes(int N, int T, int D, int C1, int C2, int64_t* bytes) {
+  if (!bytes || N <= 0) return FMI_ERR_BAD_ARG;
+  *bytes = 0;
+  if (!att_pieces_shape(T, D, C1, C2)) return FMI_OK;
+  const int ct = C1 + C2;
+  const int64_t blk = D == 64 ? (ct == 256 ? AttQImg<64, 256>::BLK : AttQImg<64, 128>::BLK) : (ct == 256 ? AttQImg<32, 256>::BLK : AttQImg<32, 128>::BLK);
+  *bytes = (int64_t)N * (T / 32) * blk;
+  return FMI_OK;
+}
+
+extern "C" int fmi_attention_bwd_pieces_f32(const float* q, const float* v1, const float* v2, const float* o1, const float* o2,
+                                            const float* go1, const float* go2, const float* lse, float* delta_scratch, void* image,
+                                            int64_t image_bytes, float* gv1, float* gv2, float* gq_zeroed, int N, int T, int D, int C1,
+                                            int C2, void* stream) {
+  if (!q || !v1 || !o1 || !go1 || !lse || !delta_scratch || !image || !gv1 || !gq_zeroed || N <= 0 || T <= 0 || C1 <= 0 || C2 < 0)
+    return FMI_ERR_BAD_ARG;
+  if (C2 > 0 && (!v2 || !o2 || !go2 || !gv2)) return FMI_ERR_BAD_ARG;
+  if (!att_pieces_shape(T, D, C1, C2) || N > 65535) return FMI_ERR_UNSUPPORTED;
+  if ((((uintptr_t)q | (uintptr_t)v1 | (uintptr_t)v2 | (uintptr_t)go1 | (uintptr_t)go2 | (uintptr_t)gv1 | (uintptr_t)gv2 | (uintptr_t)image) & 15) != 0)
+    return FMI_ERR_BAD_ARG;
+  int64_t need = 0;
+  fmi_attention_bwd_image_bytes(N, T, D, C1, C2, &need);
+  if (image_bytes < need) return FMI_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t rows = (int64_t)N * T;
+  hipLaunchKernelGGL(rowdot2_kernel, dim3((unsigned)ceil_div64(rows, 4)), dim3(256), 0, st, go1, o1, C1, C2 ? go2 : nullptr, o2, C2,
+                     delta_scratch, rows);
+  const bool det = fmi_det();  // reproducible mode: one key block per launch, as in fmi_attention_bwd_f32
+  const dim3 grid(T / 128, N), block(256);
+  unsigned char* img = (unsigned char*)image;
+#define ATTP_LAUNCH(DD, NN)                                                                                                      \
+  do {                                                                                                                           \
+    typedef AttQImg<DD, NN * 32> I;                                                                                              \
+    constexpr int lds_bytes = I::BLK + 4 * 3 * 32 * (2 * DD + 16) + 4 * ((DD / 32) * 4096 > 6144 ? (DD / 32) * 4096 : 6144);      \
+    static fmi_attr_flags attr_set{};                                                                                            \
+    int attr_set_dev;                                                                                                            \
+    if (fmi_attr_needed(attr_set, attr_set_dev)) {                                                                               \
+      if (hipFuncSetAttribute((const void*)attn_bwd2_x6_kernel<DD, NN, true>, hipFuncAttributeMaxDynamicSharedMemorySize,        \
+                              lds_bytes) != hipSuccess)                                                                          \
+        return FMI_ERR_LAUNCH;                                                                                                   \
+      fmi_attr_mark(attr_set, attr_set_dev);                                                                                     \
+    }                                                                                                                            \
+    hipLaunchKernelGGL((attn_cut_qtile_kernel<DD, NN * 32>), dim3((unsigned)(rows / 32)), dim3(256), 0, st, q, go1, go2, lse,    \
+                       (const float*)delta_scratch, img, C1, C2);                                                                \
+    for (int kb = 0; kb < (det ? (int)grid.x : 1); ++kb)                                                                         \
+      hipLaunchKernelGGL((attn_bwd2_x6_kernel<DD, NN, true>), det ? dim3(1, grid.y) : grid, block, lds_bytes, st, q, v1, v2,     \
+                         go1, go2, lse, (const float*)delta_scratch, (const unsigned char*)img, gv1, gv2, gq_zeroed, T, C1, C2, kb); \
+  } while (0)
+  const int nct = (C1 + C2) / 32;
+  if (D == 64 && nct == 8) ATTP_LAUNCH(64, 8);
+  else if (D == 32 && nct == 8) ATTP_LAUNCH(32, 8);
+  else if (D == 32 && nct == 4) ATTP_LAUNCH(32, 4);
+  else ATTP_LAUNCH(64, 4);
+#undef ATTP_LAUNCH
+  return fmi_launch_status();
+}
+
+// =====================================================================================================
+// Forward on the key-tile image (AttKImg): the eight-wave kernel with its K / V pieces cut once per pass and streamed by LDS-DMA.
+// fmi_attention_fwd_uses_pieces is the shape dispatch (where fmi_attention_fwd_f32 takes eight waves, D in {32, 64}); the entry point
+// itself accepts every T % 256 == 0 of those D / C.
+// =====================================================================================================
+extern "C" int fmi_attention_fwd_uses_pieces(int N, int T, int D, int C1, int C2) {
+  return N > 0 && N <= 65535 && att_pieces_shape(T, D, C1, C2) && T % 256 == 0 && (int64_t)(T / 256) * N >= 256;
+}
+extern "C" int fmi_attention_fwd_image_bytes(int N, int T, int D, int C1, int C2, int64_t* bytes) {
+  if (!bytes || N <= 0) return FMI_ERR_BAD_ARG;
+  *bytes = 0;
+  if (!att_pieces_shape(T, D, C1, C2) || T % 256 != 0) return FMI_OK;
+  const int ct = C1 + C2;
+  const int64_t blk = D == 64 ? (ct == 256 ? AttKImg<64, 256>::BLK : AttKImg<64, 128>::BLK) : (ct == 256 ? AttKImg<32, 256>::BLK : AttKImg<32, 128>::BLK);
+  *bytes = (int64_t)N * (T / 32) * blk;
+  return FMI_OK;
+}
+extern "C" int fmi_attention_fwd_pieces_f32(const float* q, const float* v1, const float* v2, void* image, int64_t image_bytes, float* o1,
+                                            float* o2, float* lse, int N, int T, int D, int C1, int C2, void* stream) {
+  if (!q || !v1 || !o1 || !image || N <= 0 || T <= 0 || C1 <= 0 || C2 < 0 || (C2 > 0 && (!v2 || !o2))) return FMI_ERR_BAD_ARG;
+  if (!att_pieces_shape(T, D, C1, C2) || T % 256 != 0 || N > 65535) return FMI_ERR_UNSUPPORTED;
+  if ((((uintptr_t)q | (uintptr_t)v1 | (uintptr_t)v2 | (uintptr_t)o1 | (uintptr_t)o2 | (uintptr_t)image) & 15) != 0) return FMI_ERR_BAD_ARG;
+  int64_t need = 0;
+  fmi_attention_fwd_image_bytes(N, T, D, C1, C2, &need);
+  if (image_bytes < need) return FMI_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned char* img = (unsigned char*)image;
+#define ATTFP_LAUNCH(DD, NN)                                                                                                     \
+  do {                                                                                                                           \
+    constexpr int lds_bytes = 2 * AttKImg<DD, NN * 32>::BLK;                                                                     \
+    static fmi_attr_flags attr_set{};                                                                                            \
+    int attr_set_dev;                                                                                                            \
+    if (fmi_attr_needed(attr_set, attr_set_dev)) {                                                                               \
+      if (hipFuncSetAttribute((const void*)attn_fwd_x6_kernel<DD, NN, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize,      \
+                              lds_bytes) != hipSuccess)                                                                          \
+        return FMI_ERR_LAUNCH;                                                                                                   \
+      fmi_attr_mark(attr_set, attr_set_dev);                                                                                     \
+    }                                                                                                                            \
+    hipLaunchKernelGGL((attn_cut_ktile_kernel<DD, NN * 32>), dim3((unsigned)((int64_t)N * T / 32)), dim3(256), 0, st, q, v1, v2, \
+                       img, C1, C2);                                                                                             \
+    hipLaunchKernelGGL((attn_fwd_x6_kernel<DD, NN, 8, true>), dim3(T / 256, N), dim3(512), lds_bytes, st, q, v1, v2,             \
+                       (const unsigned char*)img, o1, o2, lse, T, C1, C2);                                                       \
+  } while (0)
+  const int nct = (C1 + C2) / 32;
+  if (D == 64 && nct == 8) ATTFP_LAUNCH(64, 8);
+  else if (D == 32 && nct == 8) ATTFP_LAUNCH(32, 8);
+  else if (D == 32 && nct == 4) ATTFP_LAUNCH(32, 4);
+  else ATTFP_LAUNCH(64, 4);
+#undef ATTFP_LAUNCH
+  return fmi_launch_status();
+}

@@ -1465,8 +1465,15 @@ class _SelfAttention(torch.autograd.Function):
             c1 = vs[0].shape[2]
             c2 = vs[1].shape[2] if len(vs) > 1 else 0
             with _prof(f"attn_fused_fwd|T{t} d{d} C{c1 + c2} b{n}", 2.0 * n * t * t * (d + c1 + c2)):
-                _L().attention_fwd_f32(_p(q), _p(vs[0]), _p(vs[1]) if len(vs) > 1 else None, _p(outs[0]),
-                                       _p(outs[1]) if len(vs) > 1 else None, _p(lse), n, t, d, c1, c2, _st())
+                if _L().attention_fwd_uses_pieces(n, t, d, c1, c2):  # K / V pieces cut once into a tile image; the cut is timed with the pass
+                    nbytes = C.c_int64(0)
+                    _L().attention_fwd_image_bytes(n, t, d, c1, c2, C.byref(nbytes))
+                    image = torch.empty(nbytes.value, device=q.device, dtype=torch.uint8)
+                    _L().attention_fwd_pieces_f32(_p(q), _p(vs[0]), _p(vs[1]) if len(vs) > 1 else None, _p(image), nbytes.value, _p(outs[0]),
+                                                  _p(outs[1]) if len(vs) > 1 else None, _p(lse), n, t, d, c1, c2, _st())
+                else:
+                    _L().attention_fwd_f32(_p(q), _p(vs[0]), _p(vs[1]) if len(vs) > 1 else None, _p(outs[0]),
+                                           _p(outs[1]) if len(vs) > 1 else None, _p(lse), n, t, d, c1, c2, _st())
             # the outputs go through save_for_backward: as plain ctx attributes they would close a reference cycle through their
             # own grad_fn (node -> ctx -> output -> node) that Python's collector cannot see -- one whole discriminator graph leaked
             # per training step (150 MB)
@@ -1508,6 +1515,14 @@ class _SelfAttention(torch.autograd.Function):
             c2 = vs[1].shape[2] if len(vs) > 1 else 0
             two = len(vs) > 1
             with _prof(f"attn_fused_bwd|T{t} d{d} C{c1 + c2} b{n}", 2.0 * n * t * t * (3 * d + 2 * (c1 + c2))):
+                if _L().attention_bwd_uses_pieces(n, t, d, c1, c2):  # gO / Q pieces cut once into a tile image; the cut is timed with the pass
+                    nbytes = C.c_int64(0)
+                    _L().attention_bwd_image_bytes(n, t, d, c1, c2, C.byref(nbytes))
+                    image = torch.empty(nbytes.value, device=q.device, dtype=torch.uint8)
+                    _L().attention_bwd_pieces_f32(_p(q), _p(vs[0]), _p(vs[1]) if two else None, _p(fwd_outs[0]), _p(fwd_outs[1]) if two else None,
+                                                  _p(gos[0]), _p(gos[1]) if two else None, _p(lse), _p(delta), _p(image), nbytes.value,
+                                                  _p(gvs[0]), _p(gvs[1]) if two else None, _p(gq), n, t, d, c1, c2, _st())
+                    return (gq,) + tuple(gvs)
                 _L().attention_bwd_f32(_p(q), _p(vs[0]), _p(vs[1]) if two else None, _p(fwd_outs[0]), _p(fwd_outs[1]) if two else None,
                                        _p(gos[0]), _p(gos[1]) if two else None, _p(lse), _p(delta), _p(gvs[0]), _p(gvs[1]) if two else None,
                                        _p(gq), n, t, d, c1, c2, _st())

@@ -335,11 +335,38 @@ int fmi_softmax_rows_bwd_f32(const float* p, const float* dp, float* ds, int64_t
 int fmi_attention_fwd_f32(const float* q, const float* v1, const float* v2, float* o1, float* o2, float* lse,
                           int N, int T, int D, int C1, int C2, void* stream);
 
+/* The same forward with the bf16 pieces of K (= q) and V cut ONCE per pass into a key-tile image (layout: csrc/attention.hip, AttKImg)
+ * that every workgroup streams into LDS by LDS-DMA; bit-identical results (the same pieces in the same MFMA order).
+ *   fmi_attention_fwd_uses_pieces   1 where the library's shape dispatch takes this path (T % 256 == 0, (T/256) N >= 256, D in {32,64},
+ *                                   (C1+C2)/32 in {4,8}); callers take fmi_attention_fwd_f32 elsewhere
+ *   fmi_attention_fwd_image_bytes   size of the image workspace (0: the shape has none)
+ *   fmi_attention_fwd_pieces_f32    cuts the image (workspace `image`, 16-byte aligned) and runs the forward; accepts every
+ *                                   T % 256 == 0 of the supported D / C, also below the dispatch threshold */
+int fmi_attention_fwd_uses_pieces(int N, int T, int D, int C1, int C2);
+int fmi_attention_fwd_image_bytes(int N, int T, int D, int C1, int C2, int64_t* bytes);
+int fmi_attention_fwd_pieces_f32(const float* q, const float* v1, const float* v2, void* image, int64_t image_bytes, float* o1, float* o2,
+                                 float* lse, int N, int T, int D, int C1, int C2, void* stream);
+
 /* Backward of fmi_attention_fwd_f32 (P recomputed from lse): gv1/gv2 [N,T,C] overwritten, gq_zeroed [N,T,D] accumulated with
  * fp32 atomics (caller zeroes it), delta_scratch [N,T] workspace.  Supported: T % 32 == 0, D in {32,64}, (C1+C2)/32 in {4,8}. */
 int fmi_attention_bwd_f32(const float* q, const float* v1, const float* v2, const float* o1, const float* o2,
                           const float* go1, const float* go2, const float* lse, float* delta_scratch,
                           float* gv1, float* gv2, float* gq_zeroed, int N, int T, int D, int C1, int C2, void* stream);
+
+/* The same backward with the bf16 pieces of gO and Q cut ONCE per pass into a query-tile image (layout: csrc/attention.hip, AttQImg)
+ * that every workgroup streams into LDS by LDS-DMA, instead of every workgroup splitting every tile itself.  Same results as the
+ * key-block structure of fmi_attention_bwd_f32 (the same pieces in the same MFMA order; dQ meets through the same atomics).
+ *   fmi_attention_bwd_uses_pieces   1 where the library's shape dispatch takes this path (T % 128 == 0, (T/128) N >= 128, D in {32,64},
+ *                                   (C1+C2)/32 in {4,8}); callers take fmi_attention_bwd_f32 elsewhere
+ *   fmi_attention_bwd_image_bytes   size of the image workspace (0: the shape has none); the only place the layout arithmetic lives
+ *   fmi_attention_bwd_pieces_f32    cuts the image (workspace `image`, 16-byte aligned, image_bytes >= the size above) and runs the
+ *                                   backward; accepts every T % 128 == 0 of the supported D / C, also below the dispatch threshold */
+int fmi_attention_bwd_uses_pieces(int N, int T, int D, int C1, int C2);
+int fmi_attention_bwd_image_bytes(int N, int T, int D, int C1, int C2, int64_t* bytes);
+int fmi_attention_bwd_pieces_f32(const float* q, const float* v1, const float* v2, const float* o1, const float* o2,
+                                 const float* go1, const float* go2, const float* lse, float* delta_scratch, void* image,
+                                 int64_t image_bytes, float* gv1, float* gv2, float* gq_zeroed, int N, int T, int D, int C1, int C2,
+                                 void* stream);
 
 /* ------------------------------------------------------------------------
  * Bandwidth-class element-wise kernels (float4 vectorised).
