@@ -448,11 +448,18 @@ __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_x6_kernel(const float* __
   if (lh == 0 && lse) lse[row] = mref + logf(lsum);
 }
 
+// The forward's shape dispatch, in one place: waves per workgroup (each owns 32 queries).  Eight where whole 256-query workgroups still
+// fill the chip, two where even 128-query ones would not, else four.  Pure host arithmetic; the tests assert it per shape.
+extern "C" int fmi_attention_fwd_waves(int N, int T) {
+  if (T % 256 == 0 && (int64_t)(T / 256) * N >= 256) return 8;
+  return (int64_t)(T / 128) * N < 256 ? 2 : 4;
+}
+
 extern "C" int fmi_attention_fwd_f32(const float* q, const float* v1, const float* v2, float* o1, float* o2, float* lse,
                                      int N, int T, int D, int C1, int C2, void* stream) {
   if (!q || !v1 || !o1 || N <= 0 || T <= 0 || C1 <= 0 || C2 < 0 || (C2 > 0 && (!v2 || !o2))) return FMI_ERR_BAD_ARG;
   if (T % 128 != 0 || C1 % 32 != 0 || C2 % 32 != 0 || N > 65535) return FMI_ERR_UNSUPPORTED;
-  const int nw = (T % 256 == 0 && (int64_t)(T / 256) * N >= 256) ? 8 : ((int64_t)(T / 128) * N < 256 ? 2 : 4);
+  const int nw = fmi_attention_fwd_waves(N, T);
   if ((((uintptr_t)q | (uintptr_t)v1 | (uintptr_t)v2 | (uintptr_t)o1 | (uintptr_t)o2) & 15) != 0) return FMI_ERR_BAD_ARG;
   const int nct = (C1 + C2) / 32;
   const dim3 grid(T / (nw * 32), N), block(nw * 64);
@@ -496,9 +503,9 @@ extern "C" int fmi_attention_fwd_f32(const float* q, const float* v1, const floa
 //   dQ[q] += sum_key dS[q][key] q[key]   (query side)       dQ[key] += sum_q dS[q][key] q[q]   (key side; K = Q)
 // One workgroup owns a block of 32 KEYS (dV and the key-side dQ of those keys stay in registers for the whole kernel)
 // and streams all query tiles; P is recomputed from the saved log-sum-exp.  The four waves of the workgroup split the
-// REDUCTION dimensions of the two tile products that feed the softmax backward -- S over d, dP over the value
-// channels -- and exchange their 32x32 partial tiles through LDS, so no product is computed twice:
-//   per (32 queries x 32 keys) pair and wave:  S part 8 + dP part 32 + dV (own 64 channels) 32 + dK or dQ tile 16 MFMAs.
+// REDUCTION dimension of dP -- the value channels -- and exchange their 32x32 partial tiles through LDS; the score tile
+// is computed whole by every wave, on the bf16 pipe in the forward's arithmetic (see the comment at its pieces below):
+//   per (32 queries x 32 keys) pair and wave:  S 6 D/16 bf16 + dP part 32 + dV (own 64 channels) 32 + dK or dQ tile 16 MFMAs.
 // Scores are computed with the key on the lane, so P and dS are directly the B operands of the dV / dK products; only
 // the query-side product needs dS transposed, through a private 4 KB LDS tile.  The query-side dQ tiles are added with
 // fp32 atomics (whole 128-byte rows per wave instruction).
@@ -513,6 +520,7 @@ __global__ void __launch_bounds__(256, 1) attn_bwd_kernel(const float* __restric
   constexpr int LDV = CT + 1, LDQ = D + 1;
   constexpr int NQL = (8 * D) / 256 > 0 ? (8 * D) / 256 : 1, NVL = (8 * CT) / 256;
   constexpr int NDT = D / 32;  // 32-wide d tiles (1 or 2)
+  constexpr bool X6S = FMI_X6;  // score tile on the bf16 pipe, in the forward's arithmetic (below)
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Vj = smem;                   // [32][LDV]
   float* Kj = Vj + 32 * LDV;          // [32][LDQ]
@@ -604,27 +612,54 @@ __global__ void __launch_bounds__(256, 1) attn_bwd_kernel(const float* __restric
   gload(0);
   lstore();
   __syncthreads();
+  // The score tile is the forward's product, not a plain fp32 one: P = exp(S - lse) is exact to fp32 rounding only while S carries the
+  // rounding that lse saw.  |S| in the thousands has an ulp of 2^-12, and a d-split fp32 sum a few ulp off the forward's left a one-hot
+  // row's P, and with it that key's dV, 6e-4 off.  So every wave computes the WHOLE tile as attn_fwd_x6_kernel does -- bf16 pieces, one
+  // accumulator chained over d in steps of 16, the same six products per step -- which makes a key's score with itself (the entry that
+  // dominates a sharp row) the same bits as in the forward.  The resident keys' pieces stay in registers.
+  bf16x8_t kpc[D / 16][3];
+  if constexpr (X6S) {
+#pragma unroll
+    for (int kk = 0; kk < D / 16; ++kk) {
+      float f[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) f[j] = Kj[l31 * LDQ + 16 * kk + 8 * lh + j];
+      split3_bf16(f, kpc[kk]);
+    }
+  }
   for (int i0 = 0; i0 < T; i0 += 32) {
     gload(i0 + 32 < T ? i0 + 32 : i0);  // unconditional prefetch of the next query tile into registers
-    // ---- 1. partial score / dP tiles over this wave's slice of the reduction dimension; lane = key, registers = queries
+    // ---- 1. score tile (whole, per wave) and the partial dP tile over this wave's slice of the value channels; lane = key, registers = queries
     f32x16 sp, dp;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       sp[r] = 0.f;
       dp[r] = 0.f;
     }
+    if constexpr (X6S) {
 #pragma unroll
-    for (int s = 0; s < DW / 2; ++s)
-      sp = __builtin_amdgcn_mfma_f32_32x32x2f32(Qi[l31 * LDQ + dbase + 2 * s + lh], Kj[l31 * LDQ + dbase + 2 * s + lh], sp, 0, 0, 0);
+      for (int kk = 0; kk < D / 16; ++kk) {
+        float f[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] = Qi[l31 * LDQ + 16 * kk + 8 * lh + j];
+        bf16x8_t qpc[3];
+        split3_bf16(f, qpc);
+        sp = mfma_x6(qpc, kpc[kk], sp);
+      }
+    } else {
+#pragma unroll
+      for (int s = 0; s < DW / 2; ++s)
+        sp = __builtin_amdgcn_mfma_f32_32x32x2f32(Qi[l31 * LDQ + dbase + 2 * s + lh], Kj[l31 * LDQ + dbase + 2 * s + lh], sp, 0, 0, 0);
+    }
 #pragma unroll
     for (int s = 0; s < CW / 2; ++s)
       dp = __builtin_amdgcn_mfma_f32_32x32x2f32(dOi[l31 * LDV + cbase + 2 * s + lh], Vj[l31 * LDV + cbase + 2 * s + lh], dp, 0, 0, 0);
-    // ---- 2. exchange: every wave needs the full S and dP tiles
+    // ---- 2. exchange: every wave needs the full dP tile (and the full S tile where it was split over d)
     {
       float* ex = EX + wid * 2048 + lane;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        ex[r * 64] = sp[r];
+        if constexpr (!X6S) ex[r * 64] = sp[r];
         ex[1024 + r * 64] = dp[r];
       }
     }
@@ -634,10 +669,10 @@ __global__ void __launch_bounds__(256, 1) attn_bwd_kernel(const float* __restric
       float a = 0.f, b = 0.f;
 #pragma unroll
       for (int w = 0; w < 4; ++w) {
-        a += EX[w * 2048 + r * 64 + lane];
+        if constexpr (!X6S) a += EX[w * 2048 + r * 64 + lane];
         b += EX[w * 2048 + 1024 + r * 64 + lane];
       }
-      sp[r] = a;
+      if constexpr (!X6S) sp[r] = a;
       dp[r] = b;
     }
     // ---- 3. P and dS (register r of half lh is query (r&3) + 8*(r>>2) + 4*lh)
@@ -1485,26 +1520,34 @@ __global__ void __launch_bounds__(256) rowdot2_kernel(const float* __restrict__ 
   if (lane == 0) out[row] = s;
 }
 
+// The backward's shape dispatch, in one place: 2 = the key-block-per-wave structure (attn_bwd2*), where its T / 128 workgroups per image
+// fill the chip; 1 = the first structure (attn_bwd_kernel), which has 4x the workgroups.
+extern "C" int fmi_attention_bwd_structure(int N, int T) {
+  return (T % 128 == 0 && (int64_t)(T / 128) * N >= 128) ? 2 : 1;
+}
+
 extern "C" int fmi_attention_bwd_f32(const float* q, const float* v1, const float* v2, const float* o1, const float* o2,
                                      const float* go1, const float* go2, const float* lse, float* delta_scratch, float* gv1,
                                      float* gv2, float* gq_zeroed, int N, int T, int D, int C1, int C2, void* stream) {
   if (!q || !v1 || !o1 || !go1 || !lse || !delta_scratch || !gv1 || !gq_zeroed || N <= 0 || T <= 0 || C1 <= 0 || C2 < 0)
     return FMI_ERR_BAD_ARG;
   if (C2 > 0 && (!v2 || !o2 || !go2 || !gv2)) return FMI_ERR_BAD_ARG;
-  if (T % 32 != 0 || C1 % 32 != 0 || C2 % 32 != 0 || N > 65535) return FMI_ERR_UNSUPPORTED;
+  // T % 128 as the forward: the kernels take any T % 32 == 0, but P = exp(S - lse) needs the lse of fmi_attention_fwd_f32 (its rounding
+  // of the scores, see attn_bwd_kernel), and no forward produces one for the other T
+  if (T % 128 != 0 || C1 % 32 != 0 || C2 % 32 != 0 || N > 65535) return FMI_ERR_UNSUPPORTED;
+  const int nct = (C1 + C2) / 32;
+  if ((D != 32 && D != 64) || (nct != 4 && nct != 8)) return FMI_ERR_UNSUPPORTED;  // refused before the delta pass is launched
   if ((((uintptr_t)q | (uintptr_t)v1 | (uintptr_t)v2 | (uintptr_t)go1 | (uintptr_t)go2 | (uintptr_t)gv1 | (uintptr_t)gv2) & 15) != 0)
     return FMI_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   const int64_t rows = (int64_t)N * T;
   hipLaunchKernelGGL(rowdot2_kernel, dim3((unsigned)ceil_div64(rows, 4)), dim3(256), 0, st, go1, o1, C1, C2 ? go2 : nullptr, o2, C2,
                      delta_scratch, rows);
-  const int nct = (C1 + C2) / 32;
   const dim3 block(256);
   // reproducible mode: the query-side tiles of dQ receive one atomic contribution per KEY BLOCK; launching the key blocks one after the
   // other (stream order) fixes the order of those additions -- same kernels, grid.x = 1, key-block offset as an argument
   const bool det = fmi_det();
-  const bool small = (int64_t)(T / 128) * N < 128;  // short sequences: the first structure has 4x the workgroups
-  if (T % 128 == 0 && !small) {  // second structure: one key block per wave, fragments in registers, 4x fewer atomics
+  if (fmi_attention_bwd_structure(N, T) == 2) {  // one key block per wave, fragments in registers, 4x fewer atomics
     const dim3 grid2(T / 128, N);
     auto lds2 = [](int d, int ct) {
       return sizeof(float) * (size_t)(32 * (ct + 1) + 32 * (d + 1) + 64 + 4 * 32 * (d + 1) + 4 * 32 * 33 + 4 * (d / 32) * 16 * 64);
@@ -1580,7 +1623,7 @@ static bool att_pieces_shape(int T, int D, int C1, int C2) {
   return FMI_X6 && T > 0 && T % 128 == 0 && C1 > 0 && C2 >= 0 && C1 % 32 == 0 && C2 % 32 == 0 && (D == 32 || D == 64) && (nct == 4 || nct == 8);
 }
 extern "C" int fmi_attention_bwd_uses_pieces(int N, int T, int D, int C1, int C2) {
-  return N > 0 && N <= 65535 && att_pieces_shape(T, D, C1, C2) && (int64_t)(T / 128) * N >= 128;
+  return N > 0 && N <= 65535 && att_pieces_shape(T, D, C1, C2) && fmi_attention_bwd_structure(N, T) == 2;
 }
 // bytes of the backward's query-tile image (0: the shape has none)
 extern "C" int fmi_attention_bwd_image_bytes(int N, int T, int D, int C1, int C2, int64_t* bytes) {
@@ -1646,7 +1689,7 @@ extern "C" int fmi_attention_bwd_pieces_f32(const float* q, const float* v1, con
 // itself accepts every T % 256 == 0 of those D / C.
 // =====================================================================================================
 extern "C" int fmi_attention_fwd_uses_pieces(int N, int T, int D, int C1, int C2) {
-  return N > 0 && N <= 65535 && att_pieces_shape(T, D, C1, C2) && T % 256 == 0 && (int64_t)(T / 256) * N >= 256;
+  return N > 0 && N <= 65535 && att_pieces_shape(T, D, C1, C2) && fmi_attention_fwd_waves(N, T) == 8;
 }
 extern "C" int fmi_attention_fwd_image_bytes(int N, int T, int D, int C1, int C2, int64_t* bytes) {
   if (!bytes || N <= 0) return FMI_ERR_BAD_ARG;

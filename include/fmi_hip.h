@@ -335,6 +335,13 @@ int fmi_softmax_rows_bwd_f32(const float* p, const float* dp, float* ds, int64_t
 int fmi_attention_fwd_f32(const float* q, const float* v1, const float* v2, float* o1, float* o2, float* lse,
                           int N, int T, int D, int C1, int C2, void* stream);
 
+/* The shape dispatch of the two fused attention passes (pure host arithmetic; the entry points call these themselves):
+ *   fmi_attention_fwd_waves      waves per forward workgroup, each owning 32 queries: 8 if T % 256 == 0 and (T/256) N >= 256,
+ *                                else 2 if (T/128) N < 256, else 4
+ *   fmi_attention_bwd_structure  2 (one key block per wave) if T % 128 == 0 and (T/128) N >= 128, else 1 (one key block per workgroup) */
+int fmi_attention_fwd_waves(int N, int T);
+int fmi_attention_bwd_structure(int N, int T);
+
 /* The same forward with the bf16 pieces of K (= q) and V cut ONCE per pass into a key-tile image (layout: csrc/attention.hip, AttKImg)
  * that every workgroup streams into LDS by LDS-DMA; bit-identical results (the same pieces in the same MFMA order).
  *   fmi_attention_fwd_uses_pieces   1 where the library's shape dispatch takes this path (T % 256 == 0, (T/256) N >= 256, D in {32,64},
@@ -348,7 +355,9 @@ int fmi_attention_fwd_pieces_f32(const float* q, const float* v1, const float* v
                                  float* lse, int N, int T, int D, int C1, int C2, void* stream);
 
 /* Backward of fmi_attention_fwd_f32 (P recomputed from lse): gv1/gv2 [N,T,C] overwritten, gq_zeroed [N,T,D] accumulated with
- * fp32 atomics (caller zeroes it), delta_scratch [N,T] workspace.  Supported: T % 32 == 0, D in {32,64}, (C1+C2)/32 in {4,8}. */
+ * fp32 atomics (caller zeroes it), delta_scratch [N,T] workspace.  Supported: T % 128 == 0 (the forward's: lse must be the one
+ * fmi_attention_fwd_f32 wrote, P = exp(S - lse) relies on its rounding of the scores), D in {32,64}, (C1+C2)/32 in {4,8}; else
+ * FMI_ERR_UNSUPPORTED, before anything is launched. */
 int fmi_attention_bwd_f32(const float* q, const float* v1, const float* v2, const float* o1, const float* o2,
                           const float* go1, const float* go2, const float* lse, float* delta_scratch,
                           float* gv1, float* gv2, float* gq_zeroed, int N, int T, int D, int C1, int C2, void* stream);
