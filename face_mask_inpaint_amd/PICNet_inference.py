@@ -18,6 +18,9 @@ from .modules.model import ReferenceFill, scale_img
 from .modules.pluralistic_model import base_function
 
 
+MASK_DETECTOR_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
+
+
 def get_args(argv=None):
     """the reference's flags for the model side (PICNet_inference.py:18-70); data flags default to synthetic input"""
     p = argparse.ArgumentParser()
@@ -35,6 +38,9 @@ def get_args(argv=None):
     p.add_argument("--use_best_reference", action="store_true")
     p.add_argument("--save_src_mask", action="store_true")
     p.add_argument("--num_batches", type=int, default=2, help="synthetic mode: batches to run")
+    p.add_argument("--out_dir", type=str, default=None, help="this build's extra: where metrics.csv goes (not written when absent)")
+    p.add_argument("--mask_detector_dtype", type=str, default="fp32", choices=("fp32", "bf16"),
+                   help="this build's extra: activation type of the mask detector's UNet body (bf16 needs H and W to be multiples of 16)")
     p.add_argument("--encoder_type", type=str, default="pluralistic")
     p.add_argument("--encoder_ngf", type=int, default=32)
     p.add_argument("--encoder_z_nc", type=int, default=128)
@@ -97,7 +103,10 @@ def evaluate(gt_img, gen_img, ssim_func, ms_ssim_func=None):
 
 
 def build(args, device):
-    mask_detector = MaskDetector(n_channels=3, bilinear=True)
+    dt = getattr(args, "mask_detector_dtype", "fp32")
+    if dt not in MASK_DETECTOR_DTYPES:
+        raise FF.FmiError(f"mask_detector_dtype must be one of {sorted(MASK_DETECTOR_DTYPES)}, got {dt!r}")
+    mask_detector = MaskDetector(n_channels=3, bilinear=True, compute_dtype=MASK_DETECTOR_DTYPES[dt])
     if args.mask_detector_path:
         mask_detector.load_state_dict(torch.load(args.mask_detector_path, map_location="cpu", weights_only=True))
     base_function._freeze(mask_detector)
@@ -143,6 +152,15 @@ def main(argv=None):
     mean_ssim = sum(r[0] for r in results) / max(len(results), 1)
     mean_ms = sum(r[1] for r in results) / max(len(results), 1)
     print({"ssim": mean_ssim, "ms_ssim": mean_ms, "batches": len(results), "image": tuple(gen_images.shape)})
+    out_dir = getattr(args, "out_dir", None)
+    if out_dir:
+        import csv
+
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "metrics.csv"), "w", newline="") as fh:
+            w = csv.writer(fh)
+            w.writerow(["ssim", "ms_ssim"])
+            w.writerow([repr(float(mean_ssim)), repr(float(mean_ms))])
     return mean_ssim
 
 

@@ -103,6 +103,13 @@ SIGNATURES = {
     "fmi_avgpool_f32": [vp, vp, i32, i32, i32, i32, i32, vp],
     "fmi_avgpool_bwd_f32": [vp, vp, i32, i32, i32, i32, i32, vp],
     "fmi_maxpool2_f32": [vp, vp, i32, i32, i32, i32, vp],
+    "fmi_maxpool2_bf16": [vp, vp, i32, i32, i32, i32, vp],
+    "fmi_maxpool2_bwd_bf16": [vp, vp, vp, i32, i32, i32, i32, vp],
+    "fmi_up2_cat_bf16": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+    "fmi_up2_cat_bwd_bf16": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+    "fmi_head1x1_bf16": [vp, vp, vp, vp, i64, i32, i32, vp],
+    "fmi_head1x1_argmax_bf16": [vp, vp, vp, vp, i64, i32, i32, vp],
+    "fmi_head1x1_bwd_bf16": [vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp],
     "fmi_adaptive_avgpool_f32": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "fmi_adaptive_avgpool_bwd_f32": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "fmi_maxpool_f32": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
@@ -135,6 +142,7 @@ SIGNATURES = {
     "fmi_resize_bilinear_bwd_f32": [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp],
     "fmi_instnorm_stats_f32": [vp, vp, vp, i32, i32, i32, f32, vp, i64, vp],
     "fmi_batchnorm_running_update_f32": [vp, vp, vp, vp, vp, i32, i64, f32, f32, vp],
+    "fmi_batchnorm_running_update_offset_f32": [vp, vp, vp, vp, vp, vp, i32, i64, f32, f32, vp],
     "fmi_instnorm_apply_f32": [vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
     "fmi_instnorm_bwd_reduce_f32": [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, i64, vp],
     "fmi_instnorm_bwd_apply_f32": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],

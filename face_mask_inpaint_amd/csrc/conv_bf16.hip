@@ -390,7 +390,10 @@ static int launch_conv_bf16(ConvSetB& set, int nph, int N, bf16_t* y, float* ws,
   auto wgs = [&](int bm, int bn) { return ceil_div64(Mmax, bm) * ceil_div64(N, bn) * nph; };
   const int tile_dbg = g_bf16_tile_mode;
   // the eight-phase kernel (conv_bf16_8ph.h): whole 64-deep reduction tiles, 8-byte output stores, no split reduction
-  bool ok8 = BK == 64 && tile_dbg != 1 && tile_dbg != 2 && N % 4 == 0 && N > 64;
+  // (narrower outputs reach it only for its fused output stage: the UNet's 64-channel layers, half of the 128-column tile masked off.
+  // With that stage on this kernel is taken whatever the tile count -- it is the only one that has the stage -- so a deep, small map at
+  // a small batch runs on a handful of workgroups: a throughput compromise of the one-launch eval form, not a tuned choice.)
+  bool ok8 = BK == 64 && tile_dbg != 1 && tile_dbg != 2 && N % 4 == 0 && (N > 64 || (act && act->on));
   for (int p = 0; p < nph && ok8; ++p)
     ok8 = set.ph[p].K % 64 == 0 && set.ph[p].la.g.ntaps() <= 32 && set.ph[p].ep.vec && (!set.ph[p].ep.colscale || (((uintptr_t)set.ph[p].ep.colscale & 15) == 0));
   if (act && act->on && !ok8) return FMI_ERR_UNSUPPORTED;
@@ -487,7 +490,7 @@ extern "C" int fmi_conv2d_fwd_bf16(const fmi_conv_desc* d, const uint16_t* x, co
 /* y = lrelu(conv(x, W) * colscale[n][k] + nw[0] * noise[n][oy][ox] + bias[k], slope) * gain: a StyledConv without upsampling in one
  * launch (stylegan2/model.py:241-279 ModulatedConv2d on pre-scaled activations, :250-252 demodulation, :282-294 NoiseInjection,
  * op/fused_act.py:30-37 FusedLeakyReLU) -- the output stage of the eight-phase kernel (csrc/conv_bf16_8ph.h).  colscale / noise / bias
- * may be NULL; FMI_ERR_UNSUPPORTED where that kernel does not apply (C % 64, K % 4 and K > 64, 8-byte aligned y, 16-byte colscale / bias). */
+ * may be NULL; FMI_ERR_UNSUPPORTED where that kernel does not apply (C % 64, K % 4, 8-byte aligned y, 16-byte colscale / bias). */
 extern "C" int fmi_conv2d_fwd_act_bf16(const fmi_conv_desc* d, const uint16_t* x, const uint16_t* wnk, const float* colscale, const float* noise,
                                        const float* nw, const float* bias, float slope, float gain, uint16_t* y, void* stream) {
   if (noise && !nw) return FMI_ERR_BAD_ARG;

@@ -399,15 +399,19 @@ extern "C" int fmi_instnorm_bwd_apply_bf16(const uint16_t* x, const uint16_t* gy
 
 // nn.BatchNorm2d running-statistics bookkeeping (torch/nn/modules/batchnorm.py semantics: momentum average of the batch mean and of
 // the UNBIASED batch variance, num_batches_tracked += 1) from the (mean, rstd) pairs the statistics pass produced: one launch per
-// BatchNorm instead of nine [C]-sized ATen kernels (104 BatchNorms per pSp step).
+// BatchNorm instead of nine [C]-sized ATen kernels (104 BatchNorms per pSp step).  mean_offset (may be NULL): a per-channel constant that
+// was left out of the normalised tensor because it cancels there (the bias of the convolution in front, bf16 UNet body): the running
+// mean is that of the tensor WITH it, as the path that applies it stores.
 __global__ void __launch_bounds__(256) bn_running_update_kernel(const float* __restrict__ stats, const double* __restrict__ sums,
-                                                                float* __restrict__ rmean, float* __restrict__ rvar,
+                                                                const float* __restrict__ mean_offset, float* __restrict__ rmean, float* __restrict__ rvar,
                                                                 int64_t* __restrict__ nbt, int C, float unbias, double count, float eps,
                                                                 float momentum) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c == 0 && nbt) nbt[0] += 1;
   if (c >= C) return;
-  const float mean = stats[2 * c], rstd = stats[2 * c + 1];
+  float mean = stats[2 * c];
+  const float rstd = stats[2 * c + 1];
+  if (mean_offset) mean = __fadd_rn(mean, mean_offset[c]);
   float var;
   if (sums) {  // the fp64 (sum, sum of squares) of the statistics pass: no 1 / rstd^2 - eps cancellation when var << eps
     const double m = sums[2 * c] / count;
@@ -419,12 +423,22 @@ __global__ void __launch_bounds__(256) bn_running_update_kernel(const float* __r
   rmean[c] = __fadd_rn(__fmul_rn(rmean[c], 1.f - momentum), __fmul_rn(momentum, mean));
   rvar[c] = __fadd_rn(__fmul_rn(rvar[c], 1.f - momentum), __fmul_rn(momentum, var));
 }
+static int running_update_impl(const float* stats, const double* sums, const float* mean_offset, float* running_mean, float* running_var,
+                               int64_t* num_batches_tracked, int C, int64_t count, float eps, float momentum, void* stream) {
+  if (!stats || !running_mean || !running_var || C <= 0 || count <= 0) return FMI_ERR_BAD_ARG;
+  const float unbias = (float)((double)count / (double)(count > 1 ? count - 1 : 1));
+  hipLaunchKernelGGL(bn_running_update_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, stats, sums, mean_offset, running_mean,
+                     running_var, num_batches_tracked, C, unbias, (double)count, eps, momentum);
+  return fmi_launch_status();
+}
 extern "C" int fmi_batchnorm_running_update_f32(const float* stats, const double* sums, float* running_mean, float* running_var,
                                                 int64_t* num_batches_tracked, int C, int64_t count, float eps, float momentum,
                                                 void* stream) {
-  if (!stats || !running_mean || !running_var || C <= 0 || count <= 0) return FMI_ERR_BAD_ARG;
-  const float unbias = (float)((double)count / (double)(count > 1 ? count - 1 : 1));
-  hipLaunchKernelGGL(bn_running_update_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, stats, sums, running_mean, running_var,
-                     num_batches_tracked, C, unbias, (double)count, eps, momentum);
-  return fmi_launch_status();
+  return running_update_impl(stats, sums, nullptr, running_mean, running_var, num_batches_tracked, C, count, eps, momentum, stream);
+}
+extern "C" int fmi_batchnorm_running_update_offset_f32(const float* stats, const double* sums, const float* mean_offset, float* running_mean,
+                                                       float* running_var, int64_t* num_batches_tracked, int C, int64_t count, float eps,
+                                                       float momentum, void* stream) {
+  if (!mean_offset) return FMI_ERR_BAD_ARG;
+  return running_update_impl(stats, sums, mean_offset, running_mean, running_var, num_batches_tracked, C, count, eps, momentum, stream);
 }

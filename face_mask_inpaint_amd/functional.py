@@ -1087,6 +1087,10 @@ class _MaxPool(torch.autograd.Function):
 
 def max_pool(x, k, stride):
     """nn.MaxPool2d(k, stride) (no padding, floor mode) on NHWC"""
+    if x.dtype == BF16:
+        if k != 2 or stride != 2:
+            raise FmiError("bf16 max pooling exists for k = 2, stride = 2 only")
+        return max_pool2(x)
     if k == 2 and stride == 2 and x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0:
         return max_pool2(x)
     return _MaxPool.apply(x, int(k), int(stride))
@@ -1171,8 +1175,165 @@ class _MaxPool2(torch.autograd.Function):
         return gx
 
 
+class _MaxPool2BF16(torch.autograd.Function):
+    """2 x 2 stride-2 max pooling on bf16 NHWC (H, W even); the gradient goes to the first maximum of the window"""
+
+    @staticmethod
+    def forward(ctx, x):
+        _chk(x, dtype=BF16)
+        n, h, w, c = x.shape
+        if h % 2 or w % 2:
+            raise FmiError(f"bf16 max pooling needs even H and W, got {h} x {w}")
+        y = torch.empty((n, h // 2, w // 2, c), device=x.device, dtype=BF16)
+        _L().maxpool2_bf16(_p(x), _p(y), n, h, w, c, _st())
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        n, h, w, c = x.shape
+        gx = torch.empty_like(x)
+        _L().maxpool2_bwd_bf16(_p(x), _p(g.contiguous()), _p(gx), n, h, w, c, _st())
+        return gx
+
+
 def max_pool2(x):
+    if x.dtype == BF16:
+        return _MaxPool2BF16.apply(x)
     return _MaxPool2.apply(x)
+
+
+class _Up2CatBF16(torch.autograd.Function):
+    """Up of the UNet (unet_parts.py:45-72) on bf16 NHWC in one pass each way: bilinear x2 (align_corners=True) of x1, zero border up
+    to the skip's size, cat([skip, up], C)"""
+
+    @staticmethod
+    def forward(ctx, x1, skip):
+        _chk(x1, skip, dtype=BF16)
+        n, h, w, c1 = x1.shape
+        n2, H, W, c2 = skip.shape
+        if n2 != n or H < 2 * h or W < 2 * w:
+            raise FmiError(f"up2_cat: x1 {tuple(x1.shape)} does not fit under the skip {tuple(skip.shape)}")
+        y = torch.empty((n, H, W, c2 + c1), device=x1.device, dtype=BF16)
+        _L().up2_cat_bf16(_p(x1), _p(skip), _p(y), n, h, w, c1, H, W, c2, _st())
+        ctx.cfg = (n, h, w, c1, H, W, c2)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        n, h, w, c1, H, W, c2 = ctx.cfg
+        g = g.contiguous()
+        gx1 = torch.empty((n, h, w, c1), device=g.device, dtype=BF16)
+        gskip = torch.empty((n, H, W, c2), device=g.device, dtype=BF16)
+        _L().up2_cat_bwd_bf16(_p(g), _p(gskip), _p(gx1), n, h, w, c1, H, W, c2, _st())
+        return gx1, gskip
+
+
+def up2_cat(x1, skip):
+    """cat([skip, pad(upsample2(x1))], C) on bf16 NHWC tensors -> [N, H, W, C2 + C1]"""
+    return _Up2CatBF16.apply(x1, skip)
+
+
+_HEAD_ROWS = 512  # partial rows of fmi_head1x1_bwd_bf16 (the cap in csrc/unet_bf16.hip)
+
+
+def _head_args(x, w, b):
+    _chk(x, dtype=BF16)
+    _chk(w, b)
+    k, c = w.shape[0], x.shape[-1]
+    if w.numel() != k * c or b.numel() != k:
+        raise FmiError(f"head1x1: weight {tuple(w.shape)} / bias {tuple(b.shape)} do not match {c} input channels")
+    return k, c
+
+
+class _Head1x1BF16(torch.autograd.Function):
+    """OutConv of the UNet: bf16 activations [.., C] times the fp32 1 x 1 weight [K, C, 1, 1] plus bias -> fp32 logits [.., K]"""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        k, c = _head_args(x, w, b)
+        y = torch.empty(x.shape[:-1] + (k,), device=x.device, dtype=torch.float32)
+        _L().head1x1_bf16(_p(x), _p(w), _p(b), _p(y), x.numel() // c, c, k, _st())
+        ctx.save_for_backward(x, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        k, c = w.shape[0], x.shape[-1]
+        g = g.contiguous()
+        gx = torch.empty_like(x)
+        gw = torch.empty_like(w)
+        gb = torch.empty(k, device=x.device, dtype=torch.float32)
+        ws = torch.empty(_HEAD_ROWS * (k * c + k), device=x.device, dtype=torch.float64)
+        _L().head1x1_bwd_bf16(_p(g), _p(x), _p(w), _p(gx), _p(gw), _p(gb), C.c_void_p(ws.data_ptr()), ws.numel(), x.numel() // c, c, k, _st())
+        return gx, gw, gb
+
+
+def head1x1(x, w, b):
+    return _Head1x1BF16.apply(x, w.contiguous(), b.contiguous())
+
+
+def head1x1_argmax(x, w, b):
+    """float {0, .., K-1} mask [N, H, W] = argmax_channels(head1x1(x, w, b)) without storing the logits (first maximum wins); no gradient"""
+    x, w, b = x.detach(), w.detach().contiguous(), b.detach().contiguous()
+    k, c = _head_args(x, w, b)
+    out = torch.empty(x.shape[:-1], device=x.device, dtype=torch.float32)
+    _L().head1x1_argmax_bf16(_p(x), _p(w), _p(b), _p(out), out.numel(), c, k, _st())
+    return out
+
+
+class _ZeroGradOf(torch.autograd.Function):
+    """y unchanged; ``param`` receives an exact zero gradient.  A convolution bias in front of a training-mode BatchNorm cancels in the
+    mean subtraction: it is not applied, and its gradient is this zero tensor (not None), so the optimiser keeps the state it would have
+    on the path that does apply it."""
+
+    @staticmethod
+    def forward(ctx, y, param):
+        ctx.save_for_backward(param)
+        return y.view_as(y)
+
+    @staticmethod
+    def backward(ctx, g):
+        (param,) = ctx.saved_tensors
+        return g, (torch.zeros_like(param) if ctx.needs_input_grad[1] else None)
+
+
+def zero_grad_of(y, param):
+    return _ZeroGradOf.apply(y, param)
+
+
+def conv_bn_relu_eval_bf16(x, pw: PackedWeight, conv_bias, bn, pad=1):
+    """relu(BatchNorm2d(eval)(conv(x) + conv_bias)) on bf16 NHWC in ONE launch: the running statistics and both biases fold into the
+    per-column scale and bias of fmi_conv2d_fwd_act_bf16's output stage (slope 0, gain 1, no noise).  Inference form: gradients off."""
+    if torch.is_grad_enabled():
+        raise FmiError("conv_bn_relu_eval_bf16 is the inference form of the bf16 UNet body (eval-mode BatchNorm): gradients must be off "
+                       "(torch.no_grad()); train-mode BatchNorm is the path that differentiates")
+    _chk(x, dtype=BF16)
+    n, h, w, c = x.shape
+    k = pw.wf.shape[2]
+    ts = (bn.weight, bn.bias, bn.running_var, bn.running_mean) + ((conv_bias,) if conv_bias is not None else ())
+    # the folded constants of a FROZEN network are kept while none of the tensors changes (storage + version counter), as
+    # helpers.batch_norm keeps its own; trainable parameters are written by the fused optimiser through raw pointers: folded every call.
+    # The running-statistics update writes through raw pointers too: helpers.batch_norm drops the kept constants on such a pass.
+    key = None if any(t.requires_grad for t in ts) else tuple((t.data_ptr(), t._version) for t in ts) + (bn.eps, n)
+    kept = getattr(bn, "_fmi_fold", None)
+    if key is not None and kept is not None and kept[0] == key:
+        colscale, bias = kept[1], kept[2]
+    else:
+        scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)  # [K]-sized torch bookkeeping
+        bias = (bn.bias - bn.running_mean * scale if conv_bias is None else bn.bias + (conv_bias - bn.running_mean) * scale).contiguous()
+        colscale = scale.unsqueeze(0).expand(n, k).contiguous()
+        if key is not None:
+            object.__setattr__(bn, "_fmi_fold", (key, colscale, bias))
+    _chk(colscale, bias)
+    dsc, oh, ow = conv_desc(n, h, w, c, k, pw.kh, pw.kw, 1, pad)
+    y = torch.empty((n, oh, ow, k), device=x.device, dtype=BF16)
+    wnk = _pack_bf16(pw.wf)
+    with _prof(f"conv_fwd_bf16|{n}x{h}x{w} {c}->{k} k{pw.kh}s1 +bn", 2.0 * n * oh * ow * k * c * pw.kh * pw.kw):
+        _L().conv2d_fwd_act_bf16(C.byref(dsc), _p(x), _p(wnk), _p(colscale), None, None, _p(bias), 0.0, 1.0, _p(y), _st())
+    return y
 
 
 class _Resize(torch.autograd.Function):
@@ -2489,8 +2650,9 @@ class _BatchNormTrain(torch.autograd.Function):
     Returns (y, stats[G][C][2] = (mean, rstd), sums[G][C][2] = fp64 (sum, sum of squares))."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, eps, groups=1, passthrough=False):
-        """passthrough: x itself is returned as a fourth output for x's OTHER consumer (the identity shortcut of an IR block); its
+    def forward(ctx, x, gamma, beta, eps, groups=1, passthrough=False, slope=1.0):
+        """slope != 1: lrelu(BatchNorm(x), slope) in the same pass each way (0 = ReLU), as instance_norm_act does.
+        passthrough: x itself is returned as a fourth output for x's OTHER consumer (the identity shortcut of an IR block); its
         gradient then arrives here and joins gx inside the backward kernel instead of in a separate accumulation pass"""
         b16 = x.dtype == BF16  # bf16 activations (IR-SE50 body of the pSp encoder): fp32 statistics / parameters, bf16 in and out
         _chk(x, dtype=x.dtype)
@@ -2505,9 +2667,9 @@ class _BatchNormTrain(torch.autograd.Function):
         (lib.instnorm_stats_bf16 if b16 else lib.instnorm_stats_f32)(_p(x), C.c_void_p(sums.data_ptr()), _p(stats), groups, rows, c, eps,
                                                                       C.c_void_p(ws.data_ptr()), ws.numel(), _st())
         y = torch.empty_like(x)
-        (lib.instnorm_apply_bf16 if b16 else lib.instnorm_apply_f32)(_p(x), _p(stats), _p(gamma), _p(beta), _p(y), groups, rows, c, 1.0, _st())
+        (lib.instnorm_apply_bf16 if b16 else lib.instnorm_apply_f32)(_p(x), _p(stats), _p(gamma), _p(beta), _p(y), groups, rows, c, slope, _st())
         ctx.save_for_backward(x, stats, gamma, beta)
-        ctx.groups = groups
+        ctx.groups, ctx.slope = groups, slope
         ctx.mark_non_differentiable(stats, sums)
         ctx.set_materialize_grads(False)  # no zero-filled "gradient" for the statistics output (one fill launch per BatchNorm and step)
         if passthrough:
@@ -2519,7 +2681,7 @@ class _BatchNormTrain(torch.autograd.Function):
         lib = _L()
         x, stats, gamma, beta = ctx.saved_tensors
         if g is None:  # only the pass-through branch carried a gradient
-            return gpass, None, None, None, None, None
+            return gpass, None, None, None, None, None, None
         c = x.shape[-1]
         groups = ctx.groups
         rows = x.numel() // c // groups
@@ -2527,36 +2689,45 @@ class _BatchNormTrain(torch.autograd.Function):
         red, ws = _norm_ws(x.device, groups, c)
         gx, dg, db = torch.empty_like(x), _zeros_like(gamma), _zeros_like(beta)
         if x.dtype == BF16:
-            lib.instnorm_bwd_reduce_bf16(_p(x), _p(g), _p(stats), _p(gamma), _p(beta), C.c_void_p(red.data_ptr()), groups, rows, c, 1.0,
+            lib.instnorm_bwd_reduce_bf16(_p(x), _p(g), _p(stats), _p(gamma), _p(beta), C.c_void_p(red.data_ptr()), groups, rows, c, ctx.slope,
                                          C.c_void_p(ws.data_ptr()), ws.numel(), _st())
             lib.instnorm_bwd_apply_bf16(_p(x), _p(g), _p(stats), _p(gamma), _p(beta), C.c_void_p(red.data_ptr()),
-                                        _p(gpass.contiguous()) if gpass is not None else None, _p(gx), _p(dg), _p(db), groups, rows, c, 1.0, _st())
-            return gx, dg, db, None, None, None
-        lib.instnorm_bwd_reduce_f32(_p(x), _p(g), _p(stats), _p(gamma), _p(beta), C.c_void_p(red.data_ptr()), groups, rows, c, 1.0,
+                                        _p(gpass.contiguous()) if gpass is not None else None, _p(gx), _p(dg), _p(db), groups, rows, c, ctx.slope, _st())
+            return gx, dg, db, None, None, None, None
+        lib.instnorm_bwd_reduce_f32(_p(x), _p(g), _p(stats), _p(gamma), _p(beta), C.c_void_p(red.data_ptr()), groups, rows, c, ctx.slope,
                                     C.c_void_p(ws.data_ptr()), ws.numel(), _st())
         if gpass is not None:
             lib.instnorm_bwd_apply_add_f32(_p(x), _p(g), _p(stats), _p(gamma), _p(beta), C.c_void_p(red.data_ptr()), _p(gpass.contiguous()),
-                                           _p(gx), _p(dg), _p(db), groups, rows, c, 1.0, _st())
+                                           _p(gx), _p(dg), _p(db), groups, rows, c, ctx.slope, _st())
         else:
             lib.instnorm_bwd_apply_f32(_p(x), _p(g), _p(stats), _p(gamma), _p(beta), C.c_void_p(red.data_ptr()), _p(gx), _p(dg), _p(db),
-                                       groups, rows, c, 1.0, _st())
-        return gx, dg, db, None, None, None
+                                       groups, rows, c, ctx.slope, _st())
+        return gx, dg, db, None, None, None, None
 
 
-def batch_norm_running_update(stats, running_mean, running_var, num_batches_tracked, count, eps, momentum, sums=None):
+def batch_norm_running_update(stats, running_mean, running_var, num_batches_tracked, count, eps, momentum, sums=None, mean_offset=None):
     """in-place momentum update of the BatchNorm2d buffers from stats [1, C, 2] = (mean, rstd) of the batch (one launch); sums = the
-    fp64 (sum, sum of squares) of the same pass, from which the variance is taken when given"""
-    _chk(stats, running_mean, running_var)
+    fp64 (sum, sum of squares) of the same pass, from which the variance is taken when given; mean_offset [C] = a per-channel constant
+    that was left out of the normalised tensor because it cancels there (a convolution bias): the running mean includes it"""
+    _chk(stats, running_mean, running_var, mean_offset)
     _chk(sums, dtype=torch.float64)
     if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64 or not num_batches_tracked.is_cuda):
         raise FmiError("num_batches_tracked must be an int64 device tensor")
     nbt = C.c_void_p(num_batches_tracked.data_ptr()) if num_batches_tracked is not None else None
+    if mean_offset is not None:
+        if mean_offset.numel() != running_mean.numel():
+            raise FmiError("mean_offset must have one entry per channel")
+        _L().batchnorm_running_update_offset_f32(_p(stats), C.c_void_p(sums.data_ptr()) if sums is not None else None, _p(mean_offset.detach()),
+                                                 _p(running_mean), _p(running_var), nbt, running_mean.numel(), int(count), float(eps),
+                                                 float(momentum), _st())
+        return
     _L().batchnorm_running_update_f32(_p(stats), C.c_void_p(sums.data_ptr()) if sums is not None else None, _p(running_mean),
                                       _p(running_var), nbt, running_mean.numel(), int(count), float(eps), float(momentum), _st())
 
 
-def batch_norm_train(x, gamma, beta, eps=1e-5, groups=1, passthrough=False):
-    return _BatchNormTrain.apply(x, gamma, beta, float(eps), int(groups), bool(passthrough))
+def batch_norm_train(x, gamma, beta, eps=1e-5, groups=1, passthrough=False, slope=1.0):
+    """slope: lrelu(BatchNorm(x), slope) as one pass each way (1 = no activation, 0 = ReLU)"""
+    return _BatchNormTrain.apply(x, gamma, beta, float(eps), int(groups), bool(passthrough), float(slope))
 
 
 class _SplitBatch(torch.autograd.Function):

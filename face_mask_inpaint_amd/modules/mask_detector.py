@@ -11,9 +11,11 @@ from .unet.unet_model import UNet
 
 
 class MaskDetector(nn.Module):
-    def __init__(self, n_channels, bilinear=True, threshold=0.5):
+    def __init__(self, n_channels, bilinear=True, threshold=0.5, compute_dtype=torch.float32):
+        """compute_dtype=torch.bfloat16: the UNet body on the bf16 kernels (see UNet); inputs, logits, parameters and the state_dict stay fp32"""
         super().__init__()
-        self.model = UNet(n_channels, 2, bilinear=bilinear)
+        self.model = UNet(n_channels, 2, bilinear=bilinear, compute_dtype=compute_dtype)
+        self.compute_dtype = compute_dtype
         self.threshold = threshold
         self.n_channels = n_channels
         self.bilinear = bilinear
@@ -30,4 +32,4 @@ class MaskDetector(nn.Module):
     @torch.no_grad()
     def predict_mask(self, image):
         """[N, H, W] float {0, 1} = forward(image, 'train').argmax(1).float() -- logits stay NHWC, the argmax is bit exact"""
-        return FF.argmax_channels(self.model.nhwc(FF.to_nhwc(image)))
+        return self.model.argmax_nhwc(FF.to_nhwc(image))

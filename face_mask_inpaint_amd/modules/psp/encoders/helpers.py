@@ -42,27 +42,34 @@ _FUSE = __import__("os").environ.get("FMI_IRSE_FUSE_OFF") is None  # debug: A/B 
 _GATE_PASS = __import__("os").environ.get("FMI_IRSE_GATE_PASS", "1") != "0"  # debug: A/B of the SE input's one-pass gradient join (fp32)
 
 
-def batch_norm(bn: BatchNorm2d, x, passthrough=False):
+def batch_norm(bn: BatchNorm2d, x, passthrough=False, slope=1.0, mean_offset=None):
     """nn.BatchNorm2d forward on NHWC with torch's training / eval semantics.  ``passthrough``: returns (y, x') where x' is x for its
-    other consumer; in training mode that consumer's gradient is added inside the BatchNorm backward kernel (one pass fewer)"""
+    other consumer; in training mode that consumer's gradient is added inside the BatchNorm backward kernel (one pass fewer).
+    ``slope`` != 1 (batch statistics only): lrelu(BatchNorm(x), slope) in the same pass each way.  ``mean_offset`` [C] (batch statistics
+    only): a per-channel constant the caller left out of x because it cancels in the mean subtraction (the bias of the convolution in
+    front); the running mean is updated as if x carried it"""
     if bn.training or not bn.track_running_stats:
         groups = BN_GROUPS[0]
         if passthrough:
-            y, stats, sums, xp = FF.batch_norm_train(x, bn.weight, bn.bias, bn.eps, groups, True)
+            y, stats, sums, xp = FF.batch_norm_train(x, bn.weight, bn.bias, bn.eps, groups, True, slope)
         else:
-            y, stats, sums = FF.batch_norm_train(x, bn.weight, bn.bias, bn.eps, groups)
+            y, stats, sums = FF.batch_norm_train(x, bn.weight, bn.bias, bn.eps, groups, False, slope)
             xp = None
         y = (y, xp) if passthrough else y
         if bn.training and bn.track_running_stats:
+            for kept in ("_fmi_affine", "_fmi_fold"):  # constants folded from the running statistics: the update below writes the buffers
+                if getattr(bn, kept, None) is not None:  # through raw pointers, which their version counters do not see
+                    object.__setattr__(bn, kept, None)
             cnt = x.numel() // x.shape[-1] // groups
             for g in range(groups):  # the running statistics see the parts one after the other, as the reference's separate calls do
                 st, sm = stats[g:g + 1], sums[g:g + 1]
                 if bn.momentum is not None and bn.running_mean.is_contiguous() and bn.running_var.is_contiguous():
                     with torch.no_grad():  # one launch: momentum update of both buffers and the batch counter
-                        FF.batch_norm_running_update(st, bn.running_mean, bn.running_var, bn.num_batches_tracked, cnt, bn.eps, bn.momentum, sm)
+                        FF.batch_norm_running_update(st, bn.running_mean, bn.running_var, bn.num_batches_tracked, cnt, bn.eps, bn.momentum, sm,
+                                                     mean_offset)
                     continue
                 with torch.no_grad():  # cumulative moving average (momentum=None): [C]-sized torch bookkeeping
-                    mean = st[0, :, 0]
+                    mean = st[0, :, 0] if mean_offset is None else st[0, :, 0] + mean_offset
                     m64 = sm[0, :, 0] / cnt
                     var = ((sm[0, :, 1] / cnt - m64 * m64).clamp_min(0) * (cnt / max(cnt - 1, 1))).float()
                     m = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked + 1)
@@ -70,6 +77,8 @@ def batch_norm(bn: BatchNorm2d, x, passthrough=False):
                     bn.running_var.mul_(1 - m).add_(var, alpha=m)
                     bn.num_batches_tracked += 1
         return y
+    if slope != 1.0 or mean_offset is not None:
+        raise FF.FmiError("batch_norm(slope=..., mean_offset=...) is the batch-statistics form: eval mode has no fused activation or offset")
     if x.dtype == torch.bfloat16:  # eval-mode BatchNorm of a bf16 body: evaluated in fp32 (inference path, not the benchmarked one)
         y = batch_norm(bn, x.float()).to(torch.bfloat16)
         return (y, x) if passthrough else y

@@ -25,6 +25,9 @@ from .modules.pluralistic_model import base_function
 from .modules.psp.psp import pSp
 
 
+MASK_DETECTOR_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
+
+
 def get_args(argv=None):
     """the reference's flags with the reference's defaults (psp_inference.py:19-77).  Differences, all about paths: no default points
     outside the working directory (``--data_root`` absent = synthetic batches; ``--pt_ckpt_path`` / ``--mask_detector_path`` absent =
@@ -50,6 +53,8 @@ def get_args(argv=None):
     p.add_argument("--stylegan_weights", default=None, type=str, help="Path to StyleGAN model weights")
     # this build's extras
     p.add_argument("--decoder_dtype", type=str, default="fp32", choices=("fp32", "bf16"), help="activation type of the synthesis network")
+    p.add_argument("--mask_detector_dtype", type=str, default="fp32", choices=("fp32", "bf16"),
+                   help="activation type of the mask detector's UNet body (bf16 needs H and W to be multiples of 16)")
     p.add_argument("--out_dir", type=str, default=None, help="where gen_<id>.jpg / metrics.csv go (default: test_results/<run name>)")
     p.add_argument("--num_batches", type=int, default=2, help="synthetic mode: batches to run")
     return p.parse_args(argv)
@@ -113,7 +118,10 @@ def evaluate(gt_img, gen_img, ssim_func, ms_ssim_func, unit=None):
 
 def build(args, device):
     """frozen eval mask detector + pSp(args); without a stored latent_avg the mean of 1e5 mapped latents (psp_inference.py:131-143)"""
-    mask_detector = MaskDetector(n_channels=3, bilinear=True)
+    dt = getattr(args, "mask_detector_dtype", "fp32")
+    if dt not in MASK_DETECTOR_DTYPES:
+        raise FF.FmiError(f"mask_detector_dtype must be one of {sorted(MASK_DETECTOR_DTYPES)}, got {dt!r}")
+    mask_detector = MaskDetector(n_channels=3, bilinear=True, compute_dtype=MASK_DETECTOR_DTYPES[dt])
     if args.mask_detector_path:
         mask_detector.load_state_dict(torch.load(args.mask_detector_path, map_location="cpu", weights_only=True))
     base_function._freeze(mask_detector)

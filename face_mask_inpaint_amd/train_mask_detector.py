@@ -11,12 +11,16 @@ Dice score (:107,162) and one ``checkpoint_epoch{n}.pth`` state_dict per epoch (
   * logging goes through ``logging`` and an optional ``callback(event: dict)`` -- no wandb, no tqdm;
   * ``train_step`` never synchronises with the host.  The one synchronisation per evaluation round is the ``float()`` that
     ReduceLROnPlateau needs; per-step losses stay device scalars until that read (or the end of the epoch);
-  * ``--amp`` is refused: a bf16 UNet body is not built.
+  * ``--amp`` is refused: fp16 autocast with a GradScaler is not built.  What is built is the bf16 UNet body (fp32 master weights,
+    statistics and parameter gradients; no loss scaling needed): ``train_net(..., dtype="bf16")``, or on the command line the
+    environment variable ``FMI_MASK_DETECTOR_DTYPE=bf16`` (``fp32`` is the default; ``get_args`` keeps exactly the reference's flags).
+    The bf16 body needs image sizes that are multiples of 16; checkpoints are the same in either dtype.
 """
 from __future__ import annotations
 
 import argparse
 import logging
+import os
 import sys
 from pathlib import Path
 
@@ -32,6 +36,20 @@ from .optim import FusedAdam
 DIR_IMG = Path('../CelebAHQ/images_masked')
 DIR_MASK = Path('../CelebAHQ/binary_map')
 DIR_CHECKPOINT = Path('./checkpoints256_mask_detector/')
+
+
+DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
+
+
+def set_compute_dtype(net, compute_dtype):
+    """put ``net`` (a MaskDetector) on the fp32 or the bf16 UNet body in place: parameters, buffers and the state_dict do not change"""
+    from .modules.unet.unet_parts import _mark_bf16
+
+    for m in net.modules():
+        if hasattr(m, "compute_dtype"):
+            m.compute_dtype = compute_dtype
+    _mark_bf16(net, compute_dtype)
+    return net
 
 
 def train_step(net, optimizer, images, true_masks):
@@ -75,16 +93,27 @@ def train_net(net,
               dir_checkpoint=DIR_CHECKPOINT,
               seed=None,
               callback=None,
-              history=None):
+              history=None,
+              dtype: str = "fp32"):
     """the reference's train_net (:61-181).  Returns the history: ``losses`` (one float per step), ``val_scores`` / ``val_steps`` /
     ``lrs`` (one entry per evaluation round; the learning rate after the scheduler saw the score), ``checkpoints`` (paths).  A dict
     passed as ``history`` is filled in place, so a caller that catches an exception (``main`` on Ctrl-C) still holds what was recorded.
     Per-step losses wait on the device until the next point that synchronises anyway (a validation round, the end of an epoch)."""
+    if dtype not in DTYPES:
+        raise FmiError(f"dtype must be one of {sorted(DTYPES)}, got {dtype!r}")
     if amp:
-        raise FmiError("--amp: the UNet runs in fp32 here (a bf16 UNet body is not built); run without --amp")
+        raise FmiError('--amp: fp16 autocast with a GradScaler is not built; run without --amp and use dtype="bf16" '
+                       '(FMI_MASK_DETECTOR_DTYPE=bf16 on the command line) for the bf16 UNet body')
     device = torch.device(device)
     if device.type != 'cuda':
         raise FmiError("train_mask_detector needs the GPU (there is no CPU path)")
+
+    have = getattr(net, "compute_dtype", torch.float32)
+    if have != DTYPES[dtype]:
+        if dtype == "fp32":  # never take a net that was built for bf16 off its body behind the caller's back
+            raise FmiError('dtype="fp32" (the default) but the net was built with compute_dtype=torch.bfloat16: pass dtype="bf16", '
+                           'or set_compute_dtype(net, torch.float32) first')
+        net = set_compute_dtype(net, DTYPES[dtype])
 
     # 1. Create dataset
     dataset = BasicDataset(dir_img, dir_mask, img_scale, device=device)
@@ -175,7 +204,7 @@ def get_args(argv=None):
     parser.add_argument('--scale', '-s', type=float, default=1, help='Downscaling factor of the images')
     parser.add_argument('--validation', '-v', dest='val', type=float, default=10.0,
                         help='Percent of the data that is used as validation (0-100)')
-    parser.add_argument('--amp', action='store_true', default=False, help='Use mixed precision (refused: the UNet is fp32 here)')
+    parser.add_argument('--amp', action='store_true', default=False, help='Use mixed precision (refused: fp16 autocast is not built; FMI_MASK_DETECTOR_DTYPE=bf16 selects the bf16 body)')
     parser.add_argument('--threshold', '-t', type=float, default=0.5, help='Threshold for deciding mask')
 
     return parser.parse_args(argv)
@@ -191,7 +220,10 @@ def main(argv=None):
     logging.info(f'Using device {device}')
 
     # n_channels=3 for RGB images; two classes (mask / no mask)
-    net = MaskDetector(n_channels=3, bilinear=True, threshold=args.threshold)
+    dtype = os.environ.get("FMI_MASK_DETECTOR_DTYPE", "fp32")
+    if dtype not in DTYPES:
+        raise FmiError(f"FMI_MASK_DETECTOR_DTYPE: dtype must be one of {sorted(DTYPES)}, got {dtype!r}")
+    net = MaskDetector(n_channels=3, bilinear=True, threshold=args.threshold, compute_dtype=DTYPES[dtype])
 
     logging.info(f'Network:\n'
                  f'\t{net.n_channels} input channels\n'
@@ -213,7 +245,8 @@ def main(argv=None):
                          device=device,
                          img_scale=args.scale,
                          val_percent=args.val / 100,
-                         amp=args.amp)
+                         amp=args.amp,
+                         dtype=dtype)
     except KeyboardInterrupt:
         torch.save(net.state_dict(), 'INTERRUPTED.pth')
         logging.info('Saved interrupt after %d recorded steps, %d validation rounds',

@@ -227,7 +227,8 @@ int fmi_conv2d_fwd_bf16(const fmi_conv_desc* d, const uint16_t* x, const uint16_
 /* y = lrelu(conv(x, W) * colscale[n][k] + nw[0] * noise[n][oy][ox] + bias[k], slope) * gain in one launch: ModulatedConv2d on pre-scaled
  * activations + demodulation + NoiseInjection + FusedLeakyReLU (stylegan2/model.py:241-294, op/fused_act.py:30-37).  colscale [N][K],
  * noise [N][OH][OW], bias [K] may be NULL.  FMI_ERR_UNSUPPORTED where the eight-phase kernel does not apply (needs C % 64 == 0,
- * K % 4 == 0, K > 64, y 8-byte and colscale / bias 16-byte aligned). */
+ * K % 4 == 0, y 8-byte and colscale / bias 16-byte aligned).  With colscale = gamma / sqrt(running_var + eps) per sample, bias =
+ * beta + (conv_bias - running_mean) * scale, slope 0 and gain 1 this is an eval-mode conv + BatchNorm + ReLU. */
 int fmi_conv2d_fwd_act_bf16(const fmi_conv_desc* d, const uint16_t* x, const uint16_t* wnk, const float* colscale, const float* noise,
                             const float* nw, const float* bias, float slope, float gain, uint16_t* y, void* stream);
 int fmi_conv2d_dgrad_bf16(const fmi_conv_desc* d, const uint16_t* dy, const uint16_t* wck, const float* colscale, uint16_t* dx, float* ws,
@@ -530,6 +531,11 @@ int fmi_instnorm_apply_f32(const float* x, const float* stats, const float* gamm
  * instead of being reconstructed as 1 / rstd^2 - eps */
 int fmi_batchnorm_running_update_f32(const float* stats, const double* sums, float* running_mean, float* running_var,
                                      int64_t* num_batches_tracked, int C, int64_t count, float eps, float momentum, void* stream);
+/* the same update for a tensor that was normalised WITHOUT a per-channel constant that cancels in the mean subtraction (the bias of the
+ * convolution in front): running_mean takes batch mean + mean_offset[c], the value the path that applies the constant stores */
+int fmi_batchnorm_running_update_offset_f32(const float* stats, const double* sums, const float* mean_offset, float* running_mean,
+                                            float* running_var, int64_t* num_batches_tracked, int C, int64_t count, float eps,
+                                            float momentum, void* stream);
 /* backward of y = lrelu(IN(x)): red[n][c] = {sum g', sum g'*xhat} (ws as above), then gx; dgamma/dbeta += */
 int fmi_instnorm_bwd_reduce_f32(const float* x, const float* gy, const float* stats, const float* gamma,
                                 const float* beta, double* red, int N, int HW, int C, float slope, double* ws, int64_t ws_doubles,
@@ -748,6 +754,27 @@ int fmi_prelu_bwd_f32(const float* g, const float* x, const float* a, float* gx,
                       int C, void* stream);
 /* MaxPool2d(1, stride) = sub-sampling; backward != 0: x is the output gradient [N,OH,OW,C], y the (fully written) input gradient */
 int fmi_subsample_f32(const float* x, float* y, int N, int H, int W, int C, int stride, int backward, void* stream);
+
+/* ------------------------------------------------------------------------
+ * bf16 body of the UNet mask detector (modules/unet/unet_parts.py), csrc/unet_bf16.hip.  NHWC bf16 tensors (raw bits), C % 8 == 0 and
+ * 16-byte aligned pointers (FMI_ERR_UNSUPPORTED otherwise), fp32 arithmetic, round-to-nearest-even stores, no atomics.
+ * ---------------------------------------------------------------------- */
+/* 2 x 2 stride-2 max pooling, H and W even; the backward routes gy to the FIRST maximum of the window in row-major order */
+int fmi_maxpool2_bf16(const uint16_t* x, uint16_t* y, int N, int H, int W, int C, void* stream);
+int fmi_maxpool2_bwd_bf16(const uint16_t* x, const uint16_t* gy, uint16_t* gx, int N, int H, int W, int C, void* stream);
+/* Up (unet_parts.py:45-72) in one pass: y [N,H,W,C2+C1] = cat([skip [N,H,W,C2], pad(bilinear x2 align_corners=True of x1 [N,h,w,C1])], C);
+ * the zero border is (H - 2h) / 2 rows on top and the rest below, the same split left and right; H >= 2h, W >= 2w.
+ * Backward: gskip = the first C2 channels of g, gx1 = the adjoint of the interpolation as a gather (both fully written). */
+int fmi_up2_cat_bf16(const uint16_t* x1, const uint16_t* skip, uint16_t* y, int N, int h, int w, int C1, int H, int W, int C2, void* stream);
+int fmi_up2_cat_bwd_bf16(const uint16_t* g, uint16_t* gskip, uint16_t* gx1, int N, int h, int w, int C1, int H, int W, int C2, void* stream);
+/* OutConv (1 x 1): y [P,K] fp32 = x [P,C] bf16 . w [K][C] fp32 + b [K]; K <= 4, C <= 1024.  The argmax form writes the float index of
+ * the first maximum per pixel (fmi_argmax_channels_f32 of the same logits, which are never stored). */
+int fmi_head1x1_bf16(const uint16_t* x, const float* w, const float* b, float* y, int64_t P, int C, int K, void* stream);
+int fmi_head1x1_argmax_bf16(const uint16_t* x, const float* w, const float* b, float* mask, int64_t P, int C, int K, void* stream);
+/* g [P,K] fp32 -> gx [P,C] bf16, gw [K][C] and gb [K] fp32 (written): one partial row per workgroup in ws (ws_doubles >= K*C + K; up to
+ * 512 rows are used), added in a fixed order by a finishing launch */
+int fmi_head1x1_bwd_bf16(const float* g, const uint16_t* x, const float* w, uint16_t* gx, float* gw, float* gb, double* ws,
+                         int64_t ws_doubles, int64_t P, int C, int K, void* stream);
 
 #ifdef __cplusplus
 }
