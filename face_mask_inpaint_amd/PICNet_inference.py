@@ -19,6 +19,7 @@ from .modules.pluralistic_model import base_function
 
 
 MASK_DETECTOR_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
+GENERATOR_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
 
 
 def get_args(argv=None):
@@ -41,6 +42,10 @@ def get_args(argv=None):
     p.add_argument("--out_dir", type=str, default=None, help="this build's extra: where metrics.csv goes (not written when absent)")
     p.add_argument("--mask_detector_dtype", type=str, default="fp32", choices=("fp32", "bf16"),
                    help="this build's extra: activation type of the mask detector's UNet body (bf16 needs H and W to be multiples of 16)")
+    # not --decoder_*: process_params would sweep it into define_g's keywords
+    p.add_argument("--generator_dtype", type=str, default="fp32", choices=("fp32", "bf16"),
+                   help="this build's extra: activation type of the generator's decoder blocks, attention and Output block (bf16: inference "
+                        "on the bf16 kernels; needs a token count at attn1 that is a multiple of 128, which --old_model does not give)")
     p.add_argument("--encoder_type", type=str, default="pluralistic")
     p.add_argument("--encoder_ngf", type=int, default=32)
     p.add_argument("--encoder_z_nc", type=int, default=128)
@@ -103,6 +108,12 @@ def evaluate(gt_img, gen_img, ssim_func, ms_ssim_func=None):
 
 
 def build(args, device):
+    gdt = getattr(args, "generator_dtype", "fp32")
+    if gdt not in GENERATOR_DTYPES:
+        raise FF.FmiError(f"generator_dtype must be one of {sorted(GENERATOR_DTYPES)}, got {gdt!r}")
+    if gdt == "bf16" and args.old_model:
+        raise FF.FmiError("--generator_dtype bf16 does not go with --old_model: its 218 x 178 input gives a token count at attn1 that is not a "
+                          "multiple of 128, which the bf16 attention kernel needs; run --old_model in fp32")
     dt = getattr(args, "mask_detector_dtype", "fp32")
     if dt not in MASK_DETECTOR_DTYPES:
         raise FF.FmiError(f"mask_detector_dtype must be one of {sorted(MASK_DETECTOR_DTYPES)}, got {dt!r}")
@@ -113,7 +124,7 @@ def build(args, device):
     mask_detector = mask_detector.to(device).eval()
     encoder_params, decoder_params = process_params(args)
     kw = dict(out_size=(218, 178)) if args.old_model else {}
-    generator = ReferenceFill(None, encoder_params, decoder_params, use_att=bool(args.use_att), **kw).to(device)
+    generator = ReferenceFill(None, encoder_params, decoder_params, use_att=bool(args.use_att), decoder_dtype=GENERATOR_DTYPES[gdt], **kw).to(device)
     if args.pt_ckpt_path:
         generator.load_state_dict(torch.load(args.pt_ckpt_path, map_location="cpu", weights_only=True), strict=False)
     return generator.eval(), mask_detector

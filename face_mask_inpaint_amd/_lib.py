@@ -61,6 +61,7 @@ SIGNATURES = {
     "fmi_conv2d_thin_dgrad_f32": [PD, vp, vp, vp, vp],
     "fmi_conv2d_thin_input_dgrad_f32": [PD, vp, vp, vp, vp],
     "fmi_conv2d_thin_lrelu_fwd_f32": [PD, vp, f32, vp, vp, vp, i32, vp],
+    "fmi_conv2d_thin_lrelu_fwd_bf16": [PD, vp, f32, vp, vp, vp, i32, vp],
     "fmi_conv2d_thin_lrelu_dgrad_f32": [PD, vp, vp, vp, f32, vp, vp],
     "fmi_conv2d_thin_lrelu_wgrad_f32": [PD, vp, f32, vp, vp, vp, vp],
     "fmi_conv2d_thin_wgrad_f32": [PD, vp, vp, vp, vp, vp],
@@ -86,6 +87,7 @@ SIGNATURES = {
     "fmi_softmax_rows_f32": [vp, vp, i64, i32, vp],
     "fmi_softmax_rows_bwd_f32": [vp, vp, vp, i64, i32, vp],
     "fmi_attention_fwd_f32": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "fmi_attention_fwd_bf16": [vp] * 6 + [i32] * 5 + [vp],
     "fmi_attention_bwd_f32": [vp] * 12 + [i32] * 5 + [vp],
     "fmi_attention_fwd_image_bytes": [i32, i32, i32, i32, i32, C.POINTER(i64)],
     "fmi_attention_fwd_pieces_f32": [vp] * 4 + [i64] + [vp] * 3 + [i32] * 5 + [vp],
@@ -133,6 +135,7 @@ SIGNATURES = {
     "fmi_scale_channels_add_f32": [vp, vp, vp, vp, i32, i64, i32, vp],
     "fmi_instnorm_bwd_apply_add_f32": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
     "fmi_copy_channels_f32": [vp, vp, i64, i32, i32, i32, i32, i32, vp],
+    "fmi_copy_channels_bf16": [vp, vp, i64, i32, i32, i32, i32, i32, vp],
     "fmi_l2norm_rows_f32": [vp, vp, vp, i64, i32, f32, vp],
     "fmi_l2norm_rows_bwd_f32": [vp, vp, vp, vp, i64, i32, f32, vp],
     "fmi_lpips_layer_f32": [vp, vp, vp, vp, i64, i32, f32, vp],
@@ -189,7 +192,7 @@ SIGNATURES = {
 STATUS = {0: "ok", 1: "bad argument", 2: "unsupported shape/mode", 3: "kernel launch failed"}
 
 
-PREDICATES = {"fmi_debug_bf16_tile": [i32], "fmi_set_deterministic": [i32], "fmi_get_deterministic": [], "fmi_conv2d_thin_supported": [PD], "fmi_conv2d_bf16_supported": [PD], "fmi_conv2d_thin_lrelu_supported": [PD], "fmi_conv2d_thin_lrelu_bwd_ws_bytes": [PD], "fmi_conv_transpose2d_pair_bwd_supported": [PD, i32, i32], "fmi_conv_transpose2d_pair_bwd_ws_bytes": [PD, i32, i32], "fmi_attention_fwd_uses_pieces": [i32] * 5, "fmi_attention_bwd_uses_pieces": [i32] * 5, "fmi_attention_fwd_waves": [i32] * 2, "fmi_attention_bwd_structure": [i32] * 2}
+PREDICATES = {"fmi_debug_bf16_tile": [i32], "fmi_set_deterministic": [i32], "fmi_get_deterministic": [], "fmi_conv2d_thin_supported": [PD], "fmi_conv2d_bf16_supported": [PD], "fmi_conv2d_thin_lrelu_supported": [PD], "fmi_conv2d_thin_lrelu_bwd_ws_bytes": [PD], "fmi_conv_transpose2d_pair_bwd_supported": [PD, i32, i32], "fmi_conv_transpose2d_pair_bwd_ws_bytes": [PD, i32, i32], "fmi_attention_fwd_uses_pieces": [i32] * 5, "fmi_attention_bwd_uses_pieces": [i32] * 5, "fmi_attention_fwd_waves": [i32] * 2, "fmi_attention_fwd_bf16_waves": [i32] * 2, "fmi_attention_bwd_structure": [i32] * 2}
 
 
 class FmiError(RuntimeError):

@@ -421,3 +421,12 @@ extern "C" int fmi_copy_channels_f32(const float* src, float* dst, int64_t rows,
                      src_stride, src_c0, dst_stride, dst_c0, c, vec);
   return fmi_launch_status();
 }
+// the same strided copy for bf16 maps: every count a multiple of 8 elements, moved as the 16-byte chunks of the kernel above
+extern "C" int fmi_copy_channels_bf16(const uint16_t* src, uint16_t* dst, int64_t rows, int src_stride, int src_c0, int dst_stride, int dst_c0,
+                                      int c, void* stream) {
+  if (!src || !dst || rows <= 0 || c <= 0 || src_c0 < 0 || dst_c0 < 0 || src_c0 + c > src_stride || dst_c0 + c > dst_stride) return FMI_ERR_BAD_ARG;
+  if (((src_stride | src_c0 | dst_stride | dst_c0 | c) & 7) || (((uintptr_t)src | (uintptr_t)dst) & 15)) return FMI_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(copy_channels_kernel, dim3(fmi_bw_grid(rows * (c / 8), 256)), dim3(256), 0, (hipStream_t)stream, (const float*)src,
+                     (float*)dst, rows, src_stride / 2, src_c0 / 2, dst_stride / 2, dst_c0 / 2, c / 2, 4);
+  return fmi_launch_status();
+}

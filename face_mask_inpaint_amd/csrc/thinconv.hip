@@ -330,8 +330,11 @@ __global__ void __launch_bounds__(256) thin_fwd_mfma_kernel(ThinArgs a, int qbit
 // the gather of the row-segment kernel above -- 4 pixels x 16 B per MFMA block, 128 B apart -- costs it ~4x as many cycles per byte),
 // then every tap comes out of LDS as ds_read_b128 in the MFMA block layout.  Input bytes cross HBM/L2 1.33x instead of 9x.
 // Workgroups are persistent (one round of resident ones) and keep the window of their NEXT tile in flight during the arithmetic.
+// XB16: x is bf16 (a.x holds the bf16 base, a.xcs counts bf16 elements): the window is read as 16-byte chunks of 8 channels, 4 lanes per
+// pixel, and widened (and activated) on its way into the same fp32 LDS tile -- half the HBM bytes, the arithmetic unchanged.
 constexpr int LT_H = 8, LT_W = 32, LT_PITCH = 36;  // pixel pitch in floats (32 channels + 4 pad: spreads the b128 reads over the banks)
-template <int K>
+typedef uint32_t thin_u32x4 __attribute__((ext_vector_type(4)));
+template <int K, bool XB16 = false>
 __global__ void __launch_bounds__(256) thin_fwd_lds_kernel(ThinArgs a, int tiles_x, int tiles_y, int ntiles) {
   __shared__ __attribute__((aligned(16))) float sx[(LT_H + 2) * (LT_W + 2) * LT_PITCH];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -341,14 +344,32 @@ __global__ void __launch_bounds__(256) thin_fwd_lds_kernel(ThinArgs a, int tiles
   for (int t = 0; t < 9; ++t)
 #pragma unroll
     for (int e = 0; e < 4; ++e) wr[t][e] = i < K ? a.w[((int64_t)(a.flip ? 8 - t : t) * a.C + 4 * q + e) * K + i] : 0.f;
-  constexpr int NPIX = (LT_H + 2) * (LT_W + 2), NLD = (NPIX + 31) / 32;
+  constexpr int NPIX = (LT_H + 2) * (LT_W + 2), NLD = XB16 ? 1 : (NPIX + 31) / 32, NLDB = XB16 ? (NPIX + 63) / 64 : 1;
   float4 stage[NLD];  // all loads in flight before the first LDS store (a load-store-load chain would pay the latency NLD times)
+  thin_u32x4 stageb[NLDB];  // XB16: chunk tid & 3 (8 channels) of window pixel (tid >> 2) + 64 j
   // the window of a tile: chunk c8 = tid & 7 of window pixel (tid >> 3) + 32 j
   auto load_window = [&](int tile) {
     const int tx = tile % tiles_x;
     tile /= tiles_x;
     const int ty = tile % tiles_y, n = tile / tiles_y;
     const int y0 = ty * LT_H, x0 = tx * LT_W;
+    if constexpr (XB16) {
+      const uint16_t* imgb = reinterpret_cast<const uint16_t*>(a.x) + (int64_t)n * a.H * a.W * a.xcs;
+#pragma unroll
+      for (int j = 0; j < NLDB; ++j) {
+        const int p = (tid >> 2) + 64 * j;
+        const int wy = p / (LT_W + 2), wx = p - wy * (LT_W + 2);
+        int iy = y0 + wy - 1, ix = x0 + wx - 1;
+        if (a.pad_mode) {
+          iy = reflect1(iy, a.H);
+          ix = reflect1(ix, a.W);
+        }
+        const bool ok = p < NPIX && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
+        stageb[j] = thin_u32x4{0u, 0u, 0u, 0u};
+        if (ok) stageb[j] = *reinterpret_cast<const thin_u32x4*>(imgb + ((int64_t)iy * a.W + ix) * a.xcs + 8 * (tid & 3));
+      }
+      return;
+    }
     const float* img = a.x + (int64_t)n * a.H * a.W * a.xcs;
 #pragma unroll
     for (int j = 0; j < NLD; ++j) {
@@ -368,14 +389,30 @@ __global__ void __launch_bounds__(256) thin_fwd_lds_kernel(ThinArgs a, int tiles
   int tile = blockIdx.x;  // the host launches at most ntiles workgroups
   load_window(tile);
   while (true) {
-    if (a.in_slope != 1.f) {
+    if constexpr (XB16) {
 #pragma unroll
-      for (int j = 0; j < NLD; ++j) stage[j] = lrelu4(stage[j], a.in_slope);
-    }
+      for (int j = 0; j < NLDB; ++j) {
+        const int p = (tid >> 2) + 64 * j;
+        const thin_u32x4 u = stageb[j];
+        const float4 lo = lrelu4(make_float4(__uint_as_float(u[0] << 16), __uint_as_float(u[0] & 0xFFFF0000u), __uint_as_float(u[1] << 16),
+                                             __uint_as_float(u[1] & 0xFFFF0000u)), a.in_slope);
+        const float4 hi = lrelu4(make_float4(__uint_as_float(u[2] << 16), __uint_as_float(u[2] & 0xFFFF0000u), __uint_as_float(u[3] << 16),
+                                             __uint_as_float(u[3] & 0xFFFF0000u)), a.in_slope);
+        if (p < NPIX) {
+          *reinterpret_cast<float4*>(sx + p * LT_PITCH + 8 * (tid & 3)) = lo;
+          *reinterpret_cast<float4*>(sx + p * LT_PITCH + 8 * (tid & 3) + 4) = hi;
+        }
+      }
+    } else {
+      if (a.in_slope != 1.f) {
 #pragma unroll
-    for (int j = 0; j < NLD; ++j) {
-      const int p = (tid >> 3) + 32 * j;
-      if (p < NPIX) *reinterpret_cast<float4*>(sx + p * LT_PITCH + 4 * (tid & 7)) = stage[j];
+        for (int j = 0; j < NLD; ++j) stage[j] = lrelu4(stage[j], a.in_slope);
+      }
+#pragma unroll
+      for (int j = 0; j < NLD; ++j) {
+        const int p = (tid >> 3) + 32 * j;
+        if (p < NPIX) *reinterpret_cast<float4*>(sx + p * LT_PITCH + 4 * (tid & 7)) = stage[j];
+      }
     }
     __syncthreads();
     int b = tile;
@@ -972,9 +1009,9 @@ static void bwd_launch(const fmi_conv_desc* d, const BwdArgs& a, int64_t rows, h
   if (g_bd > 0) hipLaunchKernelGGL((thin_lrelu_bwd_kernel<K, true>), dim3((unsigned)g_bd), dim3(256), 0, st, a, tg, (int)n_bd, (int)g_in);
   *rows_used = (int)(g_in + g_bd);
 }
-template <int K>
+template <int K, bool XB16 = false>
 static int fwd_lds_resident_grid() {
-  static const int g = resident_grid(thin_fwd_lds_kernel<K>);
+  static const int g = resident_grid(thin_fwd_lds_kernel<K, XB16>);
   return g;
 }
 template <int K>
@@ -1047,6 +1084,34 @@ extern "C" int fmi_conv2d_thin_fwd_f32(const fmi_conv_desc* d, const float* x, c
 extern "C" int fmi_conv2d_thin_lrelu_fwd_f32(const fmi_conv_desc* d, const float* x, float in_slope, const float* wf, const float* bias,
                                              float* y, int act, void* stream) {
   return thin_fwd_impl(d, x, in_slope, wf, bias, nullptr, y, act, stream);
+}
+
+/* The Output block from a bf16 activation: x [N,H,W,32] bf16 (pixel pitch d->x_cstride bf16 elements, a multiple of 8), y the fp32 image.
+ * The LDS halo-tile kernel with 16-byte loads of 8 channels; lrelu, taps, bias and tanh in fp32. */
+extern "C" int fmi_conv2d_thin_lrelu_fwd_bf16(const fmi_conv_desc* d, const uint16_t* x, float in_slope, const float* wf, const float* bias,
+                                              float* y, int act, void* stream) {
+  if (!d || !x || !wf || !y || act < 0 || act > 2) return FMI_ERR_BAD_ARG;
+  if (!thin_lrelu_ok(d) || d->x_cstride % 8 != 0 || ((uintptr_t)x & 15)) return FMI_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  ThinArgs a{reinterpret_cast<const float*>(x), wf, bias, nullptr, y, d->N, d->H, d->W, d->C, d->K, d->x_cstride, d->y_cstride, d->pad_mode, act};
+  a.in_slope = in_slope;
+  const int tiles_x = (d->W + LT_W - 1) / LT_W, tiles_y = (d->H + LT_H - 1) / LT_H;
+  const int64_t nb = (int64_t)d->N * tiles_x * tiles_y;  // < 2^31: thin_shape_ok bounds N H W
+  int res = 768;
+  switch (d->K) {
+    case 1: res = fwd_lds_resident_grid<1, true>(); break;
+    case 2: res = fwd_lds_resident_grid<2, true>(); break;
+    case 3: res = fwd_lds_resident_grid<3, true>(); break;
+    default: res = fwd_lds_resident_grid<4, true>(); break;
+  }
+  const int grid = (int)(nb < res ? nb : res);
+  switch (d->K) {
+    case 1: hipLaunchKernelGGL((thin_fwd_lds_kernel<1, true>), dim3(grid), dim3(256), 0, st, a, tiles_x, tiles_y, (int)nb); break;
+    case 2: hipLaunchKernelGGL((thin_fwd_lds_kernel<2, true>), dim3(grid), dim3(256), 0, st, a, tiles_x, tiles_y, (int)nb); break;
+    case 3: hipLaunchKernelGGL((thin_fwd_lds_kernel<3, true>), dim3(grid), dim3(256), 0, st, a, tiles_x, tiles_y, (int)nb); break;
+    default: hipLaunchKernelGGL((thin_fwd_lds_kernel<4, true>), dim3(grid), dim3(256), 0, st, a, tiles_x, tiles_y, (int)nb); break;
+  }
+  return fmi_launch_status();
 }
 
 /* dx (layout of x) = adjoint of the thin convolution applied to dy; pad_mode = reflect includes the fold of the padded

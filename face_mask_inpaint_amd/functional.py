@@ -1336,6 +1336,100 @@ def conv_bn_relu_eval_bf16(x, pw: PackedWeight, conv_bias, bn, pad=1):
     return y
 
 
+# ---- bf16 PICNet decoder (ResGenerator(compute_dtype=torch.bfloat16)): inference forms, no autograd nodes.  The caller has refused
+# grad mode (ResGenerator.check_inference); activations are bf16 NHWC, parameters fp32, the bf16 weight packs are cut from the fp32
+# packs that weight_scope prepared (W / sigma), exactly as the other bf16 convolutions do. ----
+def instance_norm_act_bf16(x, gamma, beta, eps=1e-5, slope=1.0):
+    """lrelu(InstanceNorm2d(affine)(x), slope) on a bf16 NHWC map: fp32 statistics (fp64 sums) and parameters, bf16 in and out"""
+    _chk(x, dtype=BF16)
+    _chk(gamma, beta)
+    lib = _L()
+    n, h, w, c = x.shape
+    sums, ws = _norm_ws(x.device, n, c)
+    stats = torch.empty((n, c, 2), device=x.device, dtype=torch.float32)
+    lib.instnorm_stats_bf16(_p(x), C.c_void_p(sums.data_ptr()), _p(stats), n, h * w, c, eps, C.c_void_p(ws.data_ptr()), ws.numel(), _st())
+    y = torch.empty_like(x)
+    lib.instnorm_apply_bf16(_p(x), _p(stats), _p(gamma), _p(beta), _p(y), n, h * w, c, slope, _st())
+    return y
+
+
+def conv2d_bias_bf16(x, pw: PackedWeight, bias, pad):
+    """conv(x) + bias on a bf16 NHWC map in one launch (the output stage of fmi_conv2d_fwd_act_bf16 with slope 1, gain 1)"""
+    _chk(x, dtype=BF16)
+    _chk(bias)
+    n, h, w, c = x.shape
+    k = pw.wf.shape[2]
+    if c % 64 or k % 4:
+        raise FmiError(f"the bf16 convolution with a bias stage needs C % 64 == 0 and K % 4 == 0, got {c} -> {k}")
+    dsc, oh, ow = conv_desc(n, h, w, c, k, pw.kh, pw.kw, 1, pad)
+    y = torch.empty((n, oh, ow, k), device=x.device, dtype=BF16)
+    wnk = _pack_bf16(pw.wf)
+    with _prof(f"conv_fwd_bf16|{n}x{h}x{w} {c}->{k} k{pw.kh}s1 +bias", 2.0 * n * oh * ow * k * c * pw.kh * pw.kw):
+        _L().conv2d_fwd_act_bf16(C.byref(dsc), _p(x), _p(wnk), None, None, None, _p(bias), 1.0, 1.0, _p(y), _st())
+    return y
+
+
+def conv_transpose2d_cat_bf16(x1, pw1: PackedWeight, x2, pw2: PackedWeight, bias=None):
+    """ConvTranspose2d_1(x1) + ConvTranspose2d_2(x2) + bias for two kernel-3 / stride-2 / padding-1 / output_padding-1 layers of one
+    output width on bf16 NHWC maps: ONE ConvTranspose2d of cat[x1, x2] with the two adjoint packs concatenated along the reduction
+    (one fmi_conv2d_dgrad_bf16 launch, all four sub-pixel phases), then the bias in one in-place pass over the result."""
+    _chk(x1, x2, dtype=BF16)
+    _chk(bias)
+    lib = _L()
+    n, h, w, c1 = x1.shape
+    c2, cb = x2.shape[3], pw1.wf.shape[1]
+    if x2.shape[:3] != x1.shape[:3] or pw2.wf.shape[1] != cb or (pw1.kh, pw1.kw, pw2.kh, pw2.kw) != (3, 3, 3, 3):
+        raise FmiError("conv_transpose2d_cat_bf16: the two layers must share the input extent, the output width and the 3 x 3 kernel")
+    if c1 % 8 or c2 % 8 or (c1 + c2) % 32 or cb % 8:
+        raise FmiError(f"conv_transpose2d_cat_bf16 needs input widths % 8 == 0 with a sum % 32 == 0 and an output width % 8 == 0, got "
+                       f"{c1} + {c2} -> {cb}")
+    cs = c1 + c2
+    cat = torch.empty((n, h, w, cs), device=x1.device, dtype=BF16)
+    lib.copy_channels_bf16(_p(x1), _p(cat), n * h * w, c1, 0, cs, 0, c1, _st())
+    lib.copy_channels_bf16(_p(x2), _p(cat), n * h * w, c2, 0, cs, c1, c2, _st())
+    wck = torch.cat([_pack_bf16(pw1.wt), _pack_bf16(pw2.wt)], dim=2).contiguous()  # [cb][taps][c1 + c2]: weight-sized bookkeeping
+    H, W = 2 * h, 2 * w
+    d, oh, ow = conv_desc(n, H, W, cb, cs, 3, 3, 2, 1)
+    y = torch.empty((n, H, W, cb), device=x1.device, dtype=BF16)
+    ws, wsn = _split_ws(y, cs * 9 // 4)
+    with _prof(f"convT_fwd_bf16|{n}x{h}x{w} {c1}+{c2}->{cb}", 2.0 * cat.numel() * cb * 9):
+        lib.conv2d_dgrad_bf16(C.byref(d), _p(cat), _p(wck), None, _p(y), _p(ws), wsn, _st())
+    if bias is not None:
+        lib.noise_bias_act_bf16(_p(y), _p(bias), None, None, _p(y), n * H * W, cb, 1.0, 1.0, _st())
+    return y
+
+
+def self_attention_bf16(q, v, gamma=None, residual=None):
+    """softmax(q q^T) v on bf16 [N,T,D] / [N,T,C] (fp32 scores and accumulators), optionally gamma[0] * O + residual in the same launch"""
+    _chk(q, v, residual, dtype=BF16)
+    _chk(gamma)
+    n, t, d = q.shape
+    c = v.shape[2]
+    if t % 128 or (d, c) not in ((64, 256), (32, 128)):
+        raise FmiError(f"the bf16 attention needs a token count that is a multiple of 128 and (d_qk, C) in {{(64, 256), (32, 128)}}, got "
+                       f"T = {t}, (d_qk, C) = ({d}, {c})")
+    o = torch.empty_like(v)
+    with _prof(f"attn_fused_fwd_bf16|T{t} d{d} C{c} b{n}", 2.0 * n * t * t * (d + c)):
+        _L().attention_fwd_bf16(_p(q), _p(v), _p(o), None, _p(gamma), _p(residual), n, t, d, c, 0, _st())
+    return o
+
+
+def lrelu_conv2d_thin_bf16(x, pw: PackedWeight, bias, slope, pad_mode, act):
+    """act(conv3x3(lrelu(x, slope)) + bias): the Output block from a bf16 NHWC map with 32 channels to the fp32 image, one pass"""
+    _chk(x, dtype=BF16)
+    _chk(bias)
+    n, h, w, c = x.shape
+    k = pw.wf.shape[2]
+    d, oh, ow = conv_desc(n, h, w, c, k, 3, 3, 1, 1, pad_mode)
+    if (pw.kh, pw.kw) != (3, 3) or not _L().conv2d_thin_lrelu_supported(C.byref(d)):
+        raise FmiError(f"the bf16 Output block takes a 3 x 3 convolution of a 32-channel map to at most 4 channels, got {c} -> {k} "
+                       f"k{pw.kh}x{pw.kw} on {h} x {w}")
+    y = torch.empty((n, oh, ow, k), device=x.device, dtype=torch.float32)
+    with _prof(f"conv_fwd_bf16|{n}x{h}x{w} {c}->{k} k3s1 thin", 2.0 * n * oh * ow * k * c * 9):
+        _L().conv2d_thin_lrelu_fwd_bf16(C.byref(d), _p(x), float(slope), _p(pw.wf), _p(bias), _p(y), act, _st())
+    return y
+
+
 class _Resize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, oh, ow, mean, std):

@@ -16,7 +16,9 @@ def scale_img(img, size):
 
 
 class ReferenceFill(nn.Module):
-    def __init__(self, mask_detector, encoder_params, decoder_params, use_att=True, out_size=(256, 256)):
+    def __init__(self, mask_detector, encoder_params, decoder_params, use_att=True, out_size=(256, 256), decoder_dtype=torch.float32):
+        """decoder_dtype=torch.bfloat16 (this build's extra, inference only): ResGenerator's decoder blocks, attention and Output block
+        on the bf16 kernels; both encoders, the guided attention and the latent path stay fp32, and so do all parameters"""
         super().__init__()
         self.mask_detector = mask_detector
         self.encoder_type = encoder_params.pop("type")
@@ -32,7 +34,7 @@ class ReferenceFill(nn.Module):
             self.ref_encoder = network.define_e(**encoder_params, encoder_type="ref")
         else:
             raise NotImplementedError
-        self.decoder = network.define_g(**decoder_params)
+        self.decoder = network.define_g(**decoder_params, compute_dtype=decoder_dtype)
         self.use_att = use_att
         if use_att:
             self.attention = ExampleGuidedAttention(encoder_params["img_f"])
@@ -45,6 +47,7 @@ class ReferenceFill(nn.Module):
         Variants of model.py:97-112: ``use_att=False`` blends the two feature maps with the rescaled mask and decodes from z_q
         alone; ``no_prior=True`` (what PICNet_inference.py:107 passes for --old_model) decodes without z and rescales the image to
         218 x 178 with scale_img instead of pooling."""
+        self.decoder.check_inference(src_image, ref_image)
         if src_mask is None:
             if self.mask_detector is None:
                 raise ValueError("src_mask is required when no mask_detector is attached")

@@ -116,6 +116,12 @@ def _norm_act(norm: nn.Module, x, slope, passthrough=False):
     return FF.instance_norm_act(x, norm.weight, norm.bias, norm.eps, slope, passthrough)
 
 
+def _norm_act_bf16(norm: nn.Module, x, slope):
+    if not isinstance(norm, nn.InstanceNorm2d) or not norm.affine or norm.track_running_stats:
+        raise NotImplementedError("only InstanceNorm2d(affine=True) is on the hot path")
+    return FF.instance_norm_act_bf16(x, norm.weight, norm.bias, norm.eps, slope)
+
+
 class _NhwcBlock(nn.Module):
     """public forward = NCHW-shaped tensors, like the reference; ``nhwc`` = channels-last fast path"""
 
@@ -207,8 +213,22 @@ class ResBlockDecoder(_NhwcBlock):
         self._slope = _slope(nonlinearity)
         self._pair_geometry = True  # both ConvTranspose2d are kernel 3 / stride 2 / padding 1 / output_padding 1 by construction
 
+    def _nhwc_bf16(self, x):
+        """inference on bf16 activations (ResGenerator(compute_dtype=torch.bfloat16)): IN + lrelu, conv1 with its bias in the output stage,
+        IN + lrelu, then conv2(h) + bypass(x) as ONE ConvTranspose2d of cat[h, x] and one bias pass -- no fp32 intermediate"""
+        if self._norms is None:
+            raise FF.FmiError("the bf16 ResBlockDecoder is the InstanceNorm form (decoder norm 'instance')")
+        c1, c2, cb = _conv(self.conv1), _conv(self.conv2), _conv(self.bypass)
+        h = _norm_act_bf16(self.model[0], x, self._slope)
+        h = FF.conv2d_bias_bf16(h, packed(c1), c1.bias, c1.padding[0])
+        h = _norm_act_bf16(self.model[3], h, self._slope)
+        bias = c2.bias if cb.bias is None else (cb.bias if c2.bias is None else FF.add(c2.bias, cb.bias))
+        return FF.conv_transpose2d_cat_bf16(h, packed(c2), x, packed(cb), bias)
+
     def nhwc(self, x):
         with weight_scope(self):
+            if x.dtype == torch.bfloat16:
+                return self._nhwc_bf16(x)
             c2, cb = _conv(self.conv2), _conv(self.bypass)
             if self._norms is None:
                 h, xp = run_conv(_conv(self.conv1), x, in_act=("apply", self._slope), passthrough=True)
@@ -241,6 +261,10 @@ class Output(_NhwcBlock):
     def nhwc(self, x):
         with weight_scope(self):
             conv = _conv(self.conv1)
+            if x.dtype == torch.bfloat16:  # bf16 decoder (inference): the fused pass or nothing, the image leaves in fp32
+                if not (self._pad == 1 and conv.stride == (1, 1) and conv.groups == 1 and conv.dilation == (1, 1)):
+                    raise FF.FmiError("the bf16 Output block takes the 3 x 3 stride-1 reflect-padded convolution only")
+                return FF.lrelu_conv2d_thin_bf16(x, packed(conv), conv.bias, self._slope, 1, FF.ACT_TANH)
             if self._pad == 1 and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.groups == 1 and conv.dilation == (1, 1):
                 # LeakyReLU, ReflectionPad2d, the convolution and tanh in one kernel (thin-output path); falls back to
                 # LeakyReLU + convolution by itself for shapes that path does not take
@@ -268,6 +292,10 @@ class Auto_Attn(nn.Module):
     def nhwc(self, x):
         with weight_scope(self):
             n, h, w, c = x.shape
+            if x.dtype == torch.bfloat16:  # bf16 decoder (inference): gamma * out + x is the attention kernel's epilogue
+                q = FF.conv2d_bias_bf16(x, packed(self.query_conv), self.query_conv.bias, 0)
+                xv = x.view(n, h * w, c)
+                return FF.self_attention_bf16(q.view(n, h * w, -1), xv, self.gamma, xv).view(n, h, w, c)
             q = run_conv(self.query_conv, x)
             (o,) = FF.self_attention(q.view(n, h * w, -1), [x.view(n, h * w, c)])
             return FF.scale_add_param(o.view(n, h, w, c), self.gamma, x)

@@ -23,8 +23,8 @@ def define_e(encoder_type="src", input_nc=3, ngf=64, z_nc=512, img_f=512, L=6, l
 
 
 def define_g(output_nc=3, ngf=64, z_nc=512, img_f=512, L=1, layers=5, norm="instance", activation="ReLU", use_spect=True,
-             use_coord=False, use_attn=True, init_type="orthogonal", gpu_ids=[]):
-    net = ResGenerator(output_nc, ngf, z_nc, img_f, L, layers, norm, activation, use_spect, use_coord, use_attn)
+             use_coord=False, use_attn=True, init_type="orthogonal", gpu_ids=[], compute_dtype=torch.float32):
+    net = ResGenerator(output_nc, ngf, z_nc, img_f, L, layers, norm, activation, use_spect, use_coord, use_attn, compute_dtype=compute_dtype)
     return init_net(net, init_type, activation, gpu_ids)
 
 
@@ -91,11 +91,16 @@ class ResEncoder(nn.Module):
 
 
 class ResGenerator(nn.Module):
-    """network.py:181-307."""
+    """network.py:181-307.  ``compute_dtype=torch.bfloat16`` (this build's extra, inference only): the latent ResBlocks stay fp32,
+    ``encoded + f`` is cast to bf16 once, and decoder0.., attn1 and the Output block run on the bf16 kernels; the image leaves the
+    Output block in fp32.  Parameters, state_dict keys and SpectralNorm state are those of the fp32 build."""
 
     def __init__(self, output_nc=3, ngf=64, z_nc=128, img_f=1024, L=1, layers=6, norm="batch", activation="ReLU",
-                 use_spect=True, use_coord=False, use_attn=False):
+                 use_spect=True, use_coord=False, use_attn=False, compute_dtype=torch.float32):
         super().__init__()
+        if compute_dtype not in (torch.float32, torch.bfloat16):
+            raise FF.FmiError(f"compute_dtype must be torch.float32 or torch.bfloat16, got {compute_dtype}")
+        self.compute_dtype = compute_dtype
         self.layers, self.L, self.use_attn = layers, L, use_attn
         norm_layer = get_norm_layer(norm_type=norm)
         nonlinearity = get_nonlinearity_layer(activation_type=activation)
@@ -113,8 +118,46 @@ class ResGenerator(nn.Module):
                 setattr(self, "out" + str(i), Output(ch, output_nc, 3, None, nonlinearity, use_spect, use_coord))
             if i == 1 and use_attn:
                 setattr(self, "attn" + str(i), Auto_Attn(ch, None))
+            if compute_dtype == torch.bfloat16:
+                self._check_bf16_block(i, prev_ch, ch, norm, use_attn)
+        if compute_dtype == torch.bfloat16:
+            for name, block in self.named_children():
+                if name.startswith(("decoder", "out")):
+                    for m in block.modules():
+                        if isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
+                            object.__setattr__(m, "_fmi_no_w3", True)  # these run on bf16 activations: no fp32 piece images of their packs
+                elif name.startswith("attn"):  # Auto_Attn.model never runs
+                    object.__setattr__(block.query_conv, "_fmi_no_w3", True)
+
+    def _check_bf16_block(self, i, prev_ch, ch, norm, use_attn):
+        """the widths the bf16 kernels take, refused at construction: there is no fp32 detour for a block that does not fit"""
+        why = None
+        if norm != "instance":
+            why = f"decoder norm 'instance' (got {norm!r})"
+        elif prev_ch % 64:
+            why = f"decoder{i}.conv1 input channels % 64 == 0 (got {prev_ch})"
+        elif ch % 8 or (ch + prev_ch) % 32:
+            why = f"decoder{i} widths with hidden % 8 == 0 and (hidden + input) % 32 == 0 (got {ch} + {prev_ch})"
+        elif i > self.layers - 2 and ch != 32:
+            why = f"32 channels into out{i} (got {ch})"
+        elif i == 1 and use_attn and (ch // 4, ch) not in ((64, 256), (32, 128)):
+            why = f"(d_qk, C) in {{(64, 256), (32, 128)}} at attn{i} (got ({ch // 4}, {ch}))"
+        if why:
+            raise FF.FmiError(f"ResGenerator(compute_dtype=torch.bfloat16) needs {why}; these channel counts run in fp32 only")
+
+    def check_inference(self, *inputs):
+        """the bf16 decoder has no backward: refuse, before any device work, a call that autograd would record"""
+        if self.compute_dtype == torch.bfloat16 and torch.is_grad_enabled() and (
+                any(t is not None and t.requires_grad for t in inputs) or any(p.requires_grad for p in self.parameters())):
+            raise FF.FmiError("the bf16 decoder (compute_dtype=torch.bfloat16) is inference only -- no bf16 backward exists: call it under "
+                              "torch.no_grad(), or build the generator with compute_dtype=torch.float32 to train")
 
     def nhwc(self, encoded, z=None):
+        bf16 = self.compute_dtype == torch.bfloat16
+        self.check_inference(encoded, z)
+        if bf16 and self.use_attn and self.layers > 1 and (16 * encoded.shape[1] * encoded.shape[2]) % 128:
+            raise FF.FmiError(f"the bf16 attention at attn1 needs a token count that is a multiple of 128: a {encoded.shape[1]} x "
+                              f"{encoded.shape[2]} feature map gives {16 * encoded.shape[1] * encoded.shape[2]} tokens")
         with weight_scope(self):
             if z is not None:
                 f = self.generator.nhwc(z)
@@ -123,6 +166,8 @@ class ResGenerator(nn.Module):
                 out = FF.add(encoded, f)
             else:
                 out = encoded
+            if bf16:
+                out = out.to(torch.bfloat16)  # the one cast: everything from decoder0 to the Output block's input is bf16
             output = None
             for i in range(self.layers):
                 out = getattr(self, "decoder" + str(i)).nhwc(out)

@@ -189,6 +189,11 @@ int fmi_conv2d_thin_wgrad_f32(const fmi_conv_desc* d, const float* x, const floa
 int fmi_conv2d_thin_lrelu_supported(const fmi_conv_desc* d);
 int fmi_conv2d_thin_lrelu_fwd_f32(const fmi_conv_desc* d, const float* x, float in_slope, const float* wf, const float* bias, float* y, int act,
                                   void* stream);
+/* The forward of that block from a bf16 activation (the bf16 PICNet decoder, inference): x [N,H,W,32] bf16 with a pixel pitch of
+ * d->x_cstride bf16 elements (a multiple of 8), read as 16-byte chunks of 8 channels; lrelu, taps, bias and act in fp32, y the fp32
+ * image [N,H,W,K].  Same geometry as fmi_conv2d_thin_lrelu_supported (ragged H / W included); x 16-byte aligned; else FMI_ERR_UNSUPPORTED. */
+int fmi_conv2d_thin_lrelu_fwd_bf16(const fmi_conv_desc* d, const uint16_t* x, float in_slope, const float* wf, const float* bias, float* y,
+                                   int act, void* stream);
 int fmi_conv2d_thin_lrelu_dgrad_f32(const fmi_conv_desc* d, const float* dy, const float* wt, const float* x, float in_slope, float* dx,
                                     void* stream);
 int fmi_conv2d_thin_lrelu_wgrad_f32(const fmi_conv_desc* d, const float* x, float in_slope, const float* dy, float* dwf, float* dbias,
@@ -343,6 +348,18 @@ int fmi_attention_fwd_f32(const float* q, const float* v1, const float* v2, floa
 int fmi_attention_fwd_waves(int N, int T);
 int fmi_attention_bwd_structure(int N, int T);
 
+/* The same forward on bf16 operands (inference; no backward): q [N,T,D], v [N,T,C] and o [N,T,C] bf16, scores / running maximum / row
+ * sum / output accumulators fp32, P rounded to bf16 only as the matrix operand of P V (the row sum adds the fp32 values).
+ * Optional epilogue o = gamma[0] * O + residual, computed in fp32 before the one rounding of o: gamma a 1-element fp32 DEVICE tensor,
+ * residual bf16 in o's layout (Auto_Attn's gamma * out + x, base_function.py:439); both NULL or both given.  lse [N,T] fp32 as above
+ * (may be NULL).  waves: 0 = the shape dispatch fmi_attention_fwd_bf16_waves(N, T) (8 if T % 256 == 0 and (T/256) N >= 256, else 4);
+ * 4 or 8 request that workgroup form explicitly (8 needs T % 256 == 0) -- same bits either way is NOT promised, same accuracy is.
+ * Supported: T % 128 == 0, (D, C) in {(64, 256), (32, 128)}, N <= 65535; else FMI_ERR_UNSUPPORTED before any launch.  NULL q / v / o,
+ * a lone gamma or residual, q / v / o / residual off 16-byte alignment: FMI_ERR_BAD_ARG.  There is no fp32 detour. */
+int fmi_attention_fwd_bf16_waves(int N, int T);
+int fmi_attention_fwd_bf16(const uint16_t* q, const uint16_t* v, uint16_t* o, float* lse, const float* gamma, const uint16_t* residual,
+                           int N, int T, int D, int C, int waves, void* stream);
+
 /* The same forward with the bf16 pieces of K (= q) and V cut ONCE per pass into a key-tile image (layout: csrc/attention.hip, AttKImg)
  * that every workgroup streams into LDS by LDS-DMA; bit-identical results (the same pieces in the same MFMA order).
  *   fmi_attention_fwd_uses_pieces   1 where the library's shape dispatch takes this path (T % 256 == 0, (T/256) N >= 256, D in {32,64},
@@ -479,6 +496,9 @@ int fmi_lpips_layer_bwd_f32(const float* fx, const float* fy, const float* w, co
  * unet_parts.py:70 and example_guided_att.py:37 torch.cat) */
 int fmi_copy_channels_f32(const float* src, float* dst, int64_t rows, int src_stride, int src_c0, int dst_stride, int dst_c0, int c,
                           void* stream);
+/* the same for bf16 maps; strides, offsets and c in bf16 elements, all multiples of 8, 16-byte aligned bases (else FMI_ERR_UNSUPPORTED) */
+int fmi_copy_channels_bf16(const uint16_t* src, uint16_t* dst, int64_t rows, int src_stride, int src_c0, int dst_stride, int dst_c0, int c,
+                           void* stream);
 /* nn.AdaptiveAvgPool2d for any input / output size (model.py:79,111 on non-1024 decoder outputs; psp.py:33 on outputs smaller than
  * 256; id_loss.py:19 188 -> 112): window i of an axis = [floor(i L / OL), ceil((i + 1) L / OL)).  NHWC. */
 int fmi_adaptive_avgpool_f32(const float* x, float* y, int N, int H, int W, int C, int OH, int OW, void* stream);
