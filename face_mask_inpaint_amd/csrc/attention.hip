@@ -2,36 +2,26 @@
 //      A = softmax_j(q_i . q_j)   (queries = keys, no scaling)      O = A V        V = [V1 | V2] along channels
 // in exact fp32 on the matrix cores, flash style: the [T x T] map (1 GiB per image at T = 16384) is never formed.
 //
-// MI355X mapping
-//  * one 256-thread workgroup = 4 waves = 128 queries; each wave owns 32 queries, ONE PER LANE COLUMN: the score tile is
-//    computed transposed, S^T[key][query] = K Q^T (A = K tile from LDS, B = the wave's Q fragment held in registers for
-//    the whole kernel), so a lane holds 16 keys of its own query.  Row max / row sum are then in-lane reductions plus one
+// MI355X mapping of the forward, attn_fwd_x6_kernel (the backward kernels are described where they stand)
+//  * one workgroup = NW waves (2, 4 or 8: fmi_attention_fwd_waves) = NW x 32 queries; each wave owns 32 queries, ONE PER LANE COLUMN:
+//    the score tile is computed transposed, S^T[key][query] = K Q^T (A = K tile from LDS, B = the wave's Q fragment held in registers
+//    for the whole kernel), so a lane holds 16 keys of its own query.  Row max / row sum are then in-lane reductions plus one
 //    exchange with lane^32, and the exponentiated tile is ALREADY the B operand of the second product
 //    O^T[c][query] += V^T[c][key] P^T[key][query] (k-index permuted identically on both operands): P never touches LDS.
-//  * O^T accumulators: C/32 tiles x 16 registers per lane (128 for 256 channels); one wave per SIMD, so the kernel runs
-//    with the 512-register budget (launch_bounds(256, 1)).
-//  * K is staged transposed ([d][key], +1 pad) and V row-major in LDS, double buffered, filled through registers
-//    (prefetch of tile t+1 is issued before the 160 MFMAs of tile t), one barrier per 32-key tile.
+//  * every product runs on the bf16 matrix pipe: six bf16 MFMAs of K = 16 on exact three-way splits of the fp32 operands (x6.h).  The
+//    Q pieces stay in registers, P is cut in registers, the K / V pieces lie in LDS.
+//  * O^T accumulators: C/32 tiles x 16 registers per lane (128 for 256 channels); one workgroup per CU, so a wave may use the
+//    512-register budget (launch_bounds(NW * 64, 1)).
+//  * a stage is the three bf16 piece images of 32 keys' K and V rows, double buffered in dynamic LDS (opted in: up to 82 KB), one barrier
+//    per tile.  The two- and four-wave forms cut the pieces on the way from the staging registers into LDS (the loads of tile t+1 are
+//    issued before the MFMAs of tile t); the eight-wave form streams a key-tile image, cut once per pass, by LDS-DMA.
 //  * online softmax with a LAZY reference maximum: the accumulators are rescaled only when a tile's maximum exceeds the
 //    reference by more than 20 (fp32 has the range; p <= e^20), which happens in the first tiles only; the branch is
 //    wave-uniform.
 #include "common.h"
 #include "x6.h"
 #include <cstdlib>
-
-// > 64 KB of dynamic LDS must be opted into per kernel AND per device (hipFuncSetAttribute acts on the current device's code object):
-// one atomic flag per (kernel instantiation, device ordinal), safe from the forward and the autograd thread alike
-struct fmi_attr_flags {
-  unsigned char done[64];
-};
-static inline bool fmi_attr_needed(fmi_attr_flags& f, int& dev) {
-  dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return true;
-  return !__atomic_load_n(&f.done[dev], __ATOMIC_ACQUIRE);
-}
-static inline void fmi_attr_mark(fmi_attr_flags& f, int dev) {
-  if (dev >= 0 && dev < 64) __atomic_store_n(&f.done[dev], (unsigned char)1, __ATOMIC_RELEASE);
-}
+#include <type_traits>
 
 #define ATT_THR 20.0f
 
@@ -54,139 +44,9 @@ __device__ __forceinline__ void att_gload(float4 (&rk)[NKL], float4 (&rv)[NVL], 
                      : *reinterpret_cast<const float4*>(v2b + (int64_t)(k0 + key) * C2 + (c - C1));
   }
 }
-template <int D, int CT, int NKL, int NVL, int LDK, int NTH>
-__device__ __forceinline__ void att_lstore(const float4 (&rk)[NKL], const float4 (&rv)[NVL], float* __restrict__ kt,
-                                           float* __restrict__ vs, int tid) {
-#pragma unroll
-  for (int i = 0; i < NKL; ++i) {
-    const int f = tid + NTH * i;
-    if (f < 8 * D) {
-      const int key = f / (D / 4), dd = (f % (D / 4)) * 4;
-      kt[(dd + 0) * LDK + key] = rk[i].x;
-      kt[(dd + 1) * LDK + key] = rk[i].y;
-      kt[(dd + 2) * LDK + key] = rk[i].z;
-      kt[(dd + 3) * LDK + key] = rk[i].w;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < NVL; ++i) {
-    const int f = tid + NTH * i;
-    *reinterpret_cast<float4*>(vs + f * 4) = rv[i];  // f*4 = key*CT + c
-  }
-}
-
-// NW waves per workgroup, each owning 32 queries; all share the staged key / value tiles.  NW = 8 for long sequences: the 82 KB of LDS
-// allow one workgroup per CU, and with four waves every SIMD held ONE wave whose softmax (exp, max, rescale) left the matrix pipe
-// idle; eight waves put two on each SIMD.  NW = 2 for short ones (T = 1024: 64 workgroups of four waves filled a quarter of the chip).
-template <int D, int NCT, int NW>
-__global__ void __launch_bounds__(NW * 64, 1) attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ v1,
-                                                          const float* __restrict__ v2, float* __restrict__ o1,
-                                                          float* __restrict__ o2, float* __restrict__ lse, int T, int C1,
-                                                          int C2) {
-  constexpr int CT = NCT * 32;        // total value channels
-  constexpr int LDK = 33;             // Kt row pitch (floats)
-  constexpr int KT_FLOATS = D * LDK, VS_FLOATS = 32 * CT;
-  constexpr int NTH = NW * 64;
-  constexpr int NKL = (8 * D + NTH - 1) / NTH;                 // float4 loads per thread for a K tile
-  constexpr int NVL = (8 * CT) / NTH;                          // float4 loads per thread for a V tile
-  static_assert((8 * CT) % NTH == 0, "whole float4 passes over the V tile");
-  __shared__ __attribute__((aligned(16))) float lds[2 * (KT_FLOATS + VS_FLOATS)];
-  float* Kt = lds;
-  float* Vs = lds + 2 * KT_FLOATS;
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, l31 = lane & 31, lh = lane >> 5;
-  const int n = blockIdx.y;
-  const int q0 = blockIdx.x * (NW * 32) + wid * 32;
-  const float* qb = q + (int64_t)n * T * D;
-  const float* v1b = v1 + (int64_t)n * T * C1;
-  const float* v2b = v2 ? v2 + (int64_t)n * T * C2 : nullptr;
-
-  // this lane's query fragment: B[k = dd][j = query], dd = 2s + lh
-  float qf[D / 2];
-#pragma unroll
-  for (int s = 0; s < D / 2; ++s) qf[s] = qb[(int64_t)(q0 + l31) * D + 2 * s + lh];
-
-  f32x16 acc[NCT];
-#pragma unroll
-  for (int c = 0; c < NCT; ++c)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
-  float mref = -INFINITY, lsum = 0.f;
-
-  float4 rk[NKL], rv[NVL];
-  att_gload<D, CT, NKL, NVL, NTH>(rk, rv, qb, v1b, v2b, C1, C2, 0, tid);
-  att_lstore<D, CT, NKL, NVL, LDK, NTH>(rk, rv, Kt, Vs, tid);
-  __syncthreads();
-  int buf = 0;
-  for (int k0 = 0; k0 < T; k0 += 32) {
-    // unconditional prefetch (the last iteration re-reads its own tile): a conditional one sends rk/rv to scratch
-    att_gload<D, CT, NKL, NVL, NTH>(rk, rv, qb, v1b, v2b, C1, C2, k0 + 32 < T ? k0 + 32 : k0, tid);
-    const float* kt = Kt + buf * KT_FLOATS + l31;
-    const float* vs = Vs + buf * VS_FLOATS + l31;
-    // S^T[key][query] for 32 keys x this wave's 32 queries
-    f32x16 st;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) st[r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < D / 2; ++s) st = __builtin_amdgcn_mfma_f32_32x32x2f32(kt[(2 * s + lh) * LDK], qf[s], st, 0, 0, 0);
-    // online softmax, one query per lane column (keys split over the lane pair l, l^32)
-    float tmax = st[0];
-#pragma unroll
-    for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, st[r]);
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    if (__any(tmax > mref + ATT_THR)) {
-      const float mnew = fmaxf(mref, tmax);
-      const float alpha = __expf(mref - mnew);
-#pragma unroll
-      for (int c = 0; c < NCT; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[c][r] *= alpha;
-      lsum *= alpha;
-      mref = mnew;
-    }
-    float psum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      st[r] = __expf(st[r] - mref);
-      psum += st[r];
-    }
-    psum += __shfl_xor(psum, 32, 64);
-    lsum += psum;
-    // O^T[c][query] += V^T[c][key] P^T[key][query]; MFMA step s of half lh carries key (s&3) + 8*(s>>2) + 4*lh
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const int key = (s & 3) + 8 * (s >> 2) + 4 * lh;
-#pragma unroll
-      for (int c = 0; c < NCT; ++c) acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(vs[key * CT + c * 32], st[s], acc[c], 0, 0, 0);
-    }
-    att_lstore<D, CT, NKL, NVL, LDK, NTH>(rk, rv, Kt + (buf ^ 1) * KT_FLOATS, Vs + (buf ^ 1) * VS_FLOATS, tid);
-    __syncthreads();
-    buf ^= 1;
-  }
-
-  // epilogue: register r of tile c is channel c*32 + (r&3) + 8*(r>>2) + 4*lh of query q0 + l31
-  const float inv = 1.f / lsum;
-  const int64_t row = (int64_t)n * T + q0 + l31;
-#pragma unroll
-  for (int c = 0; c < NCT; ++c) {
-    const int cbase = c * 32;
-    float* ob = (cbase < C1) ? o1 + row * C1 + cbase : o2 + row * C2 + (cbase - C1);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      float4 o;
-      o.x = acc[c][4 * g + 0] * inv;
-      o.y = acc[c][4 * g + 1] * inv;
-      o.z = acc[c][4 * g + 2] * inv;
-      o.w = acc[c][4 * g + 3] * inv;
-      *reinterpret_cast<float4*>(ob + 8 * g + 4 * lh) = o;
-    }
-  }
-  if (lh == 0 && lse) lse[row] = mref + logf(lsum);
-}
-
 
 // =====================================================================================================
-// Forward on the bf16 matrix pipe (x6.h): the same flash structure, every product as six bf16 MFMAs of K = 16 on exact three-way
+// Forward on the bf16 matrix pipe (x6.h): the flash structure above, every product as six bf16 MFMAs of K = 16 on exact three-way
 // splits of the fp32 operands.
 //  * the K / V tile of 32 keys is split into three bf16 images each -- on its way from the staging registers into LDS (IMG = false: the
 //    two- and four-wave forms, D = 16), or once per pass into the key-tile image that the eight-wave form streams by LDS-DMA (IMG = true,
@@ -241,6 +101,13 @@ __global__ void __launch_bounds__(256) attn_cut_ktile_kernel(const float* __rest
   }
 }
 
+// NW waves per workgroup, each owning 32 queries; all share the staged key / value tiles.  NW = 8 for long sequences: the 82 KB of LDS
+// allow one workgroup per CU, and with four waves every SIMD held ONE wave whose softmax (exp, max, rescale) left the matrix pipe
+// idle; eight waves put two on each SIMD.  NW = 2 for short ones (T = 1024: 64 workgroups of four waves filled a quarter of the chip).
+// Dynamic LDS: two stages, each the three K and three V piece images of 32 keys, or one block of the key-tile image.
+template <int D, int NCT, bool IMG>
+constexpr int attn_fwd_x6_lds = IMG ? 2 * AttKImg<D, NCT * 32>::BLK : 2 * 3 * 32 * ((2 * D + 16) + (2 * NCT * 32 + 64));
+
 template <int D, int NCT, int NW, bool IMG>
 __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_x6_kernel(const float* __restrict__ q, const float* __restrict__ v1,
                                                                  const float* __restrict__ v2, const unsigned char* __restrict__ img,
@@ -255,7 +122,8 @@ __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_x6_kernel(const float* __
   constexpr int NVL = (8 * CT) / NTH;                       // float4 loads per thread for a V tile
   static_assert((8 * CT) % NTH == 0, "whole float4 passes over the V tile");
   static_assert(D % 16 == 0, "whole bf16 k-steps");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_x6[];
+  static_assert(1 * STAGE + STAGE == attn_fwd_x6_lds<D, NCT, IMG>, "the host passes the bytes this carve ends at");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_x6[];  // [2][STAGE]
   typedef __attribute__((address_space(3))) unsigned char* lds_ptr;
   const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_ptr)smem_x6;
 
@@ -448,6 +316,22 @@ __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_x6_kernel(const float* __
   if (lh == 0 && lse) lse[row] = mref + logf(lsum);
 }
 
+// The (D, C / 32) pairs the kernels are instantiated for, in one place: calls f(D, C / 32) with the two values as
+// std::integral_constant<int, ..>; false: not a supported pair.  FWD16: also the two D = 16 pairs, which only the forward has.
+template <bool FWD16, class F>
+static bool att_dispatch(int D, int nct, F&& f) {
+  using std::integral_constant;
+  if (D == 64 && nct == 8) return f(integral_constant<int, 64>{}, integral_constant<int, 8>{}), true;
+  if (D == 32 && nct == 8) return f(integral_constant<int, 32>{}, integral_constant<int, 8>{}), true;
+  if (D == 32 && nct == 4) return f(integral_constant<int, 32>{}, integral_constant<int, 4>{}), true;
+  if (D == 64 && nct == 4) return f(integral_constant<int, 64>{}, integral_constant<int, 4>{}), true;
+  if constexpr (FWD16) {
+    if (D == 16 && nct == 2) return f(integral_constant<int, 16>{}, integral_constant<int, 2>{}), true;
+    if (D == 16 && nct == 4) return f(integral_constant<int, 16>{}, integral_constant<int, 4>{}), true;
+  }
+  return false;
+}
+
 // The forward's shape dispatch, in one place: waves per workgroup (each owns 32 queries).  Eight where whole 256-query workgroups still
 // fill the chip, two where even 128-query ones would not, else four.  Pure host arithmetic; the tests assert it per shape.
 extern "C" int fmi_attention_fwd_waves(int N, int T) {
@@ -464,36 +348,19 @@ extern "C" int fmi_attention_fwd_f32(const float* q, const float* v1, const floa
   const int nct = (C1 + C2) / 32;
   const dim3 grid(T / (nw * 32), N), block(nw * 64);
   hipStream_t st = (hipStream_t)stream;
-#if FMI_X6
-#define ATT_LAUNCH1(DD, NN, WW)                                                                                                \
-  do {                                                                                                                        \
-    constexpr int lds_bytes = 2 * 3 * 32 * ((2 * DD + 16) + (2 * NN * 32 + 64));                                               \
-    static fmi_attr_flags attr_set{}; int attr_set_dev;\
-    if (fmi_attr_needed(attr_set, attr_set_dev)) {                                                                                                          \
-      if (hipFuncSetAttribute((const void*)attn_fwd_x6_kernel<DD, NN, WW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) \
-        return FMI_ERR_LAUNCH;                                                                                                \
-      fmi_attr_mark(attr_set, attr_set_dev);                                                                                                        \
-    }                                                                                                                         \
-    hipLaunchKernelGGL((attn_fwd_x6_kernel<DD, NN, WW, false>), grid, block, lds_bytes, st, q, v1, v2, (const unsigned char*)nullptr, o1, o2, lse, T, C1, C2); \
-  } while (0)
-#else
-#define ATT_LAUNCH1(DD, NN, WW) hipLaunchKernelGGL((attn_fwd_kernel<DD, NN, WW>), grid, block, 0, st, q, v1, v2, o1, o2, lse, T, C1, C2)
-#endif
-#define ATT_LAUNCH(DD, NN)                 \
-  do {                                     \
-    if (nw == 8) ATT_LAUNCH1(DD, NN, 8);   \
-    else if (nw == 2) ATT_LAUNCH1(DD, NN, 2); \
-    else ATT_LAUNCH1(DD, NN, 4);           \
-  } while (0)
-  if (D == 64 && nct == 8) ATT_LAUNCH(64, 8);
-  else if (D == 32 && nct == 8) ATT_LAUNCH(32, 8);
-  else if (D == 32 && nct == 4) ATT_LAUNCH(32, 4);
-  else if (D == 64 && nct == 4) ATT_LAUNCH(64, 4);
-  else if (D == 16 && nct == 2) ATT_LAUNCH(16, 2);
-  else if (D == 16 && nct == 4) ATT_LAUNCH(16, 4);
-  else return FMI_ERR_UNSUPPORTED;
-#undef ATT_LAUNCH
-#undef ATT_LAUNCH1
+  int rc = FMI_OK;
+  const bool known = att_dispatch<true>(D, nct, [&](auto d, auto n) {
+    constexpr int DD = decltype(d)::value, NN = decltype(n)::value;
+    auto launch = [&](auto w) {
+      rc = fmi_launch_lds<attn_fwd_x6_kernel<DD, NN, decltype(w)::value, false>>(grid, block, attn_fwd_x6_lds<DD, NN, false>, st, q, v1, v2,
+                                                                                 (const unsigned char*)nullptr, o1, o2, lse, T, C1, C2);
+    };
+    if (nw == 8) launch(std::integral_constant<int, 8>{});
+    else if (nw == 2) launch(std::integral_constant<int, 2>{});
+    else launch(std::integral_constant<int, 4>{});
+  });
+  if (!known) return FMI_ERR_UNSUPPORTED;
+  if (rc != FMI_OK) return rc;
   return fmi_launch_status();
 }
 
@@ -510,26 +377,33 @@ extern "C" int fmi_attention_fwd_f32(const float* q, const float* v1, const floa
 // the query-side product needs dS transposed, through a private 4 KB LDS tile.  The query-side dQ tiles are added with
 // fp32 atomics (whole 128-byte rows per wave instruction).
 // =====================================================================================================
+// dynamic LDS of attn_bwd_kernel: the resident key block and one query tile (V / gO and K / Q rows at odd pitches, lse and delta), the
+// four waves' exchange tiles and two transposed dS tiles
+template <int D, int NCT>
+constexpr int attn_bwd_lds = (int)sizeof(float) * (2 * 32 * (NCT * 32 + 1) + 2 * 32 * (D + 1) + 64 + 4 * 2 * 1024 + 2 * 32 * 33);
+
 template <int D, int NCT>  // NCT = (C1 + C2) / 32, multiple of 4
 __global__ void __launch_bounds__(256, 1) attn_bwd_kernel(const float* __restrict__ q, const float* __restrict__ v1,
                                                           const float* __restrict__ v2, const float* __restrict__ g1,
                                                           const float* __restrict__ g2, const float* __restrict__ lse,
                                                           const float* __restrict__ delta, float* __restrict__ gv1,
                                                           float* __restrict__ gv2, float* __restrict__ gq, int T, int C1, int C2, int kb0) {
-  constexpr int CT = NCT * 32, CW = CT / 4, NCW = CW / 32, DW = D / 4;
+  constexpr int CT = NCT * 32, CW = CT / 4, NCW = CW / 32;
   constexpr int LDV = CT + 1, LDQ = D + 1;
   constexpr int NQL = (8 * D) / 256 > 0 ? (8 * D) / 256 : 1, NVL = (8 * CT) / 256;
   constexpr int NDT = D / 32;  // 32-wide d tiles (1 or 2)
-  constexpr bool X6S = FMI_X6;  // score tile on the bf16 pipe, in the forward's arithmetic (below)
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr int KJ = 32 * LDV, DOI = KJ + 32 * LDQ, QI = DOI + 32 * LDV, LSE = QI + 32 * LDQ, DEL = LSE + 32, EXO = DEL + 32,
+                DST = EXO + 4 * 2 * 1024;  // offsets (floats)
+  static_assert((int)sizeof(float) * (DST + 2 * 32 * 33) == attn_bwd_lds<D, NCT>, "the host passes the bytes this carve ends at");
   float* Vj = smem;                   // [32][LDV]
-  float* Kj = Vj + 32 * LDV;          // [32][LDQ]
-  float* dOi = Kj + 32 * LDQ;         // [32][LDV]
-  float* Qi = dOi + 32 * LDV;         // [32][LDQ]
-  float* lse_i = Qi + 32 * LDQ;       // [32]
-  float* del_i = lse_i + 32;          // [32]
-  float* EX = del_i + 32;             // [4][2][16][64]
-  float* dsT = EX + 4 * 2 * 1024;     // [2][32][33]
+  float* Kj = smem + KJ;              // [32][LDQ]
+  float* dOi = smem + DOI;            // [32][LDV]
+  float* Qi = smem + QI;              // [32][LDQ]
+  float* lse_i = smem + LSE;          // [32]
+  float* del_i = smem + DEL;          // [32]
+  float* EX = smem + EXO;             // [4][2][16][64]: the second [16][64] of a wave holds its partial dP tile (the first is unused)
+  float* dsT = smem + DST;            // [2][32][33]
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, l31 = lane & 31, lh = lane >> 5;
   const int n = blockIdx.y, j0 = ((int)blockIdx.x + kb0) * 32;  // kb0: key-block offset of this launch (reproducible mode: one key block per launch)
@@ -564,7 +438,6 @@ __global__ void __launch_bounds__(256, 1) attn_bwd_kernel(const float* __restric
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc_dk[r] = 0.f;
   const int cbase = wid * CW;            // this wave's value-channel slice
-  const int dbase = wid * DW;            // this wave's d slice of the score product
   const bool dk_role = wid < NDT;        // waves 0..NDT-1: key-side tile wid;  waves 2..2+NDT-1: query-side tile wid-2
   const bool dq_role = wid >= 2 && wid - 2 < NDT;
   const int dt = dk_role ? wid : wid - 2;
@@ -618,14 +491,12 @@ __global__ void __launch_bounds__(256, 1) attn_bwd_kernel(const float* __restric
   // accumulator chained over d in steps of 16, the same six products per step -- which makes a key's score with itself (the entry that
   // dominates a sharp row) the same bits as in the forward.  The resident keys' pieces stay in registers.
   bf16x8_t kpc[D / 16][3];
-  if constexpr (X6S) {
 #pragma unroll
-    for (int kk = 0; kk < D / 16; ++kk) {
-      float f[8];
+  for (int kk = 0; kk < D / 16; ++kk) {
+    float f[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) f[j] = Kj[l31 * LDQ + 16 * kk + 8 * lh + j];
-      split3_bf16(f, kpc[kk]);
-    }
+    for (int j = 0; j < 8; ++j) f[j] = Kj[l31 * LDQ + 16 * kk + 8 * lh + j];
+    split3_bf16(f, kpc[kk]);
   }
   for (int i0 = 0; i0 < T; i0 += 32) {
     gload(i0 + 32 < T ? i0 + 32 : i0);  // unconditional prefetch of the next query tile into registers
@@ -636,43 +507,30 @@ __global__ void __launch_bounds__(256, 1) attn_bwd_kernel(const float* __restric
       sp[r] = 0.f;
       dp[r] = 0.f;
     }
-    if constexpr (X6S) {
 #pragma unroll
-      for (int kk = 0; kk < D / 16; ++kk) {
-        float f[8];
+    for (int kk = 0; kk < D / 16; ++kk) {
+      float f[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = Qi[l31 * LDQ + 16 * kk + 8 * lh + j];
-        bf16x8_t qpc[3];
-        split3_bf16(f, qpc);
-        sp = mfma_x6(qpc, kpc[kk], sp);
-      }
-    } else {
-#pragma unroll
-      for (int s = 0; s < DW / 2; ++s)
-        sp = __builtin_amdgcn_mfma_f32_32x32x2f32(Qi[l31 * LDQ + dbase + 2 * s + lh], Kj[l31 * LDQ + dbase + 2 * s + lh], sp, 0, 0, 0);
+      for (int j = 0; j < 8; ++j) f[j] = Qi[l31 * LDQ + 16 * kk + 8 * lh + j];
+      bf16x8_t qpc[3];
+      split3_bf16(f, qpc);
+      sp = mfma_x6(qpc, kpc[kk], sp);
     }
 #pragma unroll
     for (int s = 0; s < CW / 2; ++s)
       dp = __builtin_amdgcn_mfma_f32_32x32x2f32(dOi[l31 * LDV + cbase + 2 * s + lh], Vj[l31 * LDV + cbase + 2 * s + lh], dp, 0, 0, 0);
-    // ---- 2. exchange: every wave needs the full dP tile (and the full S tile where it was split over d)
+    // ---- 2. exchange: every wave needs the full dP tile
     {
       float* ex = EX + wid * 2048 + lane;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if constexpr (!X6S) ex[r * 64] = sp[r];
-        ex[1024 + r * 64] = dp[r];
-      }
+      for (int r = 0; r < 16; ++r) ex[1024 + r * 64] = dp[r];
     }
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      float a = 0.f, b = 0.f;
+      float b = 0.f;
 #pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        if constexpr (!X6S) a += EX[w * 2048 + r * 64 + lane];
-        b += EX[w * 2048 + 1024 + r * 64 + lane];
-      }
-      if constexpr (!X6S) sp[r] = a;
+      for (int w = 0; w < 4; ++w) b += EX[w * 2048 + 1024 + r * 64 + lane];
       dp[r] = b;
     }
     // ---- 3. P and dS (register r of half lh is query (r&3) + 8*(r>>2) + 4*lh)
@@ -742,195 +600,13 @@ __global__ void __launch_bounds__(256, 1) attn_bwd_kernel(const float* __restric
 }
 
 // =====================================================================================================
-// Backward, second structure (used when it fits): every wave owns its OWN block of 32 keys with ALL value channels and
-// keeps that key block's V and K fragments in registers (the lane-constant B operands of the score and dP products), so
+// Backward, second structure (used when it fits), on the bf16 matrix pipe (x6.h): every wave owns its OWN block of 32 keys with ALL
+// value channels and keeps that key block's V rows in registers, so
 //  * nothing is exchanged between waves before the softmax backward (the first structure above exchanges partial tiles),
 //  * one query tile staged in LDS feeds four key blocks (4x fewer L2 reads of gO / Q),
 //  * the query-side dQ tiles of the four key blocks are summed through LDS first: 4x fewer fp32 atomics
 //    (rocprofv3 WRITE_SIZE showed 17 GB of atomic traffic per launch for the first structure at T = 16384).
-// One wave per SIMD, ~420 of the 512 registers; 352 MFMAs per wave between barriers.
-// =====================================================================================================
-template <int D, int NCT>
-__global__ void __launch_bounds__(256, 1) attn_bwd2_kernel(const float* __restrict__ q, const float* __restrict__ v1,
-                                                           const float* __restrict__ v2, const float* __restrict__ g1,
-                                                           const float* __restrict__ g2, const float* __restrict__ lse,
-                                                           const float* __restrict__ delta, float* __restrict__ gv1,
-                                                           float* __restrict__ gv2, float* __restrict__ gq, int T, int C1, int C2, int kb0) {
-  constexpr int CT = NCT * 32, LDV = CT + 1, LDQ = D + 1, NDT = D / 32;
-  constexpr int NQL = (8 * D) / 256 > 0 ? (8 * D) / 256 : 1, NVL = (8 * CT) / 256;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* dOi = smem;                   // [32][LDV]  query tile of the upstream gradient
-  float* Qi = dOi + 32 * LDV;          // [32][LDQ]
-  float* lse_i = Qi + 32 * LDQ;        // [32]
-  float* del_i = lse_i + 32;           // [32]
-  float* Kw = del_i + 32;              // [4][32][LDQ]   each wave's key block (B operand of the query-side product)
-  float* dsT = Kw + 4 * 32 * LDQ;      // [4][32][33]    private transposed dS tiles
-  float* RB = dsT + 4 * 32 * 33;       // [4][NDT][16][64] query-side partial tiles, summed over the four key blocks
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, l31 = lane & 31, lh = lane >> 5;
-  const int n = blockIdx.y, j0 = ((int)blockIdx.x + kb0) * 128 + wid * 32;   // this wave's keys (kb0: key-block offset of this launch)
-  const float* qb = q + (int64_t)n * T * D;
-  const float* v1b = v1 + (int64_t)n * T * C1;
-  const float* v2b = v2 ? v2 + (int64_t)n * T * C2 : nullptr;
-  const float* g1b = g1 + (int64_t)n * T * C1;
-  const float* g2b = g2 ? g2 + (int64_t)n * T * C2 : nullptr;
-  const float* lseb = lse + (int64_t)n * T;
-  const float* delb = delta + (int64_t)n * T;
-
-  float* kw = Kw + wid * 32 * LDQ;
-  for (int f = lane; f < 8 * D; f += 64) {
-    const int key = f / (D / 4), dd = (f % (D / 4)) * 4;
-    const float4 v = *reinterpret_cast<const float4*>(qb + (int64_t)(j0 + key) * D + dd);
-    float* d = kw + key * LDQ + dd;
-    d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-  }
-  float kfrag[D / 2], vfrag[CT / 2];   // K[key = l31][2s + lh], V[key = l31][2s + lh]
-#pragma unroll
-  for (int s = 0; s < D / 2; ++s) kfrag[s] = qb[(int64_t)(j0 + l31) * D + 2 * s + lh];
-#pragma unroll
-  for (int s = 0; s < CT / 2; ++s) {
-    const int c = 2 * s + lh;
-    vfrag[s] = (c < C1) ? v1b[(int64_t)(j0 + l31) * C1 + c] : v2b[(int64_t)(j0 + l31) * C2 + (c - C1)];
-  }
-
-  f32x16 acc_dv[NCT], acc_dk[NDT];
-#pragma unroll
-  for (int c = 0; c < NCT; ++c)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc_dv[c][r] = 0.f;
-#pragma unroll
-  for (int c = 0; c < NDT; ++c)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc_dk[c][r] = 0.f;
-
-  float4 rq[NQL], rg[NVL];
-  float rl = 0.f, rd = 0.f;
-  auto gload = [&](int i0) {
-#pragma unroll
-    for (int i = 0; i < NQL; ++i) {
-      const int f = tid + 256 * i;
-      const int row = f / (D / 4), dd = (f % (D / 4)) * 4;
-      rq[i] = (f < 8 * D) ? *reinterpret_cast<const float4*>(qb + (int64_t)(i0 + row) * D + dd) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int i = 0; i < NVL; ++i) {
-      const int f = tid + 256 * i;
-      const int row = f / (CT / 4), c = (f % (CT / 4)) * 4;
-      rg[i] = (c < C1) ? *reinterpret_cast<const float4*>(g1b + (int64_t)(i0 + row) * C1 + c)
-                       : *reinterpret_cast<const float4*>(g2b + (int64_t)(i0 + row) * C2 + (c - C1));
-    }
-    rl = lseb[i0 + (tid & 31)];
-    rd = delb[i0 + (tid & 31)];
-  };
-  auto lstore = [&]() {
-#pragma unroll
-    for (int i = 0; i < NQL; ++i) {
-      const int f = tid + 256 * i;
-      if (f < 8 * D) {
-        float* d = Qi + (f / (D / 4)) * LDQ + (f % (D / 4)) * 4;
-        d[0] = rq[i].x; d[1] = rq[i].y; d[2] = rq[i].z; d[3] = rq[i].w;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NVL; ++i) {
-      const int f = tid + 256 * i;
-      float* d = dOi + (f / (CT / 4)) * LDV + (f % (CT / 4)) * 4;
-      d[0] = rg[i].x; d[1] = rg[i].y; d[2] = rg[i].z; d[3] = rg[i].w;
-    }
-    if (tid < 32) {
-      lse_i[tid] = rl;
-      del_i[tid] = rd;
-    }
-  };
-
-  gload(0);
-  lstore();
-  __syncthreads();
-  float* t = dsT + wid * (32 * 33);
-  for (int i0 = 0; i0 < T; i0 += 32) {
-    gload(i0 + 32 < T ? i0 + 32 : i0);
-    // ---- S[q][key], dP[q][key]: lane = key, registers = queries
-    f32x16 sp, dp;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      sp[r] = 0.f;
-      dp[r] = 0.f;
-    }
-#pragma unroll
-    for (int s = 0; s < D / 2; ++s) sp = __builtin_amdgcn_mfma_f32_32x32x2f32(Qi[l31 * LDQ + 2 * s + lh], kfrag[s], sp, 0, 0, 0);
-#pragma unroll
-    for (int s = 0; s < CT / 2; ++s) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(dOi[l31 * LDV + 2 * s + lh], vfrag[s], dp, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int qi = (r & 3) + 8 * (r >> 2) + 4 * lh;
-      const float p = __expf(sp[r] - lse_i[qi]);
-      sp[r] = p;
-      dp[r] = p * (dp[r] - del_i[qi]);
-    }
-    // ---- dV^T[c][key] += gO^T[c][q] P[q][key];  dK^T[d][key] += Q^T[d][q] dS[q][key]
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const int qi = (s & 3) + 8 * (s >> 2) + 4 * lh;
-#pragma unroll
-      for (int c = 0; c < NCT; ++c) acc_dv[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(dOi[qi * LDV + c * 32 + l31], sp[s], acc_dv[c], 0, 0, 0);
-#pragma unroll
-      for (int c = 0; c < NDT; ++c) acc_dk[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(Qi[qi * LDQ + c * 32 + l31], dp[s], acc_dk[c], 0, 0, 0);
-    }
-    // ---- query side: dQ[q][d] = dS[q][key] K[key][d] for this wave's keys, through the private transposed tile
-#pragma unroll
-    for (int r = 0; r < 16; ++r) t[((r & 3) + 8 * (r >> 2) + 4 * lh) * 33 + l31] = dp[r];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int c = 0; c < NDT; ++c) {
-      f32x16 dq;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dq[r] = 0.f;
-#pragma unroll
-      for (int s = 0; s < 16; ++s) dq = __builtin_amdgcn_mfma_f32_32x32x2f32(t[l31 * 33 + 2 * s + lh], kw[(2 * s + lh) * LDQ + c * 32 + l31], dq, 0, 0, 0);
-      float* rb = RB + ((wid * NDT + c) * 16) * 64 + lane;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) rb[r * 64] = dq[r];
-    }
-    __syncthreads();   // every wave is done with the query tile; RB holds the four partial dQ tiles
-    // sum the partials: NDT*16 register-rows in all, wave w takes rows [w*NDT*4, (w+1)*NDT*4) and issues the atomics
-#pragma unroll
-    for (int rr = 0; rr < NDT * 4; ++rr) {
-      const int row = wid * NDT * 4 + rr;       // = c*16 + r
-      const int c = row >> 4, r = row & 15;
-      float s = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) s += RB[((w * NDT + c) * 16 + r) * 64 + lane];
-      atomicAdd(gq + ((int64_t)n * T + i0 + (r & 3) + 8 * (r >> 2) + 4 * lh) * D + c * 32 + l31, s);
-    }
-    lstore();
-    __syncthreads();
-  }
-
-  // all query-side atomics of this workgroup have COMPLETED before its key-side ones start: where both touch one row (the last query
-  // tile of the last key block) their order is then fixed, which the reproducible mode relies on
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  // ---- epilogue: dV rows of this wave's keys (plain stores) and the key-side dQ (atomics)
-  const int64_t row = (int64_t)n * T + j0 + l31;
-#pragma unroll
-  for (int c = 0; c < NCT; ++c) {
-    const int ch = c * 32;
-    float* ob = (ch < C1) ? gv1 + row * C1 + ch : gv2 + row * C2 + (ch - C1);
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-      *reinterpret_cast<float4*>(ob + 8 * g + 4 * lh) = make_float4(acc_dv[c][4 * g], acc_dv[c][4 * g + 1], acc_dv[c][4 * g + 2], acc_dv[c][4 * g + 3]);
-  }
-#pragma unroll
-  for (int c = 0; c < NDT; ++c) {
-    float* gqb = gq + row * D + c * 32;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) atomicAdd(gqb + (r & 3) + 8 * (r >> 2) + 4 * lh, acc_dk[c][r]);
-  }
-}
-
-// =====================================================================================================
-// Backward, second structure, on the bf16 matrix pipe (x6.h).  Same roles as attn_bwd2_kernel (a wave owns 32 keys with all value
-// channels; the query tile staged in LDS feeds the four key blocks of the workgroup), every product as six bf16 MFMAs of K = 16:
+// Every product is six bf16 MFMAs of K = 16:
 //  * the query tile (Q_i, gO_i) is cut into its three bf16 pieces on the way from the staging registers into LDS (IMG = false, reached through
 //    fmi_attention_bwd_f32) or, IMG = true (fmi_attention_bwd_pieces_f32, what the library's callers dispatch to), once per pass by
 //    attn_cut_qtile_kernel into the query-tile image (AttQImg below), whose blocks go global -> LDS by LDS-DMA: the copy of tile i + 1 is
@@ -947,8 +623,8 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_kernel(const float* __restri
 //  * P and dS (lane = key, registers = queries) are split in registers: they are the B operands of dV^T and dK^T as they stand;
 //    for the query-side product dQ = dS K the three dS pieces go through a private [key][q] LDS image and come back transposed
 //    (ds_read_b64_tr_b16) as A fragments;
-//  * the query-side tiles of the four key blocks are summed in LDS (ds_add_f32) before the global atomics, as before.
-// Per query tile and wave: 264 bf16 MFMAs (8 448 matrix-pipe cycles; the fp32 kernel: 352 MFMAs, 22 528 cycles).
+//  * the query-side tiles of the four key blocks are summed in LDS (ds_add_f32) before the global atomics.
+// Per query tile and wave: 264 bf16 MFMAs (8 448 matrix-pipe cycles; the fp32-MFMA kernel it replaced: 352 MFMAs, 22 528 cycles).
 // =====================================================================================================
 // With all 8 channel tiles in one launch the 128 dV + 32 dK accumulator registers leave no room for the V pieces (192 registers): V stays
 // fp32 and is split per tile (700 VALU instructions of ~2 400).  (A two-launch form that kept the V pieces in registers -- 288 instead of
@@ -1005,6 +681,12 @@ __global__ void __launch_bounds__(256) attn_cut_qtile_kernel(const float* __rest
   }
 }
 
+// dynamic LDS of attn_bwd2_x6_kernel: the query tile's gO and Q piece images with lse / delta (IMG: one block of the query-tile image),
+// the four waves' key-block piece images and their dS^T / partial-dQ slots
+template <int D, int NCT, bool IMG>
+constexpr int attn_bwd2_x6_lds = (IMG ? AttQImg<D, NCT * 32>::BLK : 3 * 32 * 2 * NCT * 32 + 3 * 32 * 192 + 64 * 4) + 4 * 3 * 32 * (2 * D + 16) +
+                                 4 * ((D / 32) * 4096 > 6144 ? (D / 32) * 4096 : 6144);
+
 template <int D, int NCT, bool IMG>
 __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __restrict__ q, const float* __restrict__ v1,
                                                               const float* __restrict__ v2, const float* __restrict__ g1,
@@ -1024,12 +706,14 @@ __global__ void __launch_bounds__(256, 1) attn_bwd2_x6_kernel(const float* __res
   float* lse_i = reinterpret_cast<float*>(Qs + 3 * QIMG);         // [32]
   float* del_i = lse_i + 32;                                      // [32]
   // IMG: Gs .. del_i are one block of the query-tile image (AttQImg), copied as it stands; its last KiB holds lse / delta and padding
-  unsigned char* Ks = reinterpret_cast<unsigned char*>(del_i + 32) + (IMG ? AttQImg<D, CT>::BLK - AttQImg<D, CT>::LSE - 256 : 0);  // [4][3][32][KP]  each wave's key block as bf16 pieces: B operand of S (row reads) and of dQ = dS K (transposed reads)
-  unsigned char* Ts = Ks + 4 * 3 * KIMG;                          // [4][WSLOT]  per wave: the transposed dS pieces [3][32][64 B], then (same bytes) its query-side partial tiles
+  constexpr int KS = IMG ? AttQImg<D, CT>::BLK : 3 * GIMG + 3 * QIMG + 256, TS = KS + 4 * 3 * KIMG;  // offsets (bytes)
+  unsigned char* Ks = smem_b + KS;                                // [4][3][32][KP]  each wave's key block as bf16 pieces: B operand of S (row reads) and of dQ = dS K (transposed reads)
+  unsigned char* Ts = smem_b + TS;                                // [4][WSLOT]  per wave: the transposed dS pieces [3][32][64 B], then (same bytes) its query-side partial tiles
   // a wave's partial dQ tiles [NDT][16][64] overwrite its own dS^T image once its transposed reads are done; the other waves read them between
   // the two barriers that follow, and the image is rewritten only after the second one.  (LDS float atomics instead of partial tiles: ~250
   // cycles per wave instruction, measured.)
   constexpr int WSLOT = (NDT * 16 * 64 * 4 > 3 * TIMG) ? NDT * 16 * 64 * 4 : 3 * TIMG;
+  static_assert(TS + 4 * WSLOT == attn_bwd2_x6_lds<D, NCT, IMG>, "the host passes the bytes this carve ends at");
   typedef __attribute__((address_space(3))) unsigned char* lds_ptr;
   const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_ptr)smem_b;
 
@@ -1520,6 +1204,18 @@ __global__ void __launch_bounds__(256) rowdot2_kernel(const float* __restrict__ 
   if (lane == 0) out[row] = s;
 }
 
+// Launch of a backward kernel over its key blocks (grid.x; `kb`, the key-block offset, is the kernels' last argument).  Reproducible mode:
+// the query-side tiles of dQ receive one atomic contribution per KEY BLOCK; launching the key blocks one after the other (stream order)
+// fixes the order of those additions -- same kernels, grid.x = 1.
+template <auto Kernel, class... A>
+static int att_launch_key_blocks(dim3 grid, int lds_bytes, hipStream_t st, A... args) {
+  const bool det = fmi_det();
+  int rc = FMI_OK;
+  for (int kb = 0; kb < (det ? (int)grid.x : 1) && rc == FMI_OK; ++kb)
+    rc = fmi_launch_lds<Kernel>(det ? dim3(1, grid.y) : grid, dim3(256), lds_bytes, st, args..., kb);
+  return rc;
+}
+
 // The backward's shape dispatch, in one place: 2 = the key-block-per-wave structure (attn_bwd2*), where its T / 128 workgroups per image
 // fill the chip; 1 = the first structure (attn_bwd_kernel), which has 4x the workgroups.
 extern "C" int fmi_attention_bwd_structure(int N, int T) {
@@ -1536,80 +1232,25 @@ extern "C" int fmi_attention_bwd_f32(const float* q, const float* v1, const floa
   // of the scores, see attn_bwd_kernel), and no forward produces one for the other T
   if (T % 128 != 0 || C1 % 32 != 0 || C2 % 32 != 0 || N > 65535) return FMI_ERR_UNSUPPORTED;
   const int nct = (C1 + C2) / 32;
-  if ((D != 32 && D != 64) || (nct != 4 && nct != 8)) return FMI_ERR_UNSUPPORTED;  // refused before the delta pass is launched
+  if (!att_dispatch<false>(D, nct, [](auto, auto) {})) return FMI_ERR_UNSUPPORTED;  // refused before the delta pass is launched
   if ((((uintptr_t)q | (uintptr_t)v1 | (uintptr_t)v2 | (uintptr_t)go1 | (uintptr_t)go2 | (uintptr_t)gv1 | (uintptr_t)gv2) & 15) != 0)
     return FMI_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   const int64_t rows = (int64_t)N * T;
   hipLaunchKernelGGL(rowdot2_kernel, dim3((unsigned)ceil_div64(rows, 4)), dim3(256), 0, st, go1, o1, C1, C2 ? go2 : nullptr, o2, C2,
                      delta_scratch, rows);
-  const dim3 block(256);
-  // reproducible mode: the query-side tiles of dQ receive one atomic contribution per KEY BLOCK; launching the key blocks one after the
-  // other (stream order) fixes the order of those additions -- same kernels, grid.x = 1, key-block offset as an argument
-  const bool det = fmi_det();
-  if (fmi_attention_bwd_structure(N, T) == 2) {  // one key block per wave, fragments in registers, 4x fewer atomics
-    const dim3 grid2(T / 128, N);
-    auto lds2 = [](int d, int ct) {
-      return sizeof(float) * (size_t)(32 * (ct + 1) + 32 * (d + 1) + 64 + 4 * 32 * (d + 1) + 4 * 32 * 33 + 4 * (d / 32) * 16 * 64);
-    };
-    auto lds2x = [](int d, int ct) {
-      return (size_t)(3 * 32 * 2 * ct + 3 * 32 * 192 + 64 * 4 + 4 * 3 * 32 * (2 * d + 16) + 4 * ((d / 32) * 4096 > 6144 ? (d / 32) * 4096 : 6144));
-    };
-#define ATTB2_LAUNCH(DD, NN)                                                                                             \
-  do {                                                                                                                   \
-    if (FMI_X6) {                                                                                                        \
-      static fmi_attr_flags attr_setx{}; int attr_setx_dev;\
-      if (fmi_attr_needed(attr_setx, attr_setx_dev)) {                                                                   \
-        if (hipFuncSetAttribute((const void*)attn_bwd2_x6_kernel<DD, NN, false>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)lds2x(DD, NN * 32)) != hipSuccess)                                                  \
-          return FMI_ERR_LAUNCH;                                                                                         \
-        fmi_attr_mark(attr_setx, attr_setx_dev);                                                                         \
-      }                                                                                                                  \
-      for (int kb = 0; kb < (det ? (int)grid2.x : 1); ++kb)                                                              \
-        hipLaunchKernelGGL((attn_bwd2_x6_kernel<DD, NN, false>), det ? dim3(1, grid2.y) : grid2, block, lds2x(DD, NN * 32), st, q, v1, v2, go1, go2, \
-                           lse, (const float*)delta_scratch, (const unsigned char*)nullptr, gv1, gv2, gq_zeroed, T, C1, C2, kb); \
-      return fmi_launch_status();                                                                                        \
-    }                                                                                                                    \
-    static fmi_attr_flags attr_set2{}; int attr_set2_dev;\
-    if (fmi_attr_needed(attr_set2, attr_set2_dev)) {                                                                                                    \
-      if (hipFuncSetAttribute((const void*)attn_bwd2_kernel<DD, NN>, hipFuncAttributeMaxDynamicSharedMemorySize,         \
-                              (int)lds2(DD, NN * 32)) != hipSuccess)                                                     \
-        return FMI_ERR_LAUNCH;                                                                                           \
-      fmi_attr_mark(attr_set2, attr_set2_dev);                                                                                                  \
-    }                                                                                                                    \
-    for (int kb = 0; kb < (det ? (int)grid2.x : 1); ++kb)                                                                \
-      hipLaunchKernelGGL((attn_bwd2_kernel<DD, NN>), det ? dim3(1, grid2.y) : grid2, block, lds2(DD, NN * 32), st, q, v1, v2, go1, go2, lse, \
-                         (const float*)delta_scratch, gv1, gv2, gq_zeroed, T, C1, C2, kb);                                \
-    return fmi_launch_status();                                                                                          \
-  } while (0)
-    if (D == 64 && nct == 8) ATTB2_LAUNCH(64, 8);
-    if (D == 32 && nct == 8) ATTB2_LAUNCH(32, 8);
-    if (D == 32 && nct == 4) ATTB2_LAUNCH(32, 4);
-    if (D == 64 && nct == 4) ATTB2_LAUNCH(64, 4);
-#undef ATTB2_LAUNCH
-  }
-  const dim3 grid(T / 32, N);
-  auto lds_bytes = [](int d, int ct) { return sizeof(float) * (size_t)(2 * 32 * (ct + 1) + 2 * 32 * (d + 1) + 64 + 4 * 2 * 1024 + 2 * 32 * 33); };
-#define ATTB_LAUNCH(DD, NN)                                                                                              \
-  do {                                                                                                                   \
-    static fmi_attr_flags attr_set{}; int attr_set_dev;\
-    if (fmi_attr_needed(attr_set, attr_set_dev)) {                                                                                                     \
-      if (hipFuncSetAttribute((const void*)attn_bwd_kernel<DD, NN>, hipFuncAttributeMaxDynamicSharedMemorySize,          \
-                              (int)lds_bytes(DD, NN * 32)) != hipSuccess)                                                \
-        return FMI_ERR_LAUNCH;                                                                                           \
-      fmi_attr_mark(attr_set, attr_set_dev);                                                                                                   \
-    }                                                                                                                    \
-    for (int kb = 0; kb < (det ? (int)grid.x : 1); ++kb)                                                                 \
-      hipLaunchKernelGGL((attn_bwd_kernel<DD, NN>), det ? dim3(1, grid.y) : grid, block, lds_bytes(DD, NN * 32), st, q, v1, v2, go1, go2, lse, \
-                         (const float*)delta_scratch, gv1, gv2, gq_zeroed, T, C1, C2, kb);                                \
-  } while (0)
-  if (D == 64 && nct == 8) ATTB_LAUNCH(64, 8);
-  else if (D == 32 && nct == 8) ATTB_LAUNCH(32, 8);
-  else if (D == 32 && nct == 4) ATTB_LAUNCH(32, 4);
-  else if (D == 64 && nct == 4) ATTB_LAUNCH(64, 4);
-  else return FMI_ERR_UNSUPPORTED;
-#undef ATTB_LAUNCH
-  return fmi_launch_status();
+  const bool second = fmi_attention_bwd_structure(N, T) == 2;  // one key block per wave, fragments in registers, 4x fewer atomics
+  int rc = FMI_OK;
+  att_dispatch<false>(D, nct, [&](auto d, auto n) {
+    constexpr int DD = decltype(d)::value, NN = decltype(n)::value;
+    if (second)
+      rc = att_launch_key_blocks<attn_bwd2_x6_kernel<DD, NN, false>>(dim3(T / 128, N), attn_bwd2_x6_lds<DD, NN, false>, st, q, v1, v2, go1, go2, lse,
+                                                                     delta_scratch, (const unsigned char*)nullptr, gv1, gv2, gq_zeroed, T, C1, C2);
+    else
+      rc = att_launch_key_blocks<attn_bwd_kernel<DD, NN>>(dim3(T / 32, N), attn_bwd_lds<DD, NN>, st, q, v1, v2, go1, go2, lse, delta_scratch, gv1,
+                                                          gv2, gq_zeroed, T, C1, C2);
+  });
+  return rc != FMI_OK ? rc : fmi_launch_status();
 }
 
 
@@ -1619,8 +1260,7 @@ extern "C" int fmi_attention_bwd_f32(const float* q, const float* v1, const floa
 // takes above); the entry point itself accepts every shape the kernel can run, so a test may call it below the fill-the-GPU threshold.
 // =====================================================================================================
 static bool att_pieces_shape(int T, int D, int C1, int C2) {
-  const int nct = (C1 + C2) / 32;
-  return FMI_X6 && T > 0 && T % 128 == 0 && C1 > 0 && C2 >= 0 && C1 % 32 == 0 && C2 % 32 == 0 && (D == 32 || D == 64) && (nct == 4 || nct == 8);
+  return T > 0 && T % 128 == 0 && C1 > 0 && C2 >= 0 && C1 % 32 == 0 && C2 % 32 == 0 && att_dispatch<false>(D, (C1 + C2) / 32, [](auto, auto) {});
 }
 extern "C" int fmi_attention_bwd_uses_pieces(int N, int T, int D, int C1, int C2) {
   return N > 0 && N <= 65535 && att_pieces_shape(T, D, C1, C2) && fmi_attention_bwd_structure(N, T) == 2;
@@ -1630,9 +1270,9 @@ extern "C" int fmi_attention_bwd_image_bytes(int N, int T, int D, int C1, int C2
   if (!bytes || N <= 0) return FMI_ERR_BAD_ARG;
   *bytes = 0;
   if (!att_pieces_shape(T, D, C1, C2)) return FMI_OK;
-  const int ct = C1 + C2;
-  const int64_t blk = D == 64 ? (ct == 256 ? AttQImg<64, 256>::BLK : AttQImg<64, 128>::BLK) : (ct == 256 ? AttQImg<32, 256>::BLK : AttQImg<32, 128>::BLK);
-  *bytes = (int64_t)N * (T / 32) * blk;
+  att_dispatch<false>(D, (C1 + C2) / 32, [&](auto d, auto n) {
+    *bytes = (int64_t)N * (T / 32) * AttQImg<decltype(d)::value, decltype(n)::value * 32>::BLK;
+  });
   return FMI_OK;
 }
 
@@ -1653,34 +1293,16 @@ extern "C" int fmi_attention_bwd_pieces_f32(const float* q, const float* v1, con
   const int64_t rows = (int64_t)N * T;
   hipLaunchKernelGGL(rowdot2_kernel, dim3((unsigned)ceil_div64(rows, 4)), dim3(256), 0, st, go1, o1, C1, C2 ? go2 : nullptr, o2, C2,
                      delta_scratch, rows);
-  const bool det = fmi_det();  // reproducible mode: one key block per launch, as in fmi_attention_bwd_f32
-  const dim3 grid(T / 128, N), block(256);
   unsigned char* img = (unsigned char*)image;
-#define ATTP_LAUNCH(DD, NN)                                                                                                      \
-  do {                                                                                                                           \
-    typedef AttQImg<DD, NN * 32> I;                                                                                              \
-    constexpr int lds_bytes = I::BLK + 4 * 3 * 32 * (2 * DD + 16) + 4 * ((DD / 32) * 4096 > 6144 ? (DD / 32) * 4096 : 6144);      \
-    static fmi_attr_flags attr_set{};                                                                                            \
-    int attr_set_dev;                                                                                                            \
-    if (fmi_attr_needed(attr_set, attr_set_dev)) {                                                                               \
-      if (hipFuncSetAttribute((const void*)attn_bwd2_x6_kernel<DD, NN, true>, hipFuncAttributeMaxDynamicSharedMemorySize,        \
-                              lds_bytes) != hipSuccess)                                                                          \
-        return FMI_ERR_LAUNCH;                                                                                                   \
-      fmi_attr_mark(attr_set, attr_set_dev);                                                                                     \
-    }                                                                                                                            \
-    hipLaunchKernelGGL((attn_cut_qtile_kernel<DD, NN * 32>), dim3((unsigned)(rows / 32)), dim3(256), 0, st, q, go1, go2, lse,    \
-                       (const float*)delta_scratch, img, C1, C2);                                                                \
-    for (int kb = 0; kb < (det ? (int)grid.x : 1); ++kb)                                                                         \
-      hipLaunchKernelGGL((attn_bwd2_x6_kernel<DD, NN, true>), det ? dim3(1, grid.y) : grid, block, lds_bytes, st, q, v1, v2,     \
-                         go1, go2, lse, (const float*)delta_scratch, (const unsigned char*)img, gv1, gv2, gq_zeroed, T, C1, C2, kb); \
-  } while (0)
-  const int nct = (C1 + C2) / 32;
-  if (D == 64 && nct == 8) ATTP_LAUNCH(64, 8);
-  else if (D == 32 && nct == 8) ATTP_LAUNCH(32, 8);
-  else if (D == 32 && nct == 4) ATTP_LAUNCH(32, 4);
-  else ATTP_LAUNCH(64, 4);
-#undef ATTP_LAUNCH
-  return fmi_launch_status();
+  int rc = FMI_OK;
+  att_dispatch<false>(D, (C1 + C2) / 32, [&](auto d, auto n) {
+    constexpr int DD = decltype(d)::value, NN = decltype(n)::value;
+    hipLaunchKernelGGL((attn_cut_qtile_kernel<DD, NN * 32>), dim3((unsigned)(rows / 32)), dim3(256), 0, st, q, go1, go2, lse,
+                       (const float*)delta_scratch, img, C1, C2);
+    rc = att_launch_key_blocks<attn_bwd2_x6_kernel<DD, NN, true>>(dim3(T / 128, N), attn_bwd2_x6_lds<DD, NN, true>, st, q, v1, v2, go1, go2, lse,
+                                                                  delta_scratch, (const unsigned char*)img, gv1, gv2, gq_zeroed, T, C1, C2);
+  });
+  return rc != FMI_OK ? rc : fmi_launch_status();
 }
 
 // =====================================================================================================
@@ -1695,9 +1317,9 @@ extern "C" int fmi_attention_fwd_image_bytes(int N, int T, int D, int C1, int C2
   if (!bytes || N <= 0) return FMI_ERR_BAD_ARG;
   *bytes = 0;
   if (!att_pieces_shape(T, D, C1, C2) || T % 256 != 0) return FMI_OK;
-  const int ct = C1 + C2;
-  const int64_t blk = D == 64 ? (ct == 256 ? AttKImg<64, 256>::BLK : AttKImg<64, 128>::BLK) : (ct == 256 ? AttKImg<32, 256>::BLK : AttKImg<32, 128>::BLK);
-  *bytes = (int64_t)N * (T / 32) * blk;
+  att_dispatch<false>(D, (C1 + C2) / 32, [&](auto d, auto n) {
+    *bytes = (int64_t)N * (T / 32) * AttKImg<decltype(d)::value, decltype(n)::value * 32>::BLK;
+  });
   return FMI_OK;
 }
 extern "C" int fmi_attention_fwd_pieces_f32(const float* q, const float* v1, const float* v2, void* image, int64_t image_bytes, float* o1,
@@ -1710,27 +1332,12 @@ extern "C" int fmi_attention_fwd_pieces_f32(const float* q, const float* v1, con
   if (image_bytes < need) return FMI_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   unsigned char* img = (unsigned char*)image;
-#define ATTFP_LAUNCH(DD, NN)                                                                                                     \
-  do {                                                                                                                           \
-    constexpr int lds_bytes = 2 * AttKImg<DD, NN * 32>::BLK;                                                                     \
-    static fmi_attr_flags attr_set{};                                                                                            \
-    int attr_set_dev;                                                                                                            \
-    if (fmi_attr_needed(attr_set, attr_set_dev)) {                                                                               \
-      if (hipFuncSetAttribute((const void*)attn_fwd_x6_kernel<DD, NN, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize,      \
-                              lds_bytes) != hipSuccess)                                                                          \
-        return FMI_ERR_LAUNCH;                                                                                                   \
-      fmi_attr_mark(attr_set, attr_set_dev);                                                                                     \
-    }                                                                                                                            \
-    hipLaunchKernelGGL((attn_cut_ktile_kernel<DD, NN * 32>), dim3((unsigned)((int64_t)N * T / 32)), dim3(256), 0, st, q, v1, v2, \
-                       img, C1, C2);                                                                                             \
-    hipLaunchKernelGGL((attn_fwd_x6_kernel<DD, NN, 8, true>), dim3(T / 256, N), dim3(512), lds_bytes, st, q, v1, v2,             \
-                       (const unsigned char*)img, o1, o2, lse, T, C1, C2);                                                       \
-  } while (0)
-  const int nct = (C1 + C2) / 32;
-  if (D == 64 && nct == 8) ATTFP_LAUNCH(64, 8);
-  else if (D == 32 && nct == 8) ATTFP_LAUNCH(32, 8);
-  else if (D == 32 && nct == 4) ATTFP_LAUNCH(32, 4);
-  else ATTFP_LAUNCH(64, 4);
-#undef ATTFP_LAUNCH
-  return fmi_launch_status();
+  int rc = FMI_OK;
+  att_dispatch<false>(D, (C1 + C2) / 32, [&](auto d, auto n) {
+    constexpr int DD = decltype(d)::value, NN = decltype(n)::value;
+    hipLaunchKernelGGL((attn_cut_ktile_kernel<DD, NN * 32>), dim3((unsigned)((int64_t)N * T / 32)), dim3(256), 0, st, q, v1, v2, img, C1, C2);
+    rc = fmi_launch_lds<attn_fwd_x6_kernel<DD, NN, 8, true>>(dim3(T / 256, N), dim3(512), attn_fwd_x6_lds<DD, NN, true>, st, q, v1, v2,
+                                                             (const unsigned char*)img, o1, o2, lse, T, C1, C2);
+  });
+  return rc != FMI_OK ? rc : fmi_launch_status();
 }

@@ -16,23 +16,13 @@
 #include "common.h"
 #include "x6.h"
 
-// > 64 KB of dynamic LDS must be opted into per kernel AND per device (hipFuncSetAttribute acts on the current device's code object):
-// one atomic flag per (kernel instantiation, device ordinal), as in attention.hip
-struct fmi_attr_flags {
-  unsigned char done[64];
-};
-static inline bool fmi_attr_needed(fmi_attr_flags& f, int& dev) {
-  dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return true;
-  return !__atomic_load_n(&f.done[dev], __ATOMIC_ACQUIRE);
-}
-static inline void fmi_attr_mark(fmi_attr_flags& f, int dev) {
-  if (dev >= 0 && dev < 64) __atomic_store_n(&f.done[dev], (unsigned char)1, __ATOMIC_RELEASE);
-}
-
 #define ATT_THR 20.0f
 
 __device__ __forceinline__ float bf16_bits_to_f32(uint32_t h) { return __uint_as_float(h << 16); }
+
+// dynamic LDS of attn_fwd_bf16_kernel: two stages of 64 K rows and 64 V rows at their padded pitches
+template <int D, int NCT>
+constexpr int attn_fwd_bf16_lds = 2 * 64 * ((2 * D + 16) + (2 * NCT * 32 + 64));
 
 template <int D, int NCT, int NW>
 __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_bf16_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ v,
@@ -46,7 +36,8 @@ __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_bf16_kernel(const uint16_
   constexpr int NKL = (KCH + NTH - 1) / NTH, NVL = VCH / NTH;
   static_assert(VCH % NTH == 0, "whole 16-byte passes over the V tile");
   static_assert(D % 16 == 0, "whole bf16 k-steps");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_b16[];
+  static_assert(1 * STAGE + STAGE == attn_fwd_bf16_lds<D, NCT>, "the host passes the bytes this carve ends at");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_b16[];  // [2][STAGE]
   typedef __attribute__((address_space(3))) unsigned char* lds_ptr;
   const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_ptr)smem_b16;
 
@@ -215,26 +206,9 @@ extern "C" int fmi_attention_fwd_bf16(const uint16_t* q, const uint16_t* v, uint
   const int nw = waves ? waves : fmi_attention_fwd_bf16_waves(N, T);
   const dim3 grid(T / (nw * 32), N), block(nw * 64);
   hipStream_t st = (hipStream_t)stream;
-#define ATTB16_LAUNCH(DD, NN, WW)                                                                                                  \
-  do {                                                                                                                             \
-    constexpr int lds_bytes = 2 * 64 * ((2 * DD + 16) + (2 * NN * 32 + 64));                                                       \
-    static fmi_attr_flags attr_set{};                                                                                              \
-    int attr_set_dev;                                                                                                              \
-    if (fmi_attr_needed(attr_set, attr_set_dev)) {                                                                                 \
-      if (hipFuncSetAttribute((const void*)attn_fwd_bf16_kernel<DD, NN, WW>, hipFuncAttributeMaxDynamicSharedMemorySize,           \
-                              lds_bytes) != hipSuccess)                                                                            \
-        return FMI_ERR_LAUNCH;                                                                                                     \
-      fmi_attr_mark(attr_set, attr_set_dev);                                                                                       \
-    }                                                                                                                              \
-    hipLaunchKernelGGL((attn_fwd_bf16_kernel<DD, NN, WW>), grid, block, lds_bytes, st, q, v, o, lse, gamma, residual, T);          \
-  } while (0)
-  if (D == 64) {
-    if (nw == 8) ATTB16_LAUNCH(64, 8, 8);
-    else ATTB16_LAUNCH(64, 8, 4);
-  } else {
-    if (nw == 8) ATTB16_LAUNCH(32, 4, 8);
-    else ATTB16_LAUNCH(32, 4, 4);
-  }
+#define ATTB16_LAUNCH(DD, NN, WW) \
+  fmi_launch_lds<attn_fwd_bf16_kernel<DD, NN, WW>>(grid, block, attn_fwd_bf16_lds<DD, NN>, st, q, v, o, lse, gamma, residual, T)
+  const int rc = D == 64 ? (nw == 8 ? ATTB16_LAUNCH(64, 8, 8) : ATTB16_LAUNCH(64, 8, 4)) : (nw == 8 ? ATTB16_LAUNCH(32, 4, 8) : ATTB16_LAUNCH(32, 4, 4));
 #undef ATTB16_LAUNCH
-  return fmi_launch_status();
+  return rc != FMI_OK ? rc : fmi_launch_status();
 }

@@ -32,6 +32,33 @@ static inline bool fmi_det() { return false; }          // the launch-decomposit
 #include "host_threads.h"
 #else
 #include <hip/hip_runtime.h>
+
+// Launch of a kernel that carves more than 64 KB of dynamic LDS.  That much must be opted into per kernel AND per device
+// (hipFuncSetAttribute acts on the current device's code object): one atomic flag per (kernel instantiation, device ordinal), safe from
+// the forward and the autograd thread alike.  FMI_ERR_LAUNCH if the opt-in fails; the launch itself is checked by fmi_launch_status().
+struct fmi_attr_flags {
+  unsigned char done[64];
+};
+static inline bool fmi_attr_needed(fmi_attr_flags& f, int& dev) {
+  dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return true;
+  return !__atomic_load_n(&f.done[dev], __ATOMIC_ACQUIRE);
+}
+static inline void fmi_attr_mark(fmi_attr_flags& f, int dev) {
+  if (dev >= 0 && dev < 64) __atomic_store_n(&f.done[dev], (unsigned char)1, __ATOMIC_RELEASE);
+}
+template <auto Kernel>
+static fmi_attr_flags fmi_attr_flags_of{};
+template <auto Kernel, class... A>
+static int fmi_launch_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t st, A... args) {
+  int dev;
+  if (fmi_attr_needed(fmi_attr_flags_of<Kernel>, dev)) {
+    if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) return FMI_ERR_LAUNCH;
+    fmi_attr_mark(fmi_attr_flags_of<Kernel>, dev);
+  }
+  hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, st, args...);
+  return FMI_OK;
+}
 #endif
 #include <stdlib.h>
 

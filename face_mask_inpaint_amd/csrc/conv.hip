@@ -153,7 +153,7 @@ static int conv_phase(const fmi_conv_desc* d, const ConvGeom& g, const float* x,
 // d->w3, the bf16 piece image of the weights, where the kernels can read it: shared weights, 16-channel groups of the reduction
 static const void* weight_pieces(const fmi_conv_desc* d, int batch_w, int red_c) {
 #ifndef FMI_HOST_EMU
-  if (FMI_X6 && batch_w == 1 && red_c % 16 == 0 && aligned16(d->w3)) return d->w3;
+  if (batch_w == 1 && red_c % 16 == 0 && aligned16(d->w3)) return d->w3;
 #endif
   return nullptr;
 }
@@ -281,7 +281,7 @@ extern "C" int fmi_conv_transpose2d_pair_f32(const fmi_conv_desc* d, const float
   if (rc) return rc;
   if (!x1 || !x2 || !w3b || !d->w3 || !y || K2 <= 0) return FMI_ERR_BAD_ARG;
 #ifndef FMI_HOST_EMU
-  const uint16_t* w3 = (FMI_X6 && d->K % 16 == 0 && aligned16(d->w3)) ? (const uint16_t*)d->w3 : nullptr;
+  const uint16_t* w3 = (d->K % 16 == 0 && aligned16(d->w3)) ? (const uint16_t*)d->w3 : nullptr;
   if (!convt3x3_eligible(d, x1, w3) || (K2 & 15) || !aligned16(x2) || !aligned16(w3b) || d->pad_mode != 0 || d->x3) return FMI_ERR_UNSUPPORTED;
   CT3Args ca{};
   ca.x = x1; ca.w3 = w3; ca.x2 = x2; ca.w3b = (const uint16_t*)w3b; ca.Cred2 = K2; ca.cs2 = K2;
@@ -319,7 +319,7 @@ extern "C" int fmi_conv2d_wgrad_f32(const fmi_conv_desc* d, const float* x, cons
 #ifndef FMI_HOST_EMU
   // both operands as bf16 piece images (d->x3 = pieces of x, d->y3 = pieces of dy, INPUTS here): no split arithmetic, transposed LDS reads.
   // The bias gradient does not ride along on this path (the caller runs fmi_bias_grad_f32).
-  if (FMI_X6 && batch_w == 1 && !dbias && wgrad_p3_ok(d, d->x3, d->y3))
+  if (batch_w == 1 && !dbias && wgrad_p3_ok(d, d->x3, d->y3))
     return launch_wgrad_p3(d, (const uint16_t*)d->x3, (const uint16_t*)d->y3, dwf, (hipStream_t)stream);
 #endif
   const int n_eff = batch_w > 1 ? 1 : d->N;

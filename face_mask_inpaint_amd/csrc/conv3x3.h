@@ -33,7 +33,6 @@ __global__ void __launch_bounds__(256) conv3x3_dma_kernel(C3Args a, ConvEp ep, i
   constexpr int NIB = W3 ? 9 * BN / 32 : 3 * BN / 16;  // wave instructions of the three B tiles ([3][16 k][BN] floats, or [3][3][2][BN] chunks)
   constexpr int NLA = (NIA + 3) / 4, NLB = (NIB + 3) / 4;
   constexpr int STAGE = RA * BK + (W3 ? 3 * 3 * BN * 8 : 3 * BK * BN);  // floats
-  static_assert(!W3 || FMI_X6, "piece images feed the bf16 products");
   __shared__ __attribute__((aligned(1024))) float lds[2 * STAGE];
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -161,7 +160,6 @@ __global__ void __launch_bounds__(256) conv3x3_dma_kernel(C3Args a, ConvEp ep, i
 #pragma unroll
           for (int s = 0; s < 8; ++s) fb[j][s] = sb[(kx * 16 + 8 * lh + s) * BN + wn + j * 32 + l31];
       }
-#if FMI_X6
       bf16x8_t pa[T::TM][3], pb[T::TN][3];
 #pragma unroll
       for (int i = 0; i < T::TM; ++i) split3_bf16(fa[i], pa[i]);
@@ -179,14 +177,6 @@ __global__ void __launch_bounds__(256) conv3x3_dma_kernel(C3Args a, ConvEp ep, i
       for (int i = 0; i < T::TM; ++i)
 #pragma unroll
         for (int j = 0; j < T::TN; ++j) acc[i][j] = mfma_x6(pa[i], pb[j], acc[i][j]);
-#else
-#pragma unroll
-      for (int s = 0; s < 8; ++s)
-#pragma unroll
-        for (int i = 0; i < T::TM; ++i)
-#pragma unroll
-          for (int j = 0; j < T::TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][s], fb[j][s], acc[i][j], 0, 0, 0);
-#endif
     }
   };
 
@@ -260,7 +250,6 @@ static int launch_conv3x3(const C3Args& a, const ConvEp& ep, int M, int ksplit, 
   auto wgs = [&](int bm, int bn) { return ceil_div64(M, bm) * ceil_div64(a.Nout, bn) * ksplit; };
   const int N = a.Nout;
   const bool fl = it_chunk > 13 && fmi_det();  // blocked accumulation of a long unsplit reduction (conv_p3.h)
-#if FMI_X6
   // piece images of the weights: 2 x 27 KB of LDS at 64 columns (two workgroups per CU; a 128-column piece tile would leave one).  Measured
   // at 8 x 128^2 256 -> 256 / 24 x 224^2 64 -> 64 / 8 x 32^2 128 -> 128: 163 / 154 / 81 TFLOP/s against 170 / 144 / 75 with both operands split in the
   // consuming waves (128 x 128 tiles): taken for narrow outputs and for launches too small to fill the chip with the large tile
@@ -268,7 +257,6 @@ static int launch_conv3x3(const C3Args& a, const ConvEp& ep, int M, int ksplit, 
     C3_LAUNCH_(Tile128x64w, true);
     return fmi_launch_status();
   }
-#endif
   if (N <= 32) {
     C3_LAUNCH(Tile128x32);
   } else if (N <= 64) {

@@ -1,10 +1,10 @@
 // fp32 matrix-core GEMM core for gfx950, shared by the dense batched GEMM, the implicit-GEMM
 // convolution family (forward / adjoint / weight-gradient) and the attention products.
 //
-// Machine mapping (MI355X_MICROARCH.md, cdna_hip_programming.md section 3 "FP32-input MFMA"):
-//  * v_mfma_f32_32x32x2_f32: one wave owns 32x32 output tiles, 16 accumulator registers each;
-//    A operand lane l = A[i = l&31][k = l>>5], B operand lane l = B[k = l>>5][j = l&31];
-//    D register r of lane l is D[(r&3) + 8*(r>>2) + 4*(l>>5)][l&31].  Exact f32 (fmaf chain).
+// Machine mapping:
+//  * every fp32 product is six v_mfma_f32_32x32x16_bf16 on exact three-way bf16 splits of the operands (x6.h): one wave owns
+//    32x32 output tiles, 16 accumulator registers each; A operand lane l = A[i = l&31][k = 8*(l>>5) .. + 7], B operand lane
+//    l = B[k = 8*(l>>5) .. + 7][j = l&31]; D register r of lane l is D[(r&3) + 8*(r>>2) + 4*(l>>5)][l&31].
 //  * 256-thread workgroups = 4 waves (one per SIMD), 2 workgroups per CU; operand tiles are staged
 //    k-major in LDS ([k][m] with a +4 float row pad) so every fragment read is a conflict-free
 //    ds_read_b32 of 32 consecutive floats per half-wave; global->register->LDS double buffering
@@ -746,48 +746,28 @@ __global__ void __launch_bounds__(256) gemm_mfma_f32_kernel(LA la, LB lb, EP ep,
     }
   };
   // one 16-deep tile from LDS buffer `buf`: all fragments first (counted lgkmcnt waits let the MFMAs start as they
-  // arrive), then 8 x TM x TN back-to-back MFMAs: the LDS latency is exposed once per tile, not once per k-pair
+  // arrive), then 6 x TM x TN back-to-back MFMAs: the LDS latency is exposed once per tile, not once per k-step
   auto compute = [&](int buf) {
     const float* a = As + buf * BK * LDA + wm + l31;
     const float* b = Bs + buf * BK * LDB + wn + l31;
-#if FMI_X6
     static_assert(BK == 16, "one bf16 k-step per tile");
-    {
-      float ga[T::TM][8], gb[T::TN][8];
+    float ga[T::TM][8], gb[T::TN][8];
 #pragma unroll
-      for (int s = 0; s < 8; ++s) {
+    for (int s = 0; s < 8; ++s) {
 #pragma unroll
-        for (int i = 0; i < T::TM; ++i) ga[i][s] = a[(8 * lh + s) * LDA + i * 32];
+      for (int i = 0; i < T::TM; ++i) ga[i][s] = a[(8 * lh + s) * LDA + i * 32];
 #pragma unroll
-        for (int j = 0; j < T::TN; ++j) gb[j][s] = b[(8 * lh + s) * LDB + j * 32];
-      }
-      bf16x8_t pa[T::TM][3], pb[T::TN][3];
-#pragma unroll
-      for (int i = 0; i < T::TM; ++i) split3_bf16(ga[i], pa[i]);
-#pragma unroll
-      for (int j = 0; j < T::TN; ++j) split3_bf16(gb[j], pb[j]);
-#pragma unroll
-      for (int i = 0; i < T::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < T::TN; ++j) acc[i][j] = mfma_x6(pa[i], pb[j], acc[i][j]);
-      return;
+      for (int j = 0; j < T::TN; ++j) gb[j][s] = b[(8 * lh + s) * LDB + j * 32];
     }
-#endif
-    float fa[BK / 2][T::TM], fb[BK / 2][T::TN];
+    bf16x8_t pa[T::TM][3], pb[T::TN][3];
 #pragma unroll
-    for (int kk = 0; kk < BK / 2; ++kk) {
+    for (int i = 0; i < T::TM; ++i) split3_bf16(ga[i], pa[i]);
 #pragma unroll
-      for (int i = 0; i < T::TM; ++i) fa[kk][i] = a[(2 * kk + lh) * LDA + i * 32];
+    for (int j = 0; j < T::TN; ++j) split3_bf16(gb[j], pb[j]);
 #pragma unroll
-      for (int j = 0; j < T::TN; ++j) fb[kk][j] = b[(2 * kk + lh) * LDB + j * 32];
-    }
+    for (int i = 0; i < T::TM; ++i)
 #pragma unroll
-    for (int kk = 0; kk < BK / 2; ++kk) {
-#pragma unroll
-      for (int i = 0; i < T::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < T::TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[kk][i], fb[kk][j], acc[i][j], 0, 0, 0);
-    }
+      for (int j = 0; j < T::TN; ++j) acc[i][j] = mfma_x6(pa[i], pb[j], acc[i][j]);
   };
 
   if (k_begin < k_end) {
@@ -982,7 +962,6 @@ __global__ void __launch_bounds__(256) gemm_dma_f32_kernel(LA la, LB lb, EP ep, 
         for (int s = 0; s < 8; ++s) fb[j][s] = sb[(8 * lh + s) * BN + wn + j * 32 + l31];
       }
     }
-#if FMI_X6
     bf16x8_t pa[T::TM][3], pb[T::TN][3];
 #pragma unroll
     for (int i = 0; i < T::TM; ++i) split3_bf16(fa[i], pa[i]);
@@ -1000,14 +979,6 @@ __global__ void __launch_bounds__(256) gemm_dma_f32_kernel(LA la, LB lb, EP ep, 
     for (int i = 0; i < T::TM; ++i)
 #pragma unroll
       for (int j = 0; j < T::TN; ++j) acc[i][j] = mfma_x6(pa[i], pb[j], acc[i][j]);
-#else
-#pragma unroll
-    for (int s = 0; s < 8; ++s)
-#pragma unroll
-      for (int i = 0; i < T::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < T::TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][s], fb[j][s], acc[i][j], 0, 0, 0);
-#endif
   };
 
   auto wait_copies = [&](int n) {  // s_waitcnt vmcnt(n): at most n of this wave's copies may still be in flight

@@ -10,9 +10,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // x = x0 + x1 + x2 of 8 significant bits each; x y is then the six products x0 y0, x0 y1, x1 y0, x0 y2, x1 y1, x2 y0 (each exact in the
 // fp32 accumulator) -- the three dropped ones are below 2^-25 |x y|, under one fp32 rounding.  6 bf16 MFMAs of K = 16 replace 8 fp32
 // MFMAs of K = 2: 192 instead of 512 matrix-pipe cycles per 32 x 32 x 16 block; the split costs 5.5 VALU instructions per element.
-#ifndef FMI_X6
-#define FMI_X6 1  // 0: the v_mfma_f32_32x32x2_f32 path (kept for A/B timing; same results to fp32 rounding)
-#endif
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 // two fp32 values -> three words, word i = {piece i of a (low half), piece i of b (high half)}.  Round-to-nearest pieces (v_cvt_pk_bf16_f32):

@@ -22,7 +22,7 @@
 // ---- launcher fragment (inside fmi_attention_bwd_f32, second-structure branch) ----
 #if 0
     static const bool bwd3 = !(getenv("FMI_ATT_BWD3") && getenv("FMI_ATT_BWD3")[0] == '0');
-    if (FMI_X6 && bwd3 && D == 64 && nct == 8) {  // two waves per key block, channel / d halves (attn_bwd3_x6_kernel)
+    if (bwd3 && D == 64 && nct == 8) {  // two waves per key block, channel / d halves (attn_bwd3_x6_kernel)
       constexpr int lds3 = 3 * 32 * 2 * 256 + 3 * 32 * 192 + 256 + 4 * 3 * 32 * (2 * 64 + 16) + 4 * 8192 + 64;
       static fmi_attr_flags attr_set3{};
       int attr_set3_dev;

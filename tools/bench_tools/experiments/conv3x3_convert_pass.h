@@ -18,7 +18,6 @@ __global__ void __launch_bounds__(256) conv3x3_cvt_kernel(C3Args a, ConvEp ep, i
   constexpr int NIA = RA / 16, NIB = 9 * BN / 32;
   constexpr int NLA = (NIA + 3) / 4, NLB = (NIB + 3) / 4;
   constexpr int SA_B = RA * BK * 4, PA_B = 3 * 2 * RP * 16, SB_B = 3 * 3 * 2 * BN * 16;  // bytes
-  static_assert(FMI_X6, "piece images feed the bf16 products");
   extern __shared__ __attribute__((aligned(1024))) unsigned char lds_c3[];
   unsigned char* SA = lds_c3;                // [2][SA_B]
   unsigned char* SB = SA + 2 * SA_B;         // [2][SB_B]

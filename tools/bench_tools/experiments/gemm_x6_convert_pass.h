@@ -1,6 +1,6 @@
 // Implicit-GEMM core on the bf16 matrix pipe with the operand split done ONCE per workgroup ("convert pass").
 //
-// gemm_dma_f32_kernel (gemm_core.h) under FMI_X6 cuts every fp32 fragment into its three bf16 pieces in the wave that consumes it: a
+// gemm_dma_f32_kernel (gemm_core.h) cuts every fp32 fragment into its three bf16 pieces in the wave that consumes it: a
 // 128 x 128 tile is split twice over (two waves share each fragment) at 5.5 VALU instructions per element, and the kernel is VALU bound
 // (161 TFLOP/s at 8 x 128^2 256 -> 256, 220 with the split arithmetic removed).  Here the LDS-DMA still brings fp32 tiles (same
 // loaders, same images), but a tile is converted once, by all 256 threads, into piece images laid out as MFMA fragments:
