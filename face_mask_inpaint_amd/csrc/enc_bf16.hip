@@ -139,9 +139,19 @@ __global__ void __launch_bounds__(256) add_bf16_kernel(const uint4* __restrict__
     y[i] = e_pack8(f);
   }
 }
+// a length that is no multiple of 8: one element per thread (not a hot path: the IR-SE body's tensors are multiples of 64 channels)
+__global__ void __launch_bounds__(256) add_bf16_scalar_kernel(const bf16_t* __restrict__ a, const bf16_t* __restrict__ b, bf16_t* __restrict__ y,
+                                                              int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    y[i] = (bf16_t)e_pack(e_lo(a[i]) + e_lo(b[i]), 0.f);
+}
 extern "C" int fmi_add_bf16(const uint16_t* a, const uint16_t* b, uint16_t* y, int64_t n, void* stream) {
   if (!a || !b || !y || n <= 0) return FMI_ERR_BAD_ARG;
-  if (n % 8 != 0 || !e_al16(a) || !e_al16(b) || !e_al16(y)) return FMI_ERR_UNSUPPORTED;
+  if (n % 8 != 0) {
+    hipLaunchKernelGGL(add_bf16_scalar_kernel, dim3(fmi_bw_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, a, b, y, n);
+    return fmi_launch_status();
+  }
+  if (!e_al16(a) || !e_al16(b) || !e_al16(y)) return FMI_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(add_bf16_kernel, dim3(fmi_bw_grid(n / 8, 256 * 2)), dim3(256), 0, (hipStream_t)stream, (const uint4*)a, (const uint4*)b, (uint4*)y, n / 8);
   return fmi_launch_status();
 }

@@ -1,6 +1,6 @@
 // bf16 activations of the StyleGAN2 decoder (configs C3 / C5): the bandwidth kernels around the bf16 convolutions of conv_bf16.hip.
 // Tensors are NHWC bf16 (uint16_t = raw bits); per-sample / per-channel factors, noise maps, biases and every reduction result
-// stay fp32.  One thread moves 8 channels (16 bytes) per access; C % 8 == 0 throughout.
+// stay fp32.  One thread moves 8 channels (16 bytes) per access; C % 8 == 0 throughout (scale_channels and its gs also have a scalar form).
 //   scale_channels      x * s[n][c]                       ModulatedConv2d: modulation / demodulation (model.py:244-252)
 //   noise_bias_act      lrelu(x + nw*noise + bias) * g    NoiseInjection + FusedLeakyReLU (model.py:282-294, op/fused_act.py:72-85)
 //   upfirdn2d_nhwc      Blur after the up-convolutions    (model.py:52-68, op/upfirdn2d.py:85-147)
@@ -55,9 +55,25 @@ __global__ void __launch_bounds__(256) scale_channels_bf16_kernel(const uint4* _
     y[i] = pack8(f);
   }
 }
+// C % 8 != 0: one element per thread.  Not a hot path (every bf16 network here has C % 8 == 0); it exists so that the op is defined for
+// every channel count its fp32 twin takes
+__global__ void __launch_bounds__(256) scale_channels_bf16_scalar_kernel(const bf16_t* __restrict__ x, const float* __restrict__ s,
+                                                                         bf16_t* __restrict__ y, int64_t PC, int C, int64_t total) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int c = (int)(i % C);
+    const int64_t n = i / PC;
+    y[i] = (bf16_t)pack_bf(bf_lo(x[i]) * s[n * C + c], 0.f);
+  }
+}
 extern "C" int fmi_scale_channels_bf16(const uint16_t* x, const float* s, uint16_t* y, int N, int64_t P, int C, void* stream) {
   if (!x || !s || !y || N <= 0 || P <= 0 || C <= 0) return FMI_ERR_BAD_ARG;
-  if (C % 8 != 0 || !al16(x) || !al16(y) || !al16(s)) return FMI_ERR_UNSUPPORTED;
+  if (C % 8 != 0) {
+    const int64_t total = (int64_t)N * P * C;
+    hipLaunchKernelGGL(scale_channels_bf16_scalar_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, x, s, y, P * C, C,
+                       total);
+    return fmi_launch_status();
+  }
+  if (!al16(x) || !al16(y) || !al16(s)) return FMI_ERR_UNSUPPORTED;
   const int64_t total = (int64_t)N * P * (C / 8);
   hipLaunchKernelGGL(scale_channels_bf16_kernel, dim3(fmi_bw_grid(total, 256 * 2)), dim3(256), 0, (hipStream_t)stream,
                      (const uint4*)x, s, (uint4*)y, P * (C / 8), C / 8, total);
@@ -153,13 +169,35 @@ __global__ void __launch_bounds__(256) scale_channels_gs_bf16_kernel(const uint4
   }
   chunk_reduce_store(acc, ws + ((int64_t)n * gridDim.x + blockIdx.x) * C8 * 8, C8, part);
 }
+// C % 8 != 0: one workgroup per (64-channel stripe, sample), four row lanes combined in a fixed order; gs WRITTEN, no workspace.  A long
+// walk per thread (P / 4 rows): for the odd widths of small side networks, not for a body layer
+__global__ void __launch_bounds__(256) scale_channels_gs_bf16_scalar_kernel(const bf16_t* __restrict__ g, const bf16_t* __restrict__ x,
+                                                                            float* __restrict__ gs, int64_t P, int C) {
+  __shared__ float part[4][64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + tx, n = blockIdx.y;
+  float acc = 0.f;
+  if (c < C)
+    for (int64_t r = ty; r < P; r += 4) {
+      const int64_t o = ((int64_t)n * P + r) * C + c;
+      acc = fmaf(bf_lo(g[o]), bf_lo(x[o]), acc);
+    }
+  part[ty][tx] = acc;
+  __syncthreads();
+  if (ty == 0 && c < C) gs[(int64_t)n * C + c] = (part[0][tx] + part[1][tx]) + (part[2][tx] + part[3][tx]);
+}
 static bool c8_ok(int C) {
   const int c8 = C / 8;
   return C % 8 == 0 && c8 >= 1 && c8 <= 256 && (c8 & (c8 - 1)) == 0;
 }
 extern "C" int fmi_scale_channels_gs_bf16(const uint16_t* g, const uint16_t* x, float* gs, float* ws, int64_t ws_floats, int N, int64_t P,
                                           int C, void* stream) {
-  if (!g || !x || !gs || !ws || N <= 0 || P <= 0 || C <= 0 || N > 65535 || ws_floats < (int64_t)N * C) return FMI_ERR_BAD_ARG;
+  if (!g || !x || !gs || N <= 0 || P <= 0 || C <= 0 || N > 65535) return FMI_ERR_BAD_ARG;
+  if (C % 8 != 0) {  // no eight-channel chunks: the scalar form, which takes no workspace (ws may be NULL)
+    hipLaunchKernelGGL(scale_channels_gs_bf16_scalar_kernel, dim3((unsigned)((C + 63) / 64), N), dim3(256), 0, (hipStream_t)stream, g, x, gs, P, C);
+    return fmi_launch_status();
+  }
+  if (!ws || ws_floats < (int64_t)N * C) return FMI_ERR_BAD_ARG;
   if (!c8_ok(C) || !al16(g) || !al16(x) || !al16(ws)) return FMI_ERR_UNSUPPORTED;
   int64_t blocks = parts_for(P, N, C, ws_floats);
   const int64_t rpb = ceil_div64(P, blocks);

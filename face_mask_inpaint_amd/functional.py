@@ -2484,6 +2484,8 @@ class _GlobalAvgPoolPassF32(torch.autograd.Function):
     def forward(ctx, x):
         _chk(x)
         n, h, w, c = x.shape
+        if h != w:  # the pool below is a k x k window with k = H: H x H of a wider map, and W / H outputs per image where y holds one
+            raise FmiError(f"global_avg_pool_pass takes a square map, got {h} x {w}")
         y = torch.empty((n, 1, 1, c), device=x.device, dtype=torch.float32)
         _L().avgpool_f32(_p(x), _p(y), n, h, w, c, h, _st())
         ctx.shape = x.shape

@@ -254,7 +254,10 @@ int fmi_pack_weight_bf16(const float* src_tab, uint16_t* dst_bta, int T, int A, 
  * second small launch adds them: no fp32 atomics (thousands of them on a few hundred addresses serialise), bit-reproducible.
  *   upfirdn2d_nhwc      the decoder's Blur and its gradient only: up = down = 1, square FIR of 2..4 taps (model.py:52-68)
  *   torgb               out[n][p][o<3] = sum_c x w[o][c] s[n][c] + bias[o] + skip   (ToRGB, model.py:349-369; out / skip fp32)
- *   torgb_bwd           gx (bf16), gw[3][C], gs[N][C], gbias[3] (may be NULL); ws_floats >= 2 * N * (3 C + 8) */
+ *   torgb_bwd           gx (bf16), gw[3][C], gs[N][C], gbias[3] (may be NULL); ws_floats >= 2 * N * (3 C + 8)
+ * scale_channels and scale_channels_gs also take C % 8 != 0, one element per thread (gs: one workgroup per 64-channel stripe and sample
+ * walking P / 4 rows per thread, ws may be NULL) -- for odd widths, not for a body layer.  With C % 8 == 0 they need 16-byte aligned
+ * operands, and gs needs C / 8 a power of two <= 256; anything else is FMI_ERR_UNSUPPORTED. */
 int fmi_scale_channels_bf16(const uint16_t* x, const float* s, uint16_t* y, int N, int64_t P, int C, void* stream);
 int fmi_scale_channels_gs_bf16(const uint16_t* g, const uint16_t* x, float* gs, float* ws, int64_t ws_floats, int N, int64_t P, int C,
                                void* stream);
@@ -464,7 +467,7 @@ int fmi_prelu_bwd_bf16(const uint16_t* g, const uint16_t* x, const float* a, uin
 /* SE gate x residual add (helpers.py:64-72,116-118), plain residual add, AdaptiveAvgPool2d(1) -> fp32 [N][C] (ws >= N C floats), the
  * gradient of the pooled branch joined with the scaled branch's (gx = g + gpool[n][c] / P), MaxPool2d(1, stride) and its backward */
 int fmi_scale_channels_add_bf16(const uint16_t* x, const float* s, const uint16_t* res, uint16_t* y, int N, int64_t P, int C, void* stream);
-int fmi_add_bf16(const uint16_t* a, const uint16_t* b, uint16_t* y, int64_t n, void* stream);
+int fmi_add_bf16(const uint16_t* a, const uint16_t* b, uint16_t* y, int64_t n, void* stream); /* n % 8 != 0: scalar form */
 int fmi_global_avgpool_bf16(const uint16_t* x, float* pooled, float* ws, int64_t ws_floats, int N, int64_t P, int C, void* stream);
 int fmi_add_bcast_bf16(const uint16_t* g, const float* gpool, uint16_t* gx, int N, int64_t P, int C, void* stream);
 /* fp32 twin: gx[n][p][c] = g[n][p][c] + gpool[n][c] / P -- the two gradients of an SE module's input (helpers.py:38-54: avg_pool and the
