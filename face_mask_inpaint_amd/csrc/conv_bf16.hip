@@ -15,6 +15,8 @@
 //    operands come from ds_read_b64_tr_b16 (hardware transpose of a 4-pixel x 16-row block per 16 lanes), two per operand.  The
 //    image is [32-row group][64 pixels][32 rows]: the four pixel rows one transposed read touches are 256 contiguous bytes (one
 //    bank row, conflict-free without a swizzle) and all copies of a thread belong to one pixel (one anchor decode per tile).
+#include <type_traits>
+
 #include "gemm_core.h"
 
 #ifndef FMI_HOST_EMU
@@ -145,8 +147,23 @@ struct ConvSetB {
   float* ws;  // split reduction: fp32 twin of the output (zeroed by the caller), partial sums meet through atomics
 };
 
-template <class T, int BK, int NST = 2>
-__global__ void __launch_bounds__(T::NT) conv_bf16_kernel(ConvSetB set) {
+// Output stages of conv_bf16_kernel.  EpNoneB: the plain store (and the split-reduction / per-sample column scale forms).
+// EpChanB: a per-column stage for the eval-mode IR-SE block (modules/psp/encoders/helpers.py:85-89 / :107-113 of the reference):
+// v = acc * scale[k] + bias[k] (the folded eval BatchNorm behind conv2 and behind the shortcut convolution), y = v > 0 ? v : slope[k] * v
+// (the PReLU behind conv1), one rounding to bf16.  colsum (may be null): the fp32 sums of v over the rows of every FMI_CHAN_COLSUM_ROWS-row
+// block, per sample -- a block straddles at most two samples (the host refuses maps with fewer rows than a tile), so it owns two rows of
+// the workspace: [block][0] = its rows of the sample its first row lies in, [block][1] = its rows of the next sample.  Every row of the
+// workspace is written by exactly one wave, in full: no initialisation, no atomics, the same bits every run.
+struct EpNoneB {};
+struct EpChanB {
+  const float* scale;  // [Nout] or null (= 1)
+  const float* bias;   // [Nout] or null (= 0)
+  const float* slope;  // [Nout] or null (= 1)
+  float* colsum;       // [ceil(M / 64)][2][Nout] or null
+};
+
+template <class T, int BK, int NST = 2, class CH = EpNoneB>
+__global__ void __launch_bounds__(T::NT) conv_bf16_kernel(ConvSetB set, CH ch) {
   const float* const zchunk = fmi_zero_chunk_ptr();  // the zero chunk's address: read from the GOT ONCE (see fmi_zero_chunk_ptr)
   constexpr int BM = T::BM, BN = T::BN, NT = T::NT;
   const int lid = xcd_remap(blockIdx.x, gridDim.x);
@@ -290,6 +307,82 @@ __global__ void __launch_bounds__(T::NT) conv_bf16_kernel(ConvSetB set) {
 
   // epilogue: 4 x 4 transpose inside each quad of lanes -> one row, four consecutive columns per lane, 8-byte bf16 stores
   const int c = l31 & 3, colq = l31 & ~3;
+  if constexpr (std::is_same<CH, EpChanB>::value) {
+    static_assert(T::TM == 2, "a wave owns one 64-row block of the column-sum workspace");
+    // the lane's columns are the same for all of its rows: the three per-column vectors once per 32-column group
+    float4 sc[T::TN], bs[T::TN], sl[T::TN];
+#pragma unroll
+    for (int j = 0; j < T::TN; ++j) {
+      const int col = n0 + wn + j * 32 + colq;
+      sc[j] = sl[j] = make_float4(1.f, 1.f, 1.f, 1.f);
+      bs[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (col < N) {
+        if (ch.scale) sc[j] = *reinterpret_cast<const float4*>(ch.scale + col);
+        if (ch.bias) bs[j] = *reinterpret_cast<const float4*>(ch.bias + col);
+        if (ch.slope) sl[j] = *reinterpret_cast<const float4*>(ch.slope + col);
+      }
+    }
+    const int rb0 = m0 + wm;  // first row of this wave's 64-row block
+    const int bound = ((int)fdiv((uint32_t)rb0, ep.dG) + 1) * (ep.GH * ep.GW);  // first row of the next sample
+    float s0[T::TN][4], s1[T::TN][4];
+#pragma unroll
+    for (int j = 0; j < T::TN; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s0[j][e] = s1[j][e] = 0.f;
+#pragma unroll
+    for (int i = 0; i < T::TM; ++i) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int row = rb0 + i * 32 + 8 * g + 4 * lh + c;
+        const bool rv = row < M;
+        int n_s = 0;
+        const int64_t off = rv ? ep.row_off(row, n_s) : 0;
+#pragma unroll
+        for (int j = 0; j < T::TN; ++j) {
+          float a[4] = {acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
+          quad_transpose(a, c);
+          const int col = n0 + wn + j * 32 + colq;
+          const float scv[4] = {sc[j].x, sc[j].y, sc[j].z, sc[j].w}, bsv[4] = {bs[j].x, bs[j].y, bs[j].z, bs[j].w};
+          const float slv[4] = {sl[j].x, sl[j].y, sl[j].z, sl[j].w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float v = a[e] * scv[e] + bsv[e];
+            if (ch.colsum && rv) {
+              if (row < bound) s0[j][e] += v;
+              else s1[j][e] += v;
+            }
+            a[e] = v > 0.f ? v : slv[e] * v;
+          }
+          if (rv && col < N) {
+            uint2 v;
+            v.x = (uint32_t)f2bf(a[0]) | ((uint32_t)f2bf(a[1]) << 16);
+            v.y = (uint32_t)f2bf(a[2]) | ((uint32_t)f2bf(a[3]) << 16);
+            *reinterpret_cast<uint2*>(ep.y + off + col) = v;
+          }
+        }
+      }
+    }
+    if (ch.colsum) {  // the eight lanes that share a column group hold eight rows each: two quad steps and the two wave halves
+#pragma unroll
+      for (int j = 0; j < T::TN; ++j) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float u0 = s0[j][e], u1 = s1[j][e];
+          u0 += __shfl_xor(u0, 1, 64), u1 += __shfl_xor(u1, 1, 64);
+          u0 += __shfl_xor(u0, 2, 64), u1 += __shfl_xor(u1, 2, 64);
+          u0 += __shfl_xor(u0, 32, 64), u1 += __shfl_xor(u1, 32, 64);
+          s0[j][e] = u0, s1[j][e] = u1;
+        }
+        const int col = n0 + wn + j * 32 + colq;
+        if (c == 0 && lh == 0 && rb0 < M && col < N) {
+          float* dst = ch.colsum + (int64_t)(rb0 >> 6) * 2 * N + col;
+          *reinterpret_cast<float4*>(dst) = make_float4(s0[j][0], s0[j][1], s0[j][2], s0[j][3]);
+          *reinterpret_cast<float4*>(dst + N) = make_float4(s1[j][0], s1[j][1], s1[j][2], s1[j][3]);
+        }
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < T::TM; ++i) {
 #pragma unroll
@@ -383,7 +476,7 @@ static int launch_conv_bf16(ConvSetB& set, int nph, int N, bf16_t* y, float* ws,
     set.tiles_n = (int)tn;                                                                                                        \
     set.ksplit = (int)ks;                                                                                                         \
     set.ws = ks > 1 ? ws : nullptr;                                                                                               \
-    hipLaunchKernelGGL((conv_bf16_kernel<TILE, BK>), dim3((unsigned)tmax, nph, (unsigned)ks), dim3(TILE::NT), 0, st, set);        \
+    hipLaunchKernelGGL((conv_bf16_kernel<TILE, BK>), dim3((unsigned)tmax, nph, (unsigned)ks), dim3(TILE::NT), 0, st, set, EpNoneB{}); \
     if (ks > 1)                                                                                                                   \
       hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(fmi_bw_grid(out_elems / 4, 256)), dim3(256), 0, st, ws, y, out_elems / 4);      \
   } while (0)
@@ -497,6 +590,53 @@ extern "C" int fmi_conv2d_fwd_act_bf16(const fmi_conv_desc* d, const uint16_t* x
   if (bias && ((uintptr_t)bias & 15)) return FMI_ERR_UNSUPPORTED;
   EpActB act{noise, nw, bias, slope, gain, 1};
   return conv2d_fwd_bf16_impl(d, x, wnk, colscale, y, nullptr, 0, &act, stream);
+}
+/* y = prelu(conv(x, W) * scale[k] + bias[k], slope[k]): the per-column output stage EpChanB of conv_bf16_kernel, for the eval-mode IR-SE
+ * block (helpers.py:85-89 / :107-113 of the reference: conv1 + PReLU with slope; conv2 + BatchNorm and the shortcut's 1x1 convolution +
+ * BatchNorm, :82-83 / :104-105, with scale / bias).  colsum: see include/fmi_hip.h. */
+extern "C" int fmi_conv2d_fwd_chan_bf16(const fmi_conv_desc* d, const uint16_t* x, const uint16_t* wnk, const float* scale, const float* bias,
+                                        const float* slope, uint16_t* y, float* colsum, int64_t colsum_floats, void* stream) {
+  int rc = check_desc_b(d);
+  if (rc) return rc;
+  if (!x || !wnk || !y) return FMI_ERR_BAD_ARG;
+  const bool k3 = d->kh == 3 && d->kw == 3 && d->pad == 1, k1 = d->kh == 1 && d->kw == 1 && d->pad == 0;
+  if (!(k3 || k1) || (d->stride != 1 && d->stride != 2) || d->C % 64 != 0 || d->K % 64 != 0) return FMI_ERR_UNSUPPORTED;
+  const int64_t M = (int64_t)d->N * d->OH * d->OW;
+  if (colsum) {
+    if ((int64_t)d->OH * d->OW < 128) return FMI_ERR_UNSUPPORTED;  // a 128-row tile would touch more than two samples
+    if (colsum_floats < ceil_div64(M, FMI_CHAN_COLSUM_ROWS) * 2 * d->K) return FMI_ERR_BAD_ARG;
+  }
+  if (d->x_cstride % 8 != 0 || d->y_cstride % 4 != 0 || !aligned16b(x) || !aligned16b(wnk) || ((uintptr_t)y & 7) || !aligned16b(scale) ||
+      !aligned16b(bias) || !aligned16b(slope) || !aligned16b(colsum))
+    return FMI_ERR_UNSUPPORTED;
+  ConvGeom g{};
+  g.N = d->N; g.IH = d->H; g.IW = d->W; g.C = d->C; g.cstride = d->x_cstride;
+  g.GH = d->OH; g.GW = d->OW; g.S = d->stride;
+  g.nty = d->kh; g.ntx = d->kw; g.dy0 = -d->pad; g.dx0 = -d->pad; g.ystep = 1; g.xstep = 1;
+  g.kh0 = 0; g.kw0 = 0; g.khstep = 1; g.kwstep = 1; g.kw = d->kw;
+  g.pad_mode = 0; g.vec = 6;
+  g.dGW = make_fastdiv(g.GW); g.dG = make_fastdiv(g.GH * g.GW); g.dC = make_fastdiv(g.nty * g.ntx); g.dntx = make_fastdiv(g.ntx);
+  g.img_bs = 0;
+  ConvSetB set{};
+  set.ph[0].la = ConvKB{x, g};
+  set.ph[0].lb = ConvWKB{wnk, g, d->K, d->kh * d->kw};
+  set.ph[0].ep = ConvEpB{y, nullptr, d->OH, d->OW, 1, 0, 0, d->OH, d->OW, d->y_cstride, d->K, g.dGW, g.dG, 1};
+  set.ph[0].M = g.Mdim();
+  set.ph[0].K = g.Kdim();
+  set.N = d->K;
+  set.ksplit = 1;
+  set.ws = nullptr;
+  const EpChanB ch{scale, bias, slope, colsum};
+  hipStream_t st = (hipStream_t)stream;
+  // both tiles have 128 rows in two 64-row wave blocks (the column sums' granularity); 64 output columns take the narrow one
+  const int bn = d->K <= 64 ? 64 : 128;
+  const int64_t tn = ceil_div64(d->K, bn), tiles = ceil_div64(M, 128) * tn;
+  if (tiles > 0x7fffffffLL) return FMI_ERR_UNSUPPORTED;
+  set.tiles_n = (int)tn;
+  set.ph[0].tiles = (int)tiles;
+  if (bn == 64) hipLaunchKernelGGL((conv_bf16_kernel<TB128x64, 64, 2, EpChanB>), dim3((unsigned)tiles, 1, 1), dim3(TB128x64::NT), 0, st, set, ch);
+  else hipLaunchKernelGGL((conv_bf16_kernel<TB128x128, 64, 2, EpChanB>), dim3((unsigned)tiles, 1, 1), dim3(TB128x128::NT), 0, st, set, ch);
+  return fmi_launch_status();
 }
 /* dx = adjoint of the convolution described by d applied to dy; wck = weights packed [C][kh*kw][K] */
 extern "C" int fmi_conv2d_dgrad_bf16(const fmi_conv_desc* d, const uint16_t* dy, const uint16_t* wck, const float* colscale, uint16_t* dx,

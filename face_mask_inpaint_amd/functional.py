@@ -1430,6 +1430,78 @@ def lrelu_conv2d_thin_bf16(x, pw: PackedWeight, bias, slope, pad_mode, act):
     return y
 
 
+# ---- bf16 IR-SE body of the pSp encoder for inference (helpers._Bottleneck.infer_bf16): no autograd nodes -- the caller
+# (GradualStyleEncoder.forward) has refused grad mode.  Activations bf16 NHWC; parameters, folded BatchNorm constants and gates fp32. ----
+CHAN_COLSUM_ROWS = 64  # FMI_CHAN_COLSUM_ROWS (include/fmi_hip.h)
+
+
+def conv2d_chan_bf16(x, wnk, kh, kw, stride, pad, scale=None, bias=None, slope=None, colsum=False):
+    """prelu(conv(x, W) * scale[k] + bias[k], slope[k]) on a bf16 NHWC map in one launch (fmi_conv2d_fwd_chan_bf16); wnk = the bf16 pack
+    [K][kh kw][C].  ``colsum``: returns (y, part) with part the partial column sums of the value before the activation, for
+    ``se_gate`` -- or (y, None) where the map has fewer than 128 pixels and the library leaves the squeeze to the pooling kernel."""
+    _chk(x, wnk, dtype=BF16)
+    _chk(scale, bias, slope)
+    n, h, w, c = x.shape
+    k = wnk.shape[0]
+    if c % 64 or k % 64:
+        raise FmiError(f"the bf16 IR-SE convolution needs C % 64 == 0 and K % 64 == 0, got {c} -> {k}")
+    d, oh, ow = conv_desc(n, h, w, c, k, kh, kw, stride, pad)
+    y = torch.empty((n, oh, ow, k), device=x.device, dtype=BF16)
+    part = None
+    if colsum and oh * ow >= 128:
+        part = _parts_ws(x.device, -(-(n * oh * ow) // CHAN_COLSUM_ROWS) * 2 * k)
+    with _prof(f"conv_fwd_bf16|{n}x{h}x{w} {c}->{k} k{kh}s{stride} +chan", 2.0 * n * oh * ow * k * c * kh * kw):
+        _L().conv2d_fwd_chan_bf16(C.byref(d), _p(x), _p(wnk), _p(scale), _p(bias), _p(slope), _p(y), _p(part), 0 if part is None else part.numel(),
+                                  _st())
+    return (y, part) if colsum else y
+
+
+def se_gate(r, part, fc1, fc2):
+    """SEModule's gates [N, C] fp32 = sigmoid(fc2 . relu(fc1 . mean(r))) in one launch from the partial column sums ``part`` of the
+    convolution that produced r; ``part`` None (a map below 128 pixels): the mean comes from fmi_global_avgpool_bf16 first"""
+    _chk(r, dtype=BF16)
+    _chk(part, fc1, fc2)
+    n, h, w, c = r.shape
+    if c % 16 or c > 512:
+        raise FmiError(f"the one-launch SE gate takes C % 16 == 0 up to 512 channels, got {c}")
+    gates = torch.empty((n, c), device=r.device, dtype=torch.float32)
+    if part is None:
+        pooled = torch.empty((n, c), device=r.device, dtype=torch.float32)
+        ws = _parts_ws(r.device, 64 * n * c)
+        _L().global_avgpool_bf16(_p(r), _p(pooled), _p(ws), ws.numel(), n, h * w, c, _st())
+        _L().se_gate_f32(_p(pooled), 0, h * w, 1.0, _p(fc1), _p(fc2), _p(gates), n, c, _st())
+    else:
+        _L().se_gate_f32(_p(part), CHAN_COLSUM_ROWS, h * w, 1.0 / (h * w), _p(fc1), _p(fc2), _p(gates), n, c, _st())
+    return gates
+
+
+def irse_tail_bf16(r, gates, sc, next_scale=None, next_shift=None, tap=False, sc_stride=1):
+    """the block tail in one pass (fmi_irse_tail_bf16): y = r * gates[n][c] + sc (gates None: r + sc), z = y * next_scale + next_shift
+    (the next block's first eval BatchNorm, from the fp32 y; None without next_scale), the fp32 y where ``tap``.  ``sc`` is read at every
+    ``sc_stride``-th pixel.  Returns (y, z, tap)."""
+    _chk(r, sc, dtype=BF16)
+    _chk(gates, next_scale, next_shift)
+    n, oh, ow, c = r.shape
+    if sc.shape[0] != n or sc.shape[3] != c or (gates is not None and tuple(gates.shape) != (n, c)):
+        raise FmiError(f"irse_tail_bf16: r {tuple(r.shape)}, shortcut {tuple(sc.shape)}, gates {None if gates is None else tuple(gates.shape)}")
+    y = torch.empty_like(r)
+    z = torch.empty_like(r) if next_scale is not None else None
+    t = torch.empty(r.shape, device=r.device, dtype=torch.float32) if tap else None
+    _L().irse_tail_bf16(_p(r), _p(gates), _p(sc), _p(next_scale), _p(next_shift), _p(y), _p(z), _p(t), n, oh, ow, c, sc.shape[1], sc.shape[2],
+                        sc_stride, _st())
+    return y, z, t
+
+
+def irse_stem_bf16(x, scale, shift):
+    """fp32 stem output -> (bf16 x, bf16 x * scale + shift): the hand-over to the bf16 body with block 0's first BatchNorm"""
+    _chk(x, scale, shift)
+    c = x.shape[-1]
+    y = torch.empty(x.shape, device=x.device, dtype=BF16)
+    z = torch.empty_like(y)
+    _L().irse_stem_bf16(_p(x), _p(scale), _p(shift), _p(y), _p(z), x.numel() // c, c, _st())
+    return y, z
+
+
 class _Resize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, oh, ow, mean, std):

@@ -10,7 +10,7 @@ import torch
 from torch.nn import AdaptiveAvgPool2d, BatchNorm2d, Conv2d, MaxPool2d, Module, PReLU, ReLU, Sequential, Sigmoid
 
 from .... import functional as FF
-from ....weights import weight_scope
+from ....weights import packed, weight_scope
 from ...pluralistic_model.external_function import run_conv
 
 
@@ -57,7 +57,7 @@ def batch_norm(bn: BatchNorm2d, x, passthrough=False, slope=1.0, mean_offset=Non
             xp = None
         y = (y, xp) if passthrough else y
         if bn.training and bn.track_running_stats:
-            for kept in ("_fmi_affine", "_fmi_fold"):  # constants folded from the running statistics: the update below writes the buffers
+            for kept in ("_fmi_affine", "_fmi_fold", "_fmi_infer"):  # constants folded from the running statistics: the update below writes the buffers
                 if getattr(bn, kept, None) is not None:  # through raw pointers, which their version counters do not see
                     object.__setattr__(bn, kept, None)
             cnt = x.numel() // x.shape[-1] // groups
@@ -108,6 +108,35 @@ def batch_norm(bn: BatchNorm2d, x, passthrough=False, slope=1.0, mean_offset=Non
             return yp
     y = FF.channel_affine(x, scale, shift)
     return (y, x) if passthrough else y
+
+
+def fold_bn_eval(bn: BatchNorm2d):
+    """(scale, shift) fp32 [C] of an eval-mode BatchNorm2d: scale = gamma / sqrt(var + eps), shift = beta - mean * scale, for the
+    inference form of the body (``_Bottleneck.infer_bf16``).  Kept on the module under FF.conv_bn_relu_eval_bf16's rule: while none of
+    the four tensors changes (storage + version counter) and none requires a gradient; ``batch_norm`` drops them when a training pass
+    writes the running buffers through raw pointers."""
+    ts = (bn.weight, bn.bias, bn.running_var, bn.running_mean)
+    key = None if any(t.requires_grad for t in ts) else tuple((t.data_ptr(), t._version) for t in ts) + (bn.eps,)
+    kept = getattr(bn, "_fmi_infer", None)
+    if key is not None and kept is not None and kept[0] == key:
+        return kept[1], kept[2]
+    with torch.no_grad():  # [C]-sized torch bookkeeping
+        scale = (bn.weight / torch.sqrt(bn.running_var + bn.eps)).contiguous()
+        shift = (bn.bias - bn.running_mean * scale).contiguous()
+    if key is not None:
+        object.__setattr__(bn, "_fmi_infer", (key, scale, shift))
+    return scale, shift
+
+
+def _wnk(conv: Conv2d):
+    """the bf16 pack [K][taps][C] of a prepared convolution, cut from the fp32 pack weight_scope made; kept with that pack (a frozen
+    weight's pack lives while the weight is unchanged, a trainable one is new every forward)"""
+    wf = packed(conv).wf
+    kept = getattr(conv, "_fmi_wnk", None)
+    if kept is None or kept[0] is not wf:
+        kept = (wf, FF._pack_bf16(wf))
+        object.__setattr__(conv, "_fmi_wnk", kept)
+    return kept[1]
 
 
 class SEModule(Module):
@@ -178,6 +207,28 @@ class _Bottleneck(Module):
             if len(self.res_layer) > 5:
                 r = self.res_layer[5].nhwc(r)
             return FF.add(r, sc)
+
+    def infer_bf16(self, x, z, next_bn=None, tap=False):
+        """Eval-mode block on bf16 NHWC activations in 4 launches (5 with a convolution shortcut): conv1 + PReLU, conv2 + BatchNorm
+        (+ the SE squeeze as partial column sums), [shortcut conv + BatchNorm,] SE gate, tail.  ``x`` is the block's input and ``z`` the
+        first BatchNorm of it (res_layer[0]), which the PREVIOUS block's tail (or the stem hand-over) computed from its fp32 value: the
+        BatchNorm cannot be folded into conv1's weights, because conv1 pads z with zeros and the shift is not zero at the border.
+        Returns (y, z', t): the block's output, ``next_bn`` of it (None without next_bn) and its fp32 copy where ``tap``.  The caller
+        holds weight_scope and has refused grad mode."""
+        res = self.res_layer
+        r = FF.conv2d_chan_bf16(z, _wnk(res[1]), 3, 3, 1, 1, slope=res[2].weight.detach())
+        scale, shift = fold_bn_eval(res[4])
+        se = res[5] if len(res) > 5 else None
+        r, part = FF.conv2d_chan_bf16(r, _wnk(res[3]), 3, 3, self._stride, 1, scale=scale, bias=shift, colsum=True) if se is not None else \
+            (FF.conv2d_chan_bf16(r, _wnk(res[3]), 3, 3, self._stride, 1, scale=scale, bias=shift), None)
+        gates = FF.se_gate(r, part, se.fc1.weight.detach(), se.fc2.weight.detach()) if se is not None else None
+        if isinstance(self.shortcut_layer, MaxPool2d):
+            sc, ss = x, self._stride  # MaxPool2d(1, stride): the tail reads every stride-th pixel
+        else:
+            scale, shift = fold_bn_eval(self.shortcut_layer[1])
+            sc, ss = FF.conv2d_chan_bf16(x, _wnk(self.shortcut_layer[0]), 1, 1, self._stride, 0, scale=scale, bias=shift), 1
+        ns, nsh = fold_bn_eval(next_bn) if next_bn is not None else (None, None)
+        return FF.irse_tail_bf16(r, gates, sc, ns, nsh, tap, ss)
 
     def forward(self, x):
         return FF.to_nchw(self.nhwc(FF.to_nhwc(x)))

@@ -65,6 +65,14 @@ class GradualStyleEncoder(Module):
         # parameter gradients); the C = 3 stem, the attention blocks, the FPN and the style heads stay fp32
         dt = getattr(opts, "encoder_dtype", "fp32")
         self.body_dtype = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp32": torch.float32, "float32": torch.float32}.get(dt, dt)
+        # opts.encoder_eval_dtype ("fp32" default / "bf16"): the body of an EVAL-mode forward -- bf16 selects the inference form of the
+        # blocks (helpers._Bottleneck.infer_bf16: BatchNorms folded, 4-5 launches per block, no backward).  Independent of
+        # opts.encoder_dtype, which is the training body; parameters, running statistics and the state_dict are the same in every build
+        edt = getattr(opts, "encoder_eval_dtype", "fp32")
+        if edt not in ("fp32", "bf16"):
+            raise FF.FmiError(f"encoder_eval_dtype must be 'fp32' or 'bf16', got {edt!r}")
+        self.eval_body_dtype = torch.bfloat16 if edt == "bf16" else torch.float32
+        self._widths = tuple(_widths)
         self.use_attention = opts.use_attention
         if opts.use_attention:
             self.attention1 = ExampleGuidedAttention(w4, out_channels=w4)
@@ -74,11 +82,21 @@ class GradualStyleEncoder(Module):
         x = run_conv(self.input_layer[0], x)
         x = FF.prelu(batch_norm(self.input_layer[1], x), self.input_layer[2].weight)
         b16 = self.body_dtype == torch.bfloat16 and self.training
-        if getattr(self, "_fmi_body_b16", None) != b16:  # the body's convolutions need no fp32 piece images while they run on bf16 activations
+        infer16 = self._infer_bf16()
+        if getattr(self, "_fmi_body_b16", None) != (b16 or infer16):  # the body's convolutions need no fp32 piece images while they run on bf16 activations
             for m in self.body.modules():
                 if isinstance(m, nn.Conv2d):
-                    object.__setattr__(m, "_fmi_no_w3", b16)
-            object.__setattr__(self, "_fmi_body_b16", b16)
+                    object.__setattr__(m, "_fmi_no_w3", b16 or infer16)
+            object.__setattr__(self, "_fmi_body_b16", b16 or infer16)
+        if infer16:
+            taps = {}
+            x, z = FF.irse_stem_bf16(x, *helpers.fold_bn_eval(self.body[0].res_layer[0]))
+            for i, l in enumerate(self.body):
+                nxt = self.body[i + 1].res_layer[0] if i + 1 < len(self.body) else None
+                x, z, t = l.infer_bf16(x, z, nxt, tap=i in (6, 20, 23))
+                if t is not None:
+                    taps[i] = t
+            return taps[6], taps[20], taps[23]
         if b16:
             x = x.to(torch.bfloat16)
         taps = {}
@@ -97,7 +115,16 @@ class GradualStyleEncoder(Module):
         """m*r + (1-m)*c with m [N,H,W] (psp_encoders.py:135-138)"""
         return FF.add(FF.mask_mul(r, m, False), FF.mask_mul(c, m, True))
 
+    def _infer_bf16(self):
+        return self.eval_body_dtype == torch.bfloat16 and not self.training
+
     def forward(self, x, ref=None, mask=None):
+        if self._infer_bf16():  # refused before any device call; there is no fp32 detour
+            if torch.is_grad_enabled():
+                raise FF.FmiError("GradualStyleEncoder with encoder_eval_dtype='bf16' is inference only (no backward): call it under "
+                                  "torch.no_grad() or detach the input")
+            if any(w % 64 for w in self._widths):
+                raise FF.FmiError(f"the bf16 inference body needs every width to be a multiple of 64, got {self._widths}")
         with weight_scope(self):
             if ref is not None:
                 assert mask is not None, "ref and mask should both be provided"

@@ -55,6 +55,8 @@ def get_args(argv=None):
     p.add_argument("--decoder_dtype", type=str, default="fp32", choices=("fp32", "bf16"), help="activation type of the synthesis network")
     p.add_argument("--mask_detector_dtype", type=str, default="fp32", choices=("fp32", "bf16"),
                    help="activation type of the mask detector's UNet body (bf16 needs H and W to be multiples of 16)")
+    p.add_argument("--encoder_dtype", type=str, default="fp32", choices=("fp32", "bf16"),
+                   help="activation type of the encoder's IR-SE body (bf16: the fused inference form of its 24 blocks)")
     p.add_argument("--out_dir", type=str, default=None, help="where gen_<id>.jpg / metrics.csv go (default: test_results/<run name>)")
     p.add_argument("--num_batches", type=int, default=2, help="synthetic mode: batches to run")
     return p.parse_args(argv)
@@ -126,7 +128,14 @@ def build(args, device):
         mask_detector.load_state_dict(torch.load(args.mask_detector_path, map_location="cpu", weights_only=True))
     base_function._freeze(mask_detector)
     mask_detector = mask_detector.to(device).eval()
-    generator = pSp(args).to(device).eval()
+    # --encoder_dtype is this harness's name for the encoder's EVAL-mode body (pSp / GradualStyleEncoder: opts.encoder_eval_dtype); their
+    # opts.encoder_dtype is the training body, which an inference run never enters
+    opts = argparse.Namespace(**vars(args))
+    opts.encoder_eval_dtype = getattr(args, "encoder_dtype", "fp32")
+    opts.encoder_dtype = "fp32"
+    generator = pSp(opts).to(device).eval()
+    if opts.encoder_eval_dtype == "bf16":  # a frozen encoder keeps its folded BatchNorm constants and bf16 weight packs between calls
+        base_function._freeze(generator.encoder)
     if generator.latent_avg is None:
         with torch.no_grad():
             generator.latent_avg = generator.decoder.mean_latent(int(1e5))[0].detach()

@@ -799,6 +799,41 @@ int fmi_head1x1_argmax_bf16(const uint16_t* x, const float* w, const float* b, f
 int fmi_head1x1_bwd_bf16(const float* g, const uint16_t* x, const float* w, uint16_t* gx, float* gw, float* gb, double* ws,
                          int64_t ws_doubles, int64_t P, int C, int K, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Inference form of the IR-SE bottleneck blocks of the pSp encoder on bf16 NHWC activations (modules/psp/encoders/helpers.py:56-119,
+ * eval mode: the BatchNorm statistics are constants), csrc/irse_infer_bf16.hip and the per-column output stage of csrc/conv_bf16.hip.
+ * fp32 parameters and arithmetic, one round-to-nearest-even per stored bf16 value, no atomics: every result is bit-reproducible.
+ * An identity-shortcut SE block is conv1, conv2, gate, tail = 4 launches; a block with a convolution shortcut is 5.
+ * ---------------------------------------------------------------------- */
+#define FMI_CHAN_COLSUM_ROWS 64 /* rows of one partial block of fmi_conv2d_fwd_chan_bf16's column sums */
+/* y = prelu(conv(x, W) * scale[k] + bias[k], slope[k]) in one launch; scale / bias / slope are fp32 [K], each may be NULL (1 / 0 / 1).
+ * With slope: Conv2d + PReLU (helpers.py:87 / :109-110); with scale / bias: Conv2d + eval BatchNorm2d folded to scale = gamma /
+ * sqrt(var + eps), bias = beta - mean * scale (helpers.py:88 / :111-112, and the shortcut :82-83 / :104-105).  wnk: bf16 [K][kh*kw][C]
+ * (fmi_pack_weight_bf16).  3x3 pad 1 or 1x1 pad 0, stride 1 or 2, C % 64 == 0, K % 64 == 0, else FMI_ERR_UNSUPPORTED.
+ * colsum (may be NULL; colsum_floats >= ceil(N*OH*OW / 64) * 2 * K, 16-byte aligned, contents irrelevant): the squeeze of the SE module
+ * (helpers.py:67) from this output stage -- row [b][0][k] = the fp32 sum of v = acc * scale + bias (before the rounding) over those of rows
+ * 64 b .. 64 b + 63 (rows = n*OH*OW + oy*OW + ox) that belong to the sample of row 64 b, row [b][1][k] over those of the next sample;
+ * every row is written.  fmi_se_gate_f32 finishes them.  OH*OW < 128: FMI_ERR_UNSUPPORTED with colsum (use fmi_global_avgpool_bf16). */
+int fmi_conv2d_fwd_chan_bf16(const fmi_conv_desc* d, const uint16_t* x, const uint16_t* wnk, const float* scale, const float* bias,
+                             const float* slope, uint16_t* y, float* colsum, int64_t colsum_floats, void* stream);
+/* SEModule's gate (helpers.py:67-71: avg_pool, fc1, relu, fc2, sigmoid) in one launch, one workgroup per sample:
+ * gates[n][c] = sigmoid(fc2 . relu(fc1 . pooled[n])), fc1 fp32 [C/16][C], fc2 fp32 [C][C/16], C % 16 == 0, C <= 512.
+ * rows_per_part > 0: part is the colsum workspace of fmi_conv2d_fwd_chan_bf16 ([blocks of rows_per_part rows][2][C], P rows per sample,
+ * P >= rows_per_part); a sample's partial rows are added in a fixed order and pooled = sum * inv_count.
+ * rows_per_part == 0: part is [N][C] and pooled = part * inv_count (1 for the means of fmi_global_avgpool_bf16). */
+int fmi_se_gate_f32(const float* part, int rows_per_part, int64_t P, float inv_count, const float* fc1, const float* fc2, float* gates, int N,
+                    int C, void* stream);
+/* the block's tail (helpers.py:72 and :94 / :119, and the NEXT block's first BatchNorm :86 / :108) in one pass:
+ * y = r * gate[n][c] + sc (gate NULL: y = r + sc, bottleneck_IR) and z = y * next_scale[c] + next_shift[c] from the fp32 y; y and z are
+ * each rounded once to bf16; tap (may be NULL) receives the fp32 y.  z may be NULL (then next_scale / next_shift are not read).
+ * r, y, z, tap are [N][OH][OW][C]; sc is [N][SH][SW][C] read at (oy * sc_stride, ox * sc_stride) -- the MaxPool2d(1, stride) shortcut
+ * (helpers.py:79 / :101) without a pass of its own; OH == (SH - 1) / sc_stride + 1, sc_stride 1 or 2.  C % 8 == 0, 16-byte pointers. */
+int fmi_irse_tail_bf16(const uint16_t* r, const float* gate, const uint16_t* sc, const float* next_scale, const float* next_shift, uint16_t* y,
+                       uint16_t* z, float* tap, int N, int OH, int OW, int C, int SH, int SW, int sc_stride, void* stream);
+/* hand-over from the fp32 stem (after its PReLU) to the bf16 body: y = bf16(x), z = bf16(x * scale[c] + shift[c]) -- block 0's first
+ * BatchNorm (helpers.py:86 / :108) evaluated on the fp32 x.  C % 8 == 0. */
+int fmi_irse_stem_bf16(const float* x, const float* scale, const float* shift, uint16_t* y, uint16_t* z, int64_t rows, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
