@@ -13,12 +13,11 @@
 //    accumulators AND the row sum -- everything still expressed at the old reference -- are scaled by exp(old - new) exactly once;
 //  * the epilogue's gamma * O + residual is evaluated in fp32 before the one rounding of o.
 // No atomics, no score matrix in memory, no fp32 detour.
-#include "common.h"
+#include "bf16x8.h"
 #include "x6.h"
 
 #define ATT_THR 20.0f
 
-__device__ __forceinline__ float bf16_bits_to_f32(uint32_t h) { return __uint_as_float(h << 16); }
 
 // dynamic LDS of attn_fwd_bf16_kernel: two stages of 64 K rows and 64 V rows at their padded pitches
 template <int D, int NCT>
@@ -182,10 +181,10 @@ __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_bf16_kernel(const uint16_
       for (int e = 0; e < 4; ++e) f[e] = acc[c][4 * g + e] * inv;
       if (gamma) {
         const uint2 r = *reinterpret_cast<const uint2*>(res + off);
-        f[0] = fmaf(gm, f[0], bf16_bits_to_f32(r.x & 0xFFFFu));
-        f[1] = fmaf(gm, f[1], bf16_bits_to_f32(r.x >> 16));
-        f[2] = fmaf(gm, f[2], bf16_bits_to_f32(r.y & 0xFFFFu));
-        f[3] = fmaf(gm, f[3], bf16_bits_to_f32(r.y >> 16));
+        f[0] = fmaf(gm, f[0], bf_lo(r.x));
+        f[1] = fmaf(gm, f[1], bf_hi(r.x));
+        f[2] = fmaf(gm, f[2], bf_lo(r.y));
+        f[3] = fmaf(gm, f[3], bf_hi(r.y));
       }
       *reinterpret_cast<uint2*>(o + off) = make_uint2(cvt_pk_bf16(f[0], f[1]), cvt_pk_bf16(f[2], f[3]));
     }

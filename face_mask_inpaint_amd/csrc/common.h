@@ -3,6 +3,9 @@
 #include <stdint.h>
 #include "../../include/fmi_hip.h"
 
+// may p be accessed 16 bytes at a time?  The launchers' test for the vector form of a kernel
+static inline bool fmi_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 #ifdef FMI_HOST_EMU
 // CPU emulation build (tests/test_host_geometry.py): the operand loaders and epilogues of gemm_core.h are
 // compiled with g++ and driven by a plain triple loop, so that every piece of index algebra of the implicit

@@ -17,19 +17,11 @@
 //    bank row, conflict-free without a swizzle) and all copies of a thread belong to one pixel (one anchor decode per tile).
 #include <type_traits>
 
+#include "bf16x8.h"
 #include "gemm_core.h"
 
 #ifndef FMI_HOST_EMU
-typedef uint16_t bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ uint16_t f2bf(float f) {  // round to nearest even (inputs are finite)
-  uint32_t u = __float_as_uint(f);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
-static bool aligned16b(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // loaders (LDS-DMA hooks only: chunk = 8 consecutive reduction elements of one row)
@@ -355,8 +347,8 @@ __global__ void __launch_bounds__(T::NT) conv_bf16_kernel(ConvSetB set, CH ch) {
           }
           if (rv && col < N) {
             uint2 v;
-            v.x = (uint32_t)f2bf(a[0]) | ((uint32_t)f2bf(a[1]) << 16);
-            v.y = (uint32_t)f2bf(a[2]) | ((uint32_t)f2bf(a[3]) << 16);
+            v.x = bf_pack2(a[0], a[1]);
+            v.y = bf_pack2(a[2], a[3]);
             *reinterpret_cast<uint2*>(ep.y + off + col) = v;
           }
         }
@@ -410,13 +402,13 @@ __global__ void __launch_bounds__(T::NT) conv_bf16_kernel(ConvSetB set, CH ch) {
         }
         if (ep.vec) {
           uint2 v;
-          v.x = (uint32_t)f2bf(a[0]) | ((uint32_t)f2bf(a[1]) << 16);
-          v.y = (uint32_t)f2bf(a[2]) | ((uint32_t)f2bf(a[3]) << 16);
+          v.x = bf_pack2(a[0], a[1]);
+          v.y = bf_pack2(a[2], a[3]);
           *reinterpret_cast<uint2*>(ep.y + off + col) = v;
         } else {
 #pragma unroll
           for (int e = 0; e < 4; ++e)
-            if (col + e < N) ep.y[off + col + e] = f2bf(a[e]);
+            if (col + e < N) ep.y[off + col + e] = bf_round(a[e]);
         }
       }
     }
@@ -427,8 +419,8 @@ __global__ void __launch_bounds__(256) f32_to_bf16_kernel(const float* __restric
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     const float4 v = reinterpret_cast<const float4*>(src)[i];
     uint2 o;
-    o.x = (uint32_t)f2bf(v.x) | ((uint32_t)f2bf(v.y) << 16);
-    o.y = (uint32_t)f2bf(v.z) | ((uint32_t)f2bf(v.w) << 16);
+    o.x = bf_pack2(v.x, v.y);
+    o.y = bf_pack2(v.z, v.w);
     reinterpret_cast<uint2*>(dst)[i] = o;
   }
 }
@@ -554,7 +546,7 @@ static int conv2d_fwd_bf16_impl(const fmi_conv_desc* d, const uint16_t* x, const
   int rc = check_desc_b(d);
   if (rc) return rc;
   if (!x || !wnk || !y) return FMI_ERR_BAD_ARG;
-  if (d->C % 32 != 0 || d->x_cstride % 8 != 0 || !aligned16b(x) || !aligned16b(wnk)) return FMI_ERR_UNSUPPORTED;
+  if (d->C % 32 != 0 || d->x_cstride % 8 != 0 || !fmi_al16(x) || !fmi_al16(wnk)) return FMI_ERR_UNSUPPORTED;
   ConvGeom g{};
   g.N = d->N; g.IH = d->H; g.IW = d->W; g.C = d->C; g.cstride = d->x_cstride;
   g.GH = d->OH; g.GW = d->OW; g.S = d->stride;
@@ -606,8 +598,8 @@ extern "C" int fmi_conv2d_fwd_chan_bf16(const fmi_conv_desc* d, const uint16_t* 
     if ((int64_t)d->OH * d->OW < 128) return FMI_ERR_UNSUPPORTED;  // a 128-row tile would touch more than two samples
     if (colsum_floats < ceil_div64(M, FMI_CHAN_COLSUM_ROWS) * 2 * d->K) return FMI_ERR_BAD_ARG;
   }
-  if (d->x_cstride % 8 != 0 || d->y_cstride % 4 != 0 || !aligned16b(x) || !aligned16b(wnk) || ((uintptr_t)y & 7) || !aligned16b(scale) ||
-      !aligned16b(bias) || !aligned16b(slope) || !aligned16b(colsum))
+  if (d->x_cstride % 8 != 0 || d->y_cstride % 4 != 0 || !fmi_al16(x) || !fmi_al16(wnk) || ((uintptr_t)y & 7) || !fmi_al16(scale) ||
+      !fmi_al16(bias) || !fmi_al16(slope) || !fmi_al16(colsum))
     return FMI_ERR_UNSUPPORTED;
   ConvGeom g{};
   g.N = d->N; g.IH = d->H; g.IW = d->W; g.C = d->C; g.cstride = d->x_cstride;
@@ -644,7 +636,7 @@ extern "C" int fmi_conv2d_dgrad_bf16(const fmi_conv_desc* d, const uint16_t* dy,
   int rc = check_desc_b(d);
   if (rc) return rc;
   if (!dy || !wck || !dx) return FMI_ERR_BAD_ARG;
-  if (d->K % 32 != 0 || d->y_cstride % 8 != 0 || !aligned16b(dy) || !aligned16b(wck)) return FMI_ERR_UNSUPPORTED;
+  if (d->K % 32 != 0 || d->y_cstride % 8 != 0 || !fmi_al16(dy) || !fmi_al16(wck)) return FMI_ERR_UNSUPPORTED;
   const int s = d->stride;
   if (s > 2) return FMI_ERR_UNSUPPORTED;  // at most four sub-pixel phases per launch
   ConvSetB set{};
@@ -692,7 +684,7 @@ __global__ void __launch_bounds__(256) pack_bta_bf16_kernel(const float* __restr
     const int a = (int)(i % A);
     const int64_t r = i / A;
     const int t = (int)(r % T), b = (int)(r / T);
-    dst[i] = f2bf(src[((int64_t)t * A + a) * B + b]);
+    dst[i] = bf_round(src[((int64_t)t * A + a) * B + b]);
   }
 }
 extern "C" int fmi_pack_weight_bf16(const float* src_tab, uint16_t* dst_bta, int T, int A, int B, void* stream) {
@@ -874,7 +866,7 @@ extern "C" int fmi_conv2d_wgrad_bf16(const fmi_conv_desc* d, const uint16_t* x, 
   int rc = check_desc_b(d);
   if (rc) return rc;
   if (!x || !dy || !dwf) return FMI_ERR_BAD_ARG;
-  if (d->C % 32 != 0 || d->K % 8 != 0 || d->x_cstride % 8 != 0 || d->y_cstride % 8 != 0 || !aligned16b(x) || !aligned16b(dy))
+  if (d->C % 32 != 0 || d->K % 8 != 0 || d->x_cstride % 8 != 0 || d->y_cstride % 8 != 0 || !fmi_al16(x) || !fmi_al16(dy))
     return FMI_ERR_UNSUPPORTED;
   WgArgsB a{};
   a.x = x; a.dy = dy; a.dwf = dwf;

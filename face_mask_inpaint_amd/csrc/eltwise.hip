@@ -1,9 +1,8 @@
 // Bandwidth-class element-wise kernels: activations, mask handling, example-guided blend, VAE sampling,
 // and the reference's fused_bias_act native op.  All are grid-stride, float4-vectorised where the views
 // are 16-byte aligned, and sized to fill 256 CUs (common.h: fmi_bw_grid).  Roofline: HBM bytes in + out.
-#include "common.h"
+#include "bf16x8.h"
 
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 template <int OP>
 __device__ __forceinline__ float ew_op(float a, float b, float p0) {
@@ -57,7 +56,7 @@ __global__ void __launch_bounds__(256) eltwise_kernel(const float* __restrict__ 
 template <int OP>
 static int launch_ew(const float* a, const float* b, float* y, int64_t n, float p0, hipStream_t st) {
   if (ew_binary<OP>() && !b) return FMI_ERR_BAD_ARG;
-  const bool vec = al16(a) && al16(y) && (!ew_binary<OP>() || al16(b));
+  const bool vec = fmi_al16(a) && fmi_al16(y) && (!ew_binary<OP>() || fmi_al16(b));
   const int grid = fmi_bw_grid(vec ? (n + 3) / 4 : n, 256);
   if (vec) hipLaunchKernelGGL((eltwise_kernel<OP, true>), dim3(grid), dim3(256), 0, st, a, b, y, n, p0);
   else hipLaunchKernelGGL((eltwise_kernel<OP, false>), dim3(grid), dim3(256), 0, st, a, b, y, n, p0);
@@ -223,24 +222,16 @@ extern "C" int fmi_vae_sample_bwd_f32(const float* gz, const float* o_src, const
 }
 
 // ---- the reference's fused_bias_act (NCHW contiguous; op/fused_bias_act_kernel.cu:36-47 semantics) ----
-__device__ __forceinline__ float fba_ld(const float* p, int64_t i) { return p[i]; }
-__device__ __forceinline__ float fba_ld(const uint16_t* p, int64_t i) { return __uint_as_float((uint32_t)p[i] << 16); }
-__device__ __forceinline__ void fba_st(float* p, int64_t i, float v) { p[i] = v; }
-__device__ __forceinline__ void fba_st(uint16_t* p, int64_t i, float v) {  // bf16, round to nearest even
-  uint32_t u = __float_as_uint(v);
-  if ((u & 0x7fffffffu) > 0x7f800000u) u |= 0x00400000u;
-  else u += 0x7fffu + ((u >> 16) & 1u);
-  p[i] = (uint16_t)(u >> 16);
-}
+// x is a caller's tensor and may hold NaNs: the bf16 stores use bf_st_nan (a NaN stays a quiet NaN instead of rounding into an infinity)
 template <class T>
 __global__ void __launch_bounds__(256) fused_bias_act_kernel(const T* __restrict__ x, const T* __restrict__ bias,
                                                              const T* __restrict__ ref, T* __restrict__ out,
                                                              int64_t n, int step_b, int size_b, int act, int grad,
                                                              float alpha, float scale) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    float v = fba_ld(x, i);
-    if (bias) v += fba_ld(bias, (i / step_b) % size_b);
-    const float r = ref ? fba_ld(ref, i) : 0.f;
+    float v = bf_ld(x, i);
+    if (bias) v += bf_ld(bias, (i / step_b) % size_b);
+    const float r = ref ? bf_ld(ref, i) : 0.f;
     float y;
     if (act == 3) {
       if (grad == 0) y = v > 0.f ? v : v * alpha;
@@ -249,7 +240,7 @@ __global__ void __launch_bounds__(256) fused_bias_act_kernel(const T* __restrict
     } else {
       y = grad == 2 ? 0.f : v;
     }
-    fba_st(out, i, y * scale);
+    bf_st_nan(out, i, y * scale);
   }
 }
 // 16-byte vector form: V consecutive elements share a bias entry when step_b % V == 0
@@ -264,11 +255,11 @@ __global__ void __launch_bounds__(256) fused_bias_act_vec_kernel(const T* __rest
     const Pack px = reinterpret_cast<const Pack*>(x)[i];
     Pack pr = px, po;
     if (ref) pr = reinterpret_cast<const Pack*>(ref)[i];
-    const float b = bias ? fba_ld(bias, ((i * V) / step_b) % size_b) : 0.f;
+    const float b = bias ? bf_ld(bias, ((i * V) / step_b) % size_b) : 0.f;
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-      const float v = fba_ld(px.e, j) + b;
-      const float r = ref ? fba_ld(pr.e, j) : 0.f;
+      const float v = bf_ld(px.e, j) + b;
+      const float r = ref ? bf_ld(pr.e, j) : 0.f;
       float y;
       if (act == 3) {
         if (grad == 0) y = v > 0.f ? v : v * alpha;
@@ -277,7 +268,7 @@ __global__ void __launch_bounds__(256) fused_bias_act_vec_kernel(const T* __rest
       } else {
         y = grad == 2 ? 0.f : v;
       }
-      fba_st(po.e, j, y * scale);
+      bf_st_nan(po.e, j, y * scale);
     }
     reinterpret_cast<Pack*>(out)[i] = po;
   }
@@ -363,8 +354,6 @@ extern "C" int fmi_noise_bias_act_f32(const float* x, const float* bias, const f
 }
 
 // dbias[c] += sum over (n, hw) of g[n][c][hw]   (NCHW; grad_bias of FusedLeakyReLU, op/fused_act.py:29-36)
-__device__ __forceinline__ float bg_load(const float* p, int64_t i) { return p[i]; }
-__device__ __forceinline__ float bg_load(const uint16_t* p, int64_t i) { return __uint_as_float((uint32_t)p[i] << 16); }
 template <typename T>
 __global__ void __launch_bounds__(256) bias_grad_nchw_kernel(const T* __restrict__ g, int N, int C, int64_t HW,
                                                              float* __restrict__ dbias) {
@@ -374,7 +363,7 @@ __global__ void __launch_bounds__(256) bias_grad_nchw_kernel(const T* __restrict
   for (int n = blockIdx.x / C; n < N; n += gridDim.x / C) {
     const T* p = g + ((int64_t)n * C + c) * HW;
     float s = 0.f;
-    for (int64_t i = (int64_t)blockIdx.y * 256 + threadIdx.x; i < HW; i += (int64_t)gridDim.y * 256) s += bg_load(p, i);
+    for (int64_t i = (int64_t)blockIdx.y * 256 + threadIdx.x; i < HW; i += (int64_t)gridDim.y * 256) s += bf_ld(p, i);
     s = block_sum_256(s, red);
     if (threadIdx.x == 0) atomicAdd(dbias + c, s);
   }

@@ -185,8 +185,8 @@ extern "C" int fmi_gan_image_head_fwd_f32(const float* gen, const float* gt, con
     if (!al4(q)) return FMI_ERR_BAD_ARG;
   if (reinterpret_cast<uintptr_t>(ws_part) & 7) return FMI_ERR_BAD_ARG;
   const int64_t hw = (int64_t)H * W, ohw = (int64_t)OH * OW;
-  const bool vec_out = (OW & 3) == 0 && al16(x_in) && al16(y_in);
-  const bool vec_in = (hw & 3) == 0 && al16(gen) && al16(gt);
+  const bool vec_out = (OW & 3) == 0 && fmi_al16(x_in) && fmi_al16(y_in);
+  const bool vec_in = (hw & 3) == 0 && fmi_al16(gen) && fmi_al16(gt);
   const int64_t per = vec_out ? ohw >> 2 : ohw;
   const int gx = gan_fwd_gx(per, vec_in ? hw >> 2 : hw);
   if (ws_doubles < (int64_t)N * gx) return FMI_ERR_BAD_ARG;  // one partial row per workgroup
@@ -210,7 +210,7 @@ extern "C" int fmi_gan_image_head_bwd_f32(const float* gen, const float* gt, con
   for (const void* q : all)
     if (!al4(q)) return FMI_ERR_BAD_ARG;
   const int64_t hw = (int64_t)H * W;
-  const bool vec = (W & 3) == 0 && al16(gen) && al16(gt) && al16(mask) && al16(d_gen);
+  const bool vec = (W & 3) == 0 && fmi_al16(gen) && fmi_al16(gt) && fmi_al16(mask) && fmi_al16(d_gen);
   const int64_t per = vec ? hw >> 2 : hw;
   const dim3 grid(rows_for(per, 1024), N), block(256);
   const double count = 3.0 * (double)N * (double)hw;

@@ -64,7 +64,6 @@ __global__ void plane_rows_finish_kernel(const double* __restrict__ part, int gx
   out[i] = (T)(s * scale);
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 // workgroups (= partial rows) for work_items at 256 per workgroup, within [1, cap]
 inline int rows_for(int64_t work_items, int cap) {

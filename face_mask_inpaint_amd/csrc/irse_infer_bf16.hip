@@ -80,18 +80,18 @@ __global__ void __launch_bounds__(256) irse_tail_kernel(const uint4* __restrict_
       si = ((n * SH + (int64_t)oy * ss) * SW + (int64_t)ox * ss) * C8 + c8;
     }
     float f[8], s[8];
-    e_unpack8(r[i], f);
-    e_unpack8(sc[si], s);
+    bf_unpack8(r[i], f);
+    bf_unpack8(sc[si], s);
     if (gate) {
       float g[8];
-      e_load8f(gate + (n * C8 + c8) * 8, g);
+      bf_load8f(gate + (n * C8 + c8) * 8, g);
 #pragma unroll
       for (int e = 0; e < 8; ++e) f[e] = f[e] * g[e] + s[e];
     } else {
 #pragma unroll
       for (int e = 0; e < 8; ++e) f[e] += s[e];
     }
-    y[i] = e_pack8(f);
+    y[i] = bf_pack8(f);
     if (tap) {
       float4* t = reinterpret_cast<float4*>(tap + i * 8);
       t[0] = make_float4(f[0], f[1], f[2], f[3]);
@@ -99,11 +99,11 @@ __global__ void __launch_bounds__(256) irse_tail_kernel(const uint4* __restrict_
     }
     if (z) {
       float a[8], b[8];
-      e_load8f(nscale + c8 * 8, a);
-      e_load8f(nshift + c8 * 8, b);
+      bf_load8f(nscale + c8 * 8, a);
+      bf_load8f(nshift + c8 * 8, b);
 #pragma unroll
       for (int e = 0; e < 8; ++e) f[e] = f[e] * a[e] + b[e];
-      z[i] = e_pack8(f);
+      z[i] = bf_pack8(f);
     }
   }
 }
@@ -112,8 +112,8 @@ extern "C" int fmi_irse_tail_bf16(const uint16_t* r, const float* gate, const ui
   if (!r || !sc || !y || N <= 0 || OH <= 0 || OW <= 0 || C <= 0 || SH <= 0 || SW <= 0 || (z && (!next_scale || !next_shift))) return FMI_ERR_BAD_ARG;
   if (sc_stride != 1 && sc_stride != 2) return FMI_ERR_UNSUPPORTED;
   if (OH != (SH - 1) / sc_stride + 1 || OW != (SW - 1) / sc_stride + 1) return FMI_ERR_BAD_ARG;
-  if (C % 8 != 0 || !e_al16(r) || !e_al16(gate) || !e_al16(sc) || !e_al16(next_scale) || !e_al16(next_shift) || !e_al16(y) || !e_al16(z) ||
-      !e_al16(tap))
+  if (C % 8 != 0 || !fmi_al16(r) || !fmi_al16(gate) || !fmi_al16(sc) || !fmi_al16(next_scale) || !fmi_al16(next_shift) || !fmi_al16(y) || !fmi_al16(z) ||
+      !fmi_al16(tap))
     return FMI_ERR_UNSUPPORTED;
   const int64_t total = (int64_t)N * OH * OW * (C / 8);
   hipLaunchKernelGGL(irse_tail_kernel, dim3(fmi_bw_grid(total, 256 * 2)), dim3(256), 0, (hipStream_t)stream, (const uint4*)r, gate, (const uint4*)sc,
@@ -127,18 +127,18 @@ __global__ void __launch_bounds__(256) irse_stem_kernel(const float* __restrict_
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int c8 = (int)(i % C8);
     float f[8], a[8], b[8];
-    e_load8f(x + i * 8, f);
-    e_load8f(scale + c8 * 8, a);
-    e_load8f(shift + c8 * 8, b);
-    y[i] = e_pack8(f);
+    bf_load8f(x + i * 8, f);
+    bf_load8f(scale + c8 * 8, a);
+    bf_load8f(shift + c8 * 8, b);
+    y[i] = bf_pack8(f);
 #pragma unroll
     for (int e = 0; e < 8; ++e) f[e] = f[e] * a[e] + b[e];
-    z[i] = e_pack8(f);
+    z[i] = bf_pack8(f);
   }
 }
 extern "C" int fmi_irse_stem_bf16(const float* x, const float* scale, const float* shift, uint16_t* y, uint16_t* z, int64_t rows, int C, void* stream) {
   if (!x || !scale || !shift || !y || !z || rows <= 0 || C <= 0) return FMI_ERR_BAD_ARG;
-  if (C % 8 != 0 || !e_al16(x) || !e_al16(scale) || !e_al16(shift) || !e_al16(y) || !e_al16(z)) return FMI_ERR_UNSUPPORTED;
+  if (C % 8 != 0 || !fmi_al16(x) || !fmi_al16(scale) || !fmi_al16(shift) || !fmi_al16(y) || !fmi_al16(z)) return FMI_ERR_UNSUPPORTED;
   const int64_t total = rows * (C / 8);
   hipLaunchKernelGGL(irse_stem_kernel, dim3(fmi_bw_grid(total, 256 * 2)), dim3(256), 0, (hipStream_t)stream, x, scale, shift, (uint4*)y, (uint4*)z,
                      C / 8, total);

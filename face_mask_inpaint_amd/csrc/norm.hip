@@ -4,23 +4,19 @@
 // E[x^2]-E[x]^2 form does not lose precision at 512x512 planes.
 //
 // Layout of a workgroup: 256 threads = PL pixel lanes x CG channel groups (4 channels each), CG = C/4.
-#include "common.h"
+#include "bf16x8.h"
+#include "sum_parts.h"
 
 // Element types: float, or bf16 held as uint16_t (the mixed-precision IR-SE50 body of the pSp encoder: bf16 activations, fp32
 // statistics / parameters / arithmetic).  Four channels per thread either way: a 16-byte or an 8-byte access.
-__device__ __forceinline__ float nb_bf2f(uint32_t h) { return __uint_as_float(h << 16); }
-__device__ __forceinline__ uint32_t nb_f2bf(float f) {  // round to nearest even
-  const uint32_t u = __float_as_uint(f);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
 __device__ __forceinline__ float4 nld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float4 nld4(const uint16_t* p) {
   const uint2 v = *reinterpret_cast<const uint2*>(p);
-  return make_float4(nb_bf2f(v.x & 0xffffu), nb_bf2f(v.x >> 16), nb_bf2f(v.y & 0xffffu), nb_bf2f(v.y >> 16));
+  return make_float4(bf_lo(v.x), bf_hi(v.x), bf_lo(v.y), bf_hi(v.y));
 }
 __device__ __forceinline__ void nst4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ void nst4(uint16_t* p, float4 v) {
-  *reinterpret_cast<uint2*>(p) = make_uint2(nb_f2bf(v.x) | (nb_f2bf(v.y) << 16), nb_f2bf(v.z) | (nb_f2bf(v.w) << 16));
+  *reinterpret_cast<uint2*>(p) = make_uint2(bf_round(v.x) | (bf_round(v.y) << 16), bf_round(v.z) | (bf_round(v.w) << 16));  // finite: this library's own activations
 }
 
 // pixels per workgroup chunk: at least 64, grown until at most `cap` workgroups exist.  With fp64 atomics (no workspace) every
@@ -33,32 +29,6 @@ static int rows_per_block(int N, int HW, int64_t cap, int64_t r0) {
   while ((int64_t)N * ((HW + r - 1) / r) > cap && r < (1 << 20)) r *= 2;
   return (int)r;
 }
-// out[g][i] = sum_{p < nparts} ws[(g * nparts + p) * width + i].  64 columns x 16 row lanes per workgroup, 8 independent loads in
-// flight per thread (one thread per column walking 1024 rows took 37 us: pure load latency, 200 launches per pSp step)
-__global__ void __launch_bounds__(1024) sum_parts_f64_kernel(const double* __restrict__ ws, double* __restrict__ out, int nparts, int width) {
-  __shared__ double part[16][64];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + tx;
-  const double* p = ws + (int64_t)blockIdx.y * nparts * width + i;
-  double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (i < width) {
-    int q = ty;
-    for (; q + 7 * 16 < nparts; q += 8 * 16) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) a[u] += p[(int64_t)(q + 16 * u) * width];
-    }
-    for (; q < nparts; q += 16) a[0] += p[(int64_t)q * width];
-  }
-  part[ty][tx] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-  __syncthreads();
-  if (ty == 0 && i < width) {
-    double t = 0;
-#pragma unroll
-    for (int l = 0; l < 16; ++l) t += part[l][tx];
-    out[(int64_t)blockIdx.y * width + i] = t;
-  }
-}
-
 // sums[n][c][0..1] += (sum f0, sum f1) where (f0,f1) = fn(x, g) per element
 template <int MODE, typename T>  // 0: (x, x*x)   1: backward reductions (g', g'*xhat)
 __global__ void __launch_bounds__(256) in_reduce_kernel(const T* __restrict__ x, const T* __restrict__ gy,
@@ -163,7 +133,7 @@ static void launch_in_reduce(const T* x, const T* gy, const float* stats, const 
     const int rpb = rows_per_block(N, HW, cap, 64);
     const int blocks = (HW + rpb - 1) / rpb;
     hipLaunchKernelGGL((in_reduce_kernel<MODE, T>), dim3(blocks, N), dim3(256), 0, st, x, gy, stats, gamma, beta, ws, HW, C, slope, rpb, 1);
-    hipLaunchKernelGGL(sum_parts_f64_kernel, dim3((C * 2 + 63) / 64, N), dim3(1024), 0, st, (const double*)ws, sums, blocks, C * 2);
+    launch_sum_parts<double>(ws, sums, blocks, C * 2, N, st);
     return;
   }
   const int rpb = fmi_det() ? HW : rows_per_block(N, HW, 2048, 512);  // reproducible mode: one block per sample, one contribution per address

@@ -2,7 +2,6 @@
 // channels (float4) of an output pixel when C % 4 == 0, otherwise one thread per element.
 #include "common.h"
 
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 template <int V>
 struct VecT;
@@ -111,7 +110,7 @@ extern "C" int fmi_avgpool_f32(const float* x, float* y, int N, int H, int W, in
   if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || k <= 0 || H / k <= 0 || W / k <= 0) return FMI_ERR_BAD_ARG;
   {
     const int C4 = C / 4;
-    if (k == H && k == W && k >= 8 && C % 4 == 0 && C4 <= 256 && (C4 & (C4 - 1)) == 0 && al16(x) && al16(y) && N <= 65535) {
+    if (k == H && k == W && k >= 8 && C % 4 == 0 && C4 <= 256 && (C4 & (C4 - 1)) == 0 && fmi_al16(x) && fmi_al16(y) && N <= 65535) {
       const int64_t HW = (int64_t)H * W;
       int64_t blocks = ceil_div64(HW, 128);
       if (blocks * N > 2048) blocks = ceil_div64(2048, N);
@@ -124,7 +123,7 @@ extern "C" int fmi_avgpool_f32(const float* x, float* y, int N, int H, int W, in
       return fmi_launch_status();
     }
   }
-  const bool v4 = (C % 4 == 0) && al16(x) && al16(y);
+  const bool v4 = (C % 4 == 0) && fmi_al16(x) && fmi_al16(y);
   const int CV = v4 ? C / 4 : C;
   const int64_t total = (int64_t)N * (H / k) * (W / k) * CV;
   if (v4) hipLaunchKernelGGL((avgpool_kernel<4>), dim3(fmi_bw_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y, H, W, CV, k, total);
@@ -133,7 +132,7 @@ extern "C" int fmi_avgpool_f32(const float* x, float* y, int N, int H, int W, in
 }
 extern "C" int fmi_avgpool_bwd_f32(const float* gy, float* gx, int N, int H, int W, int C, int k, void* stream) {
   if (!gy || !gx || N <= 0 || H <= 0 || W <= 0 || C <= 0 || k <= 0 || H / k <= 0 || W / k <= 0) return FMI_ERR_BAD_ARG;
-  const bool v4 = (C % 4 == 0) && al16(gx) && al16(gy);
+  const bool v4 = (C % 4 == 0) && fmi_al16(gx) && fmi_al16(gy);
   const int CV = v4 ? C / 4 : C;
   const int64_t total = (int64_t)N * H * W * CV;
   if (v4) hipLaunchKernelGGL((avgpool_bwd_kernel<4>), dim3(fmi_bw_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, gy, gx, H, W, CV, k, total);
@@ -359,7 +358,7 @@ __global__ void __launch_bounds__(256) adaptive_avgpool_bwd_kernel(const float* 
 }
 extern "C" int fmi_adaptive_avgpool_f32(const float* x, float* y, int N, int H, int W, int C, int OH, int OW, void* stream) {
   if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || OH <= 0 || OW <= 0) return FMI_ERR_BAD_ARG;
-  const bool v4 = C % 4 == 0 && al16(x) && al16(y);
+  const bool v4 = C % 4 == 0 && fmi_al16(x) && fmi_al16(y);
   const int64_t total = (int64_t)N * OH * OW * (v4 ? C / 4 : C);
   if (v4)
     hipLaunchKernelGGL(adaptive_avgpool_kernel<4>, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y, H, W, OH, OW, C / 4, total);
@@ -369,7 +368,7 @@ extern "C" int fmi_adaptive_avgpool_f32(const float* x, float* y, int N, int H, 
 }
 extern "C" int fmi_adaptive_avgpool_bwd_f32(const float* gy, float* gx, int N, int H, int W, int C, int OH, int OW, void* stream) {
   if (!gy || !gx || N <= 0 || H <= 0 || W <= 0 || C <= 0 || OH <= 0 || OW <= 0) return FMI_ERR_BAD_ARG;
-  const bool v4 = C % 4 == 0 && al16(gy) && al16(gx);
+  const bool v4 = C % 4 == 0 && fmi_al16(gy) && fmi_al16(gx);
   const int64_t total = (int64_t)N * H * W * (v4 ? C / 4 : C);
   if (v4)
     hipLaunchKernelGGL(adaptive_avgpool_bwd_kernel<4>, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, gy, gx, H, W, OH, OW, C / 4, total);

@@ -131,7 +131,7 @@ extern "C" int fmi_psp_pixel_head_fwd_f32(const float* y_hat, const float* y, co
   if ((reinterpret_cast<uintptr_t>(sums) & 7) || (reinterpret_cast<uintptr_t>(ws_part) & 7)) return FMI_ERR_BAD_ARG;
   const int64_t hw = (int64_t)H * W;
   bool vec = (hw & 3) == 0;
-  for (const void* q : all) vec = vec && al16(q);
+  for (const void* q : all) vec = vec && fmi_al16(q);
   const int64_t per = vec ? hw >> 2 : hw;
   const int gx = rows_for(per, ROWS_PER_PLANE);
   const bool want_sums = sums || out2;
@@ -157,7 +157,7 @@ extern "C" int fmi_psp_pixel_head_bwd_f32(const float* y_hat, const float* y, co
   const int64_t hw = (int64_t)H * W;
   bool vec = (hw & 3) == 0;
   for (const void* q : all)
-    if (q != g2) vec = vec && al16(q);
+    if (q != g2) vec = vec && fmi_al16(q);
   const int64_t per = vec ? hw >> 2 : hw;
   const dim3 grid(rows_for(per, 1024), N), block(256);
   const double count = 3.0 * (double)N * (double)hw;

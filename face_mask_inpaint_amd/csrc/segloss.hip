@@ -286,7 +286,7 @@ __global__ void __launch_bounds__(256) plane_sums_kernel(const float* __restrict
 extern "C" int fmi_seg_ce_dice_fwd_f32(const float* logits, const void* target, int target_kind, int64_t P, int C, double eps, float* out3,
                                        double* sums, double* ws_part, int64_t ws_doubles, void* stream) {
   if (!logits || !target || !out3 || !sums || !ws_part || P <= 0 || C < 2 || C > 8 || (target_kind != 0 && target_kind != 1)) return FMI_ERR_BAD_ARG;
-  if (!al16(logits) || !al16(target)) return FMI_ERR_BAD_ARG;
+  if (!fmi_al16(logits) || !fmi_al16(target)) return FMI_ERR_BAD_ARG;
   const int rows = rows_for(P >> 2, ROWS_SEG_LOSS);
   if (ws_doubles < (int64_t)rows * (1 + 3 * C)) return FMI_ERR_BAD_ARG;
 #define CALL(CC) hipLaunchKernelGGL(seg_loss_fwd_kernel<CC>, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, target, target_kind, P, ws_part)
@@ -299,7 +299,7 @@ extern "C" int fmi_seg_ce_dice_fwd_f32(const float* logits, const void* target, 
 extern "C" int fmi_seg_ce_dice_bwd_f32(const float* logits, const void* target, int target_kind, int64_t P, int C, double eps, const double* sums,
                                        const float* gout, float* dlogits, void* stream) {
   if (!logits || !target || !sums || !gout || !dlogits || P <= 0 || C < 2 || C > 8 || (target_kind != 0 && target_kind != 1)) return FMI_ERR_BAD_ARG;
-  if (!al16(logits) || !al16(target) || !al16(dlogits)) return FMI_ERR_BAD_ARG;
+  if (!fmi_al16(logits) || !fmi_al16(target) || !fmi_al16(dlogits)) return FMI_ERR_BAD_ARG;
   const int grid = fmi_bw_grid(P >> 2, 256);
 #define CALL(CC) \
   hipLaunchKernelGGL(seg_loss_bwd_kernel<CC>, dim3(grid), dim3(256), 0, (hipStream_t)stream, logits, target, target_kind, P, eps, sums, gout, dlogits)
@@ -312,7 +312,7 @@ extern "C" int fmi_seg_dice_score_f32(const float* logits, const void* target, i
                                       double* ws_part, int64_t ws_doubles, void* stream) {
   if (!logits || !target || !out || !ws_part || N <= 0 || N > 65535 || HW <= 0 || C < 2 || C > 8 || (target_kind != 0 && target_kind != 1))
     return FMI_ERR_BAD_ARG;
-  if (!al16(logits) || !al16(target)) return FMI_ERR_BAD_ARG;
+  if (!fmi_al16(logits) || !fmi_al16(target)) return FMI_ERR_BAD_ARG;
   const bool vec = (HW & 3) == 0;
   const int gx = rows_for(vec ? HW >> 2 : HW, ROWS_PER_PLANE);
   if (ws_doubles < (int64_t)N * gx * 3 * (C - 1)) return FMI_ERR_BAD_ARG;
@@ -331,7 +331,7 @@ extern "C" int fmi_seg_dice_score_f32(const float* logits, const void* target, i
 extern "C" int fmi_plane_sums_f32(const float* a, const float* b, int planes, int64_t n, double* out3, double* ws_part, int64_t ws_doubles,
                                   void* stream) {
   if (!a || !b || !out3 || !ws_part || planes <= 0 || planes > 65535 || n <= 0) return FMI_ERR_BAD_ARG;
-  const bool vec = (n & 3) == 0 && al16(a) && al16(b);
+  const bool vec = (n & 3) == 0 && fmi_al16(a) && fmi_al16(b);
   const int gx = rows_for(vec ? n >> 2 : n, planes == 1 ? ROWS_ONE_PLANE : ROWS_PER_PLANE);
   if (ws_doubles < (int64_t)planes * gx * 3) return FMI_ERR_BAD_ARG;
   if (vec)

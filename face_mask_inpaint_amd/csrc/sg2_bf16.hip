@@ -1,213 +1,15 @@
 // bf16 activations of the StyleGAN2 decoder (configs C3 / C5): the bandwidth kernels around the bf16 convolutions of conv_bf16.hip.
 // Tensors are NHWC bf16 (uint16_t = raw bits); per-sample / per-channel factors, noise maps, biases and every reduction result
-// stay fp32.  One thread moves 8 channels (16 bytes) per access; C % 8 == 0 throughout (scale_channels and its gs also have a scalar form).
-//   scale_channels      x * s[n][c]                       ModulatedConv2d: modulation / demodulation (model.py:244-252)
+// stay fp32.  One thread moves 8 channels (16 bytes) per access; C % 8 == 0 throughout.  The modulation / demodulation product
+// (scale_channels, model.py:244-252) is in chan.hip.
 //   noise_bias_act      lrelu(x + nw*noise + bias) * g    NoiseInjection + FusedLeakyReLU (model.py:282-294, op/fused_act.py:72-85)
 //   upfirdn2d_nhwc      Blur after the up-convolutions    (model.py:52-68, op/upfirdn2d.py:85-147)
 //   torgb               1x1 modulated conv C -> 3 without demodulation + bias + skip (model.py:349-369)
-#include "common.h"
+#include "bf16x8.h"
+#include "sum_parts.h"
 #include <cstdlib>
 
 #ifndef FMI_HOST_EMU
-typedef uint16_t bf16_t;
-__device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ __forceinline__ uint32_t pack_bf(float a, float b) {  // round to nearest even
-  uint32_t ua = __float_as_uint(a), ub = __float_as_uint(b);
-  ua += 0x7fffu + ((ua >> 16) & 1u);
-  ub += 0x7fffu + ((ub >> 16) & 1u);
-  return (ua >> 16) | (ub & 0xffff0000u);
-}
-__device__ __forceinline__ void unpack8(const uint4& v, float (&f)[8]) {
-  f[0] = bf_lo(v.x), f[1] = bf_hi(v.x), f[2] = bf_lo(v.y), f[3] = bf_hi(v.y);
-  f[4] = bf_lo(v.z), f[5] = bf_hi(v.z), f[6] = bf_lo(v.w), f[7] = bf_hi(v.w);
-}
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-  return make_uint4(pack_bf(f[0], f[1]), pack_bf(f[2], f[3]), pack_bf(f[4], f[5]), pack_bf(f[6], f[7]));
-}
-__device__ __forceinline__ void load8f(const float* p, float (&f)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-  f[0] = a.x, f[1] = a.y, f[2] = a.z, f[3] = a.w, f[4] = b.x, f[5] = b.y, f[6] = b.z, f[7] = b.w;
-}
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-typedef __bf16 bf16x2h __attribute__((ext_vector_type(2)));
-typedef float f32x2h __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack_bf_hw(float a, float b) {  // v_cvt_pk_bf16_f32: round to nearest even, one instruction
-  const bf16x2h r = __builtin_convertvector((f32x2h){a, b}, bf16x2h);
-  return *reinterpret_cast<const uint32_t*>(&r);
-}
-__device__ __forceinline__ uint4 pack8_hw(const float (&f)[8]) {
-  return make_uint4(pack_bf_hw(f[0], f[1]), pack_bf_hw(f[2], f[3]), pack_bf_hw(f[4], f[5]), pack_bf_hw(f[6], f[7]));
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// y[n][p][c] = x[n][p][c] * s[n][c]
-__global__ void __launch_bounds__(256) scale_channels_bf16_kernel(const uint4* __restrict__ x, const float* __restrict__ s,
-                                                                  uint4* __restrict__ y, int64_t PC8, int C8, int64_t total) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int c8 = (int)(i % C8);
-    const int64_t n = i / PC8;
-    float f[8], sc[8];
-    unpack8(x[i], f);
-    load8f(s + (n * C8 + c8) * 8, sc);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] *= sc[e];
-    y[i] = pack8(f);
-  }
-}
-// C % 8 != 0: one element per thread.  Not a hot path (every bf16 network here has C % 8 == 0); it exists so that the op is defined for
-// every channel count its fp32 twin takes
-__global__ void __launch_bounds__(256) scale_channels_bf16_scalar_kernel(const bf16_t* __restrict__ x, const float* __restrict__ s,
-                                                                         bf16_t* __restrict__ y, int64_t PC, int C, int64_t total) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int c = (int)(i % C);
-    const int64_t n = i / PC;
-    y[i] = (bf16_t)pack_bf(bf_lo(x[i]) * s[n * C + c], 0.f);
-  }
-}
-extern "C" int fmi_scale_channels_bf16(const uint16_t* x, const float* s, uint16_t* y, int N, int64_t P, int C, void* stream) {
-  if (!x || !s || !y || N <= 0 || P <= 0 || C <= 0) return FMI_ERR_BAD_ARG;
-  if (C % 8 != 0) {
-    const int64_t total = (int64_t)N * P * C;
-    hipLaunchKernelGGL(scale_channels_bf16_scalar_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, x, s, y, P * C, C,
-                       total);
-    return fmi_launch_status();
-  }
-  if (!al16(x) || !al16(y) || !al16(s)) return FMI_ERR_UNSUPPORTED;
-  const int64_t total = (int64_t)N * P * (C / 8);
-  hipLaunchKernelGGL(scale_channels_bf16_kernel, dim3(fmi_bw_grid(total, 256 * 2)), dim3(256), 0, (hipStream_t)stream,
-                     (const uint4*)x, s, (uint4*)y, P * (C / 8), C / 8, total);
-  return fmi_launch_status();
-}
-
-// Shared shape of the per-channel reductions below: 256 threads = (256 / C8) rows x C8 channel chunks per pass; the threads that
-// own one chunk are combined through LDS.  The block's sums are STORED as row `dst` of a partials workspace: thousands of fp32 atomics on a few hundred
-// addresses serialise in L2 (measured: 0.2 ms per launch for 2048 blocks x 128 channels, 4x the streaming time of the pass itself);
-// sum_parts_kernel adds the rows afterwards -- deterministic, and nothing has to be zeroed.
-__device__ __forceinline__ void chunk_reduce_store(float (&acc)[8], float* __restrict__ dst /*[C]*/, int C8, float (*part)[8]) {
-  const int RL = 256 / C8, cg = threadIdx.x % C8;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) part[threadIdx.x][e] = acc[e];
-  __syncthreads();
-  if ((int)threadIdx.x < C8) {
-    float t[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) t[e] = part[threadIdx.x][e];
-    for (int l = 1; l < RL; ++l)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) t[e] += part[l * C8 + cg][e];
-    *reinterpret_cast<float4*>(dst + 8 * cg) = make_float4(t[0], t[1], t[2], t[3]);
-    *reinterpret_cast<float4*>(dst + 8 * cg + 4) = make_float4(t[4], t[5], t[6], t[7]);
-  }
-  __syncthreads();
-}
-// out[g][i] = sum_{p < nparts} ws[(g * nparts + p) * width + i]
-// 64 columns x 16 row lanes per workgroup, eight independent loads in flight per thread, the lanes' sums added in a fixed order (one
-// thread per column walking up to 512 rows with four accumulators was a latency chain: 18 us per launch, 43 launches per C5 step)
-__global__ void __launch_bounds__(1024) sum_parts_kernel(const float* __restrict__ ws, float* __restrict__ out, int nparts, int width) {
-  __shared__ float part[16][64];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + tx;
-  const float* p = ws + (int64_t)blockIdx.y * nparts * width + i;
-  float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (i < width) {
-    int q = ty;
-    for (; q + 7 * 16 < nparts; q += 8 * 16) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) a[u] += p[(int64_t)(q + 16 * u) * width];
-    }
-    for (; q < nparts; q += 16) a[0] += p[(int64_t)q * width];
-  }
-  part[ty][tx] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-  __syncthreads();
-  if (ty == 0 && i < width) {
-    float t = 0.f;
-#pragma unroll
-    for (int l = 0; l < 16; ++l) t += part[l][tx];
-    out[(int64_t)blockIdx.y * width + i] = t;
-  }
-}
-static void launch_sum_parts(const float* ws, float* out, int nparts, int width, int64_t groups, hipStream_t st) {
-  hipLaunchKernelGGL(sum_parts_kernel, dim3((unsigned)((width + 63) / 64), (unsigned)groups), dim3(1024), 0, st, ws, out, nparts, width);
-}
-// how many row blocks a reduction pass uses: enough to fill the chip, at most what the workspace holds (width floats per block)
-static int64_t parts_for(int64_t rows, int64_t groups, int64_t width, int64_t ws_floats) {
-  int64_t b = ceil_div64(rows, 64);
-  const int64_t want = ceil_div64(2048, groups);
-  if (b > want) b = want;
-  const int64_t fit = ws_floats / (groups * width);
-  if (b > fit) b = fit;
-  return b;
-}
-
-// gs[n][c] = sum_p g[n][p][c] * x[n][p][c]   (written, not accumulated; ws: partials workspace of >= N*C floats)
-__global__ void __launch_bounds__(256) scale_channels_gs_bf16_kernel(const uint4* __restrict__ g, const uint4* __restrict__ x,
-                                                                     float* __restrict__ ws, int64_t P, int C8, int64_t rows_per_block) {
-  __shared__ float part[256][8];
-  const int RL = 256 / C8, cg = threadIdx.x % C8, rl = threadIdx.x / C8;
-  const int n = blockIdx.y;
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t r1 = r0 + rows_per_block;
-  if (r1 > P) r1 = P;
-  const uint4* gb = g + (int64_t)n * P * C8;
-  const uint4* xb = x + (int64_t)n * P * C8;
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  int64_t r = r0 + rl;
-  for (; r + RL < r1; r += 2 * RL) {  // two independent pairs of 16-byte loads in flight
-    float a[8], b[8], a2[8], b2[8];
-    const uint4 ga = gb[r * C8 + cg], xa = xb[r * C8 + cg], gc = gb[(r + RL) * C8 + cg], xc = xb[(r + RL) * C8 + cg];
-    unpack8(ga, a), unpack8(xa, b), unpack8(gc, a2), unpack8(xc, b2);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = fmaf(a2[e], b2[e], fmaf(a[e], b[e], acc[e]));
-  }
-  for (; r < r1; r += RL) {
-    float a[8], b[8];
-    unpack8(gb[r * C8 + cg], a);
-    unpack8(xb[r * C8 + cg], b);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = fmaf(a[e], b[e], acc[e]);
-  }
-  chunk_reduce_store(acc, ws + ((int64_t)n * gridDim.x + blockIdx.x) * C8 * 8, C8, part);
-}
-// C % 8 != 0: one workgroup per (64-channel stripe, sample), four row lanes combined in a fixed order; gs WRITTEN, no workspace.  A long
-// walk per thread (P / 4 rows): for the odd widths of small side networks, not for a body layer
-__global__ void __launch_bounds__(256) scale_channels_gs_bf16_scalar_kernel(const bf16_t* __restrict__ g, const bf16_t* __restrict__ x,
-                                                                            float* __restrict__ gs, int64_t P, int C) {
-  __shared__ float part[4][64];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + tx, n = blockIdx.y;
-  float acc = 0.f;
-  if (c < C)
-    for (int64_t r = ty; r < P; r += 4) {
-      const int64_t o = ((int64_t)n * P + r) * C + c;
-      acc = fmaf(bf_lo(g[o]), bf_lo(x[o]), acc);
-    }
-  part[ty][tx] = acc;
-  __syncthreads();
-  if (ty == 0 && c < C) gs[(int64_t)n * C + c] = (part[0][tx] + part[1][tx]) + (part[2][tx] + part[3][tx]);
-}
-static bool c8_ok(int C) {
-  const int c8 = C / 8;
-  return C % 8 == 0 && c8 >= 1 && c8 <= 256 && (c8 & (c8 - 1)) == 0;
-}
-extern "C" int fmi_scale_channels_gs_bf16(const uint16_t* g, const uint16_t* x, float* gs, float* ws, int64_t ws_floats, int N, int64_t P,
-                                          int C, void* stream) {
-  if (!g || !x || !gs || N <= 0 || P <= 0 || C <= 0 || N > 65535) return FMI_ERR_BAD_ARG;
-  if (C % 8 != 0) {  // no eight-channel chunks: the scalar form, which takes no workspace (ws may be NULL)
-    hipLaunchKernelGGL(scale_channels_gs_bf16_scalar_kernel, dim3((unsigned)((C + 63) / 64), N), dim3(256), 0, (hipStream_t)stream, g, x, gs, P, C);
-    return fmi_launch_status();
-  }
-  if (!ws || ws_floats < (int64_t)N * C) return FMI_ERR_BAD_ARG;
-  if (!c8_ok(C) || !al16(g) || !al16(x) || !al16(ws)) return FMI_ERR_UNSUPPORTED;
-  int64_t blocks = parts_for(P, N, C, ws_floats);
-  const int64_t rpb = ceil_div64(P, blocks);
-  blocks = ceil_div64(P, rpb);
-  hipLaunchKernelGGL(scale_channels_gs_bf16_kernel, dim3((unsigned)blocks, N), dim3(256), 0, (hipStream_t)stream, (const uint4*)g,
-                     (const uint4*)x, ws, P, C / 8, rpb);
-  launch_sum_parts(ws, gs, (int)blocks, C, N, (hipStream_t)stream);
-  return fmi_launch_status();
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // y = lrelu(x + bias[c] + nw * noise[p], alpha) * scale
 __global__ void __launch_bounds__(256) noise_bias_act_bf16_kernel(const uint4* __restrict__ x, const float* __restrict__ bias,
@@ -218,21 +20,21 @@ __global__ void __launch_bounds__(256) noise_bias_act_bf16_kernel(const uint4* _
     const int64_t p = i / C8;
     const int c8 = (int)(i - p * C8);
     float f[8], b[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    unpack8(x[i], f);
-    if (bias) load8f(bias + 8 * c8, b);
+    bf_unpack8(x[i], f);
+    if (bias) bf_load8f(bias + 8 * c8, b);
     const float nz = (noise && nw) ? w * noise[p] : 0.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const float v = f[e] + b[e] + nz;
       f[e] = (v > 0.f ? v : v * alpha) * scale;
     }
-    y[i] = pack8(f);
+    y[i] = bf_pack8(f);
   }
 }
 extern "C" int fmi_noise_bias_act_bf16(const uint16_t* x, const float* bias, const float* noise, const float* nw, uint16_t* y,
                                        int64_t pixels, int C, float alpha, float scale, void* stream) {
   if (!x || !y || pixels <= 0 || C <= 0) return FMI_ERR_BAD_ARG;
-  if (C % 8 != 0 || !al16(x) || !al16(y) || !al16(bias)) return FMI_ERR_UNSUPPORTED;
+  if (C % 8 != 0 || !fmi_al16(x) || !fmi_al16(y) || !fmi_al16(bias)) return FMI_ERR_UNSUPPORTED;
   const int64_t total = pixels * (C / 8);
   hipLaunchKernelGGL(noise_bias_act_bf16_kernel, dim3(fmi_bw_grid(total, 256 * 2)), dim3(256), 0, (hipStream_t)stream, (const uint4*)x,
                      bias, noise, nw, (uint4*)y, total, C / 8, alpha, scale);
@@ -255,8 +57,8 @@ __global__ void __launch_bounds__(256) noise_bias_act_bwd_bf16_kernel(const uint
   float an = 0.f;
   auto one = [&](int64_t r, const uint4& gv, const uint4& yv) {
     float a[8], b[8];
-    unpack8(gv, a);
-    unpack8(yv, b);
+    bf_unpack8(gv, a);
+    bf_unpack8(yv, b);
     float rs = 0.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -265,7 +67,7 @@ __global__ void __launch_bounds__(256) noise_bias_act_bwd_bf16_kernel(const uint
       rs += a[e];
     }
     if (noise) an = fmaf(rs, noise[r], an);
-    gx[r * C8 + cg] = pack8(a);
+    gx[r * C8 + cg] = bf_pack8(a);
   };
   int64_t r = r0 + rl;
   for (; r + RL < r1; r += 2 * RL) {  // two independent pairs of 16-byte loads in flight
@@ -314,7 +116,7 @@ extern "C" int fmi_noise_bias_act_bwd_bf16(const uint16_t* g, const uint16_t* y,
                                            float* gbias, float* ws, int64_t ws_floats, int64_t pixels, int C, float alpha, float scale,
                                            void* stream) {
   if (!g || !y || !gx || !ws || pixels <= 0 || C <= 0 || ws_floats < C + 8) return FMI_ERR_BAD_ARG;
-  if (!c8_ok(C) || !al16(g) || !al16(y) || !al16(gx) || !al16(ws)) return FMI_ERR_UNSUPPORTED;
+  if (!c8_ok(C) || !fmi_al16(g) || !fmi_al16(y) || !fmi_al16(gx) || !fmi_al16(ws)) return FMI_ERR_UNSUPPORTED;
   int64_t blocks = parts_for(pixels, 1, C + 8, ws_floats);
   const int64_t rpb = ceil_div64(pixels, blocks);
   blocks = ceil_div64(pixels, rpb);
@@ -353,14 +155,14 @@ __global__ void __launch_bounds__(256) styled_out_bwd_bf16_kernel(const uint4* _
   float d[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) d[e] = 1.f;
-  if (colscale) load8f(colscale + ((int64_t)n * C8 + cg) * 8, d);
+  if (colscale) bf_load8f(colscale + ((int64_t)n * C8 + cg) * 8, d);
   float sa[8], sb[8], sc[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) sa[e] = 0.f, sb[e] = 0.f, sc[e] = 0.f;
   auto one = [&](int64_t r, const uint4& gv, const uint4& yv) {
     float a[8], b[8];
-    unpack8(gv, a);
-    unpack8(yv, b);
+    bf_unpack8(gv, a);
+    bf_unpack8(yv, b);
     const float nz = nb ? nb[r] : 0.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -370,7 +172,7 @@ __global__ void __launch_bounds__(256) styled_out_bwd_bf16_kernel(const uint4* _
       sc[e] += gp;
       a[e] = gp * d[e];
     }
-    tb[r * C8 + cg] = pack8_hw(a);
+    tb[r * C8 + cg] = bf_pack8_hw(a);
   };
   int64_t r = r0 + rl;
   for (; r + RL < r1; r += 2 * RL) {  // two independent pairs of 16-byte loads in flight
@@ -413,7 +215,7 @@ extern "C" int fmi_styled_out_bwd_bf16(const uint16_t* g, const uint16_t* y, con
                                        const float* bias, uint16_t* t, float* gd, float* gbias, float* gnw, float* ws, int64_t ws_floats,
                                        float* sums, int N, int64_t P, int C, float slope, float gain, void* stream) {
   if (!g || !y || !t || !ws || !sums || N <= 0 || P <= 0 || C <= 0 || (noise && !nw)) return FMI_ERR_BAD_ARG;
-  if (!c8_ok(C) || !al16(g) || !al16(y) || !al16(t) || !al16(ws) || (colscale && !al16(colscale))) return FMI_ERR_UNSUPPORTED;
+  if (!c8_ok(C) || !fmi_al16(g) || !fmi_al16(y) || !fmi_al16(t) || !fmi_al16(ws) || (colscale && !fmi_al16(colscale))) return FMI_ERR_UNSUPPORTED;
   if (ws_floats < (int64_t)N * 3 * C) return FMI_ERR_BAD_ARG;
   int64_t blocks = parts_for(P, N, 3 * (int64_t)C, ws_floats);
   const int64_t rpb = ceil_div64(P, blocks);
@@ -463,7 +265,7 @@ __global__ void __launch_bounds__(256) upfirdn2d_nhwc_fir_bf16_kernel(const uint
         const int ix = ix0 + b;
         if ((unsigned)ix >= (unsigned)in_w) continue;
         float v[8];
-        unpack8(row[(int64_t)ix * C8], v);
+        bf_unpack8(row[(int64_t)ix * C8], v);
         if (b < KW) {
           const float k0 = kf[a][b];
 #pragma unroll
@@ -477,8 +279,8 @@ __global__ void __launch_bounds__(256) upfirdn2d_nhwc_fir_bf16_kernel(const uint
       }
     }
     uint4* o = out + ((int64_t)(n * out_h + oy) * out_w + ox) * C8 + c8;
-    o[0] = pack8(a0);
-    if (ox + 1 < out_w) o[C8] = pack8(a1);
+    o[0] = bf_pack8(a0);
+    if (ox + 1 < out_w) o[C8] = bf_pack8(a1);
   }
 }
 // Column-run form of the same FIR, bf16 (E = 8 channels per 16 bytes) and fp32 (E = 4): one thread = (2 adjacent output columns,
@@ -522,7 +324,7 @@ __global__ void __launch_bounds__(256) upfirdn2d_nhwc_fir_run_kernel(const uint4
         uint4 raw = make_uint4(0u, 0u, 0u, 0u);
         if ((unsigned)ix < (unsigned)in_w) raw = row[(int64_t)ix * CV];
         if constexpr (BF) {
-          unpack8(raw, v[b]);
+          bf_unpack8(raw, v[b]);
         } else {
           v[b][0] = __uint_as_float(raw.x), v[b][1] = __uint_as_float(raw.y), v[b][2] = __uint_as_float(raw.z), v[b][3] = __uint_as_float(raw.w);
         }
@@ -548,8 +350,8 @@ __global__ void __launch_bounds__(256) upfirdn2d_nhwc_fir_run_kernel(const uint4
       if (oy >= out_h) break;
       uint4* o = out + ((int64_t)(n * out_h + oy) * out_w + ox) * CV + cv;
       if constexpr (BF) {
-        o[0] = pack8(acc[q][0]);
-        if (ox + 1 < out_w) o[CV] = pack8(acc[q][1]);
+        o[0] = bf_pack8(acc[q][0]);
+        if (ox + 1 < out_w) o[CV] = bf_pack8(acc[q][1]);
       } else {
         o[0] = make_uint4(__float_as_uint(acc[q][0][0]), __float_as_uint(acc[q][0][1]), __float_as_uint(acc[q][0][2]), __float_as_uint(acc[q][0][3]));
         if (ox + 1 < out_w)
@@ -677,7 +479,7 @@ __global__ void __launch_bounds__(256) blur4_lds_bf16_kernel(BlurActArgs a) {
 #pragma unroll
     for (int bb = 0; bb < 5; ++bb) {
       float v[8];
-      unpack8(row[slot[bb]], v);
+      bf_unpack8(row[slot[bb]], v);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         if (bb < 4) h0[e] = bb == 0 ? v[e] * kx[0] : fmaf(v[e], kx[bb], h0[e]);
@@ -706,8 +508,8 @@ __global__ void __launch_bounds__(256) blur4_lds_bf16_kernel(BlurActArgs a) {
   if (ACT) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) d[e] = 1.f, bs[e] = 0.f;
-    if (a.colscale) load8f(a.colscale + (int64_t)n * a.CV * 8 + c, d);
-    if (a.bias) load8f(a.bias + c, bs);
+    if (a.colscale) bf_load8f(a.colscale + (int64_t)n * a.CV * 8 + c, d);
+    if (a.bias) bf_load8f(a.bias + c, bs);
   }
   const float nwv = (ACT && a.noise) ? a.nw[0] : 0.f;
 #pragma unroll
@@ -726,8 +528,8 @@ __global__ void __launch_bounds__(256) blur4_lds_bf16_kernel(BlurActArgs a) {
       }
     }
     uint4* o = a.out + pix * a.CV + cv0 + cv;
-    o[0] = pack8_hw(acc[q][0]);
-    if (two) o[a.CV] = pack8_hw(acc[q][1]);
+    o[0] = bf_pack8_hw(acc[q][0]);
+    if (two) o[a.CV] = bf_pack8_hw(acc[q][1]);
   }
 }
 extern "C" int fmi_upfirdn2d_nhwc_bf16(const uint16_t* in, const float* kernel, uint16_t* out, int N, int in_h, int in_w, int C, int kh,
@@ -762,7 +564,7 @@ extern "C" int fmi_blur_act_bf16(const uint16_t* in, const float* kernel, uint16
   if (!in || !kernel || !out || N <= 0 || in_h <= 0 || in_w <= 0 || C <= 0 || (noise && !nw)) return FMI_ERR_BAD_ARG;
   const int out_h = in_h + pad_y0 + pad_y1 - 3, out_w = in_w + pad_x0 + pad_x1 - 3;
   if (out_h <= 0 || out_w <= 0) return FMI_ERR_BAD_ARG;
-  if (C % 32 != 0 || !al16(in) || !al16(out) || (colscale && !al16(colscale)) || (bias && !al16(bias))) return FMI_ERR_UNSUPPORTED;
+  if (C % 32 != 0 || !fmi_al16(in) || !fmi_al16(out) || (colscale && !fmi_al16(colscale)) || (bias && !fmi_al16(bias))) return FMI_ERR_UNSUPPORTED;
   BlurActArgs a{};
   a.in = (const uint4*)in; a.out = (uint4*)out; a.kernel = kernel;
   a.colscale = colscale; a.noise = noise; a.nw = nw; a.bias = bias; a.slope = slope; a.gain = gain; a.act = (colscale || noise || bias || slope != 1.f || gain != 1.f) ? 1 : 0;
@@ -778,7 +580,7 @@ extern "C" int fmi_upfirdn2d_nhwc_bf16(const uint16_t* in, const float* kernel, 
                                        int kw, int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
                                        void* stream) {
   if (!in || !kernel || !out || N <= 0 || in_h <= 0 || in_w <= 0 || C <= 0 || kh <= 0 || kw <= 0) return FMI_ERR_BAD_ARG;
-  if (up_x != 1 || up_y != 1 || down_x != 1 || down_y != 1 || kh != kw || kh < 2 || kh > 4 || C % 8 != 0 || !al16(in) || !al16(out))
+  if (up_x != 1 || up_y != 1 || down_x != 1 || down_y != 1 || kh != kw || kh < 2 || kh > 4 || C % 8 != 0 || !fmi_al16(in) || !fmi_al16(out))
     return FMI_ERR_UNSUPPORTED;  // the bf16 decoder only blurs; resampling stays on the fp32 entry
   const int fh = in_h + pad_y0 + pad_y1 - kh, fw = in_w + pad_x0 + pad_x1 - kw;
   if (fh < 0 || fw < 0) return FMI_ERR_BAD_ARG;
@@ -809,10 +611,10 @@ __global__ void __launch_bounds__(256) torgb_fwd_bf16_kernel(const uint4* __rest
   float wm[3][8];
   {
     float sc[8];
-    load8f(s + (int64_t)n * C + 8 * cg, sc);
+    bf_load8f(s + (int64_t)n * C + 8 * cg, sc);
 #pragma unroll
     for (int o = 0; o < 3; ++o) {
-      load8f(w + o * C + 8 * cg, wm[o]);
+      bf_load8f(w + o * C + 8 * cg, wm[o]);
 #pragma unroll
       for (int e = 0; e < 8; ++e) wm[o][e] *= sc[e];
     }
@@ -826,7 +628,7 @@ __global__ void __launch_bounds__(256) torgb_fwd_bf16_kernel(const uint4* __rest
     float d[3] = {0.f, 0.f, 0.f};
     if (r < r1) {
       float v[8];
-      unpack8(xb[r * C8 + cg], v);
+      bf_unpack8(xb[r * C8 + cg], v);
 #pragma unroll
       for (int o = 0; o < 3; ++o)
 #pragma unroll
@@ -855,10 +657,10 @@ __global__ void __launch_bounds__(256) torgb_bwd_bf16_kernel(const uint4* __rest
   float wm[3][8];
   {
     float sc[8];
-    load8f(s + (int64_t)n * C + 8 * cg, sc);
+    bf_load8f(s + (int64_t)n * C + 8 * cg, sc);
 #pragma unroll
     for (int o = 0; o < 3; ++o) {
-      load8f(w + o * C + 8 * cg, wm[o]);
+      bf_load8f(w + o * C + 8 * cg, wm[o]);
 #pragma unroll
       for (int e = 0; e < 8; ++e) wm[o][e] *= sc[e];
     }
@@ -878,7 +680,7 @@ __global__ void __launch_bounds__(256) torgb_bwd_bf16_kernel(const uint4* __rest
     const int64_t q = ((int64_t)n * P + r) * 3;
     const float g0 = g[q], g1 = g[q + 1], g2 = g[q + 2];
     float v[8], o8[8];
-    unpack8(xb[r * C8 + cg], v);
+    bf_unpack8(xb[r * C8 + cg], v);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       o8[e] = g0 * wm[0][e] + g1 * wm[1][e] + g2 * wm[2][e];
@@ -886,7 +688,7 @@ __global__ void __launch_bounds__(256) torgb_bwd_bf16_kernel(const uint4* __rest
       acc[1][e] = fmaf(g1, v[e], acc[1][e]);
       acc[2][e] = fmaf(g2, v[e], acc[2][e]);
     }
-    gxb[r * C8 + cg] = pack8(o8);
+    gxb[r * C8 + cg] = bf_pack8(o8);
     if (cg == 0) gb[0] += g0, gb[1] += g1, gb[2] += g2;
   }
   float* row = ws + ((int64_t)n * gridDim.x + blockIdx.x) * (3 * C + 8);
@@ -931,7 +733,7 @@ static bool torgb_ok(int C) {
 extern "C" int fmi_torgb_fwd_bf16(const uint16_t* x, const float* w, const float* s, const float* bias, const float* skip, float* out,
                                   int N, int64_t P, int C, void* stream) {
   if (!x || !w || !s || !out || N <= 0 || P <= 0 || C <= 0 || N > 65535) return FMI_ERR_BAD_ARG;
-  if (!torgb_ok(C) || !al16(x) || !al16(w) || !al16(s)) return FMI_ERR_UNSUPPORTED;
+  if (!torgb_ok(C) || !fmi_al16(x) || !fmi_al16(w) || !fmi_al16(s)) return FMI_ERR_UNSUPPORTED;
   const int RL = 256 / (C / 8);
   int64_t blocks = ceil_div64(P, 64);
   if (blocks > 512) blocks = 512;
@@ -948,7 +750,7 @@ extern "C" int fmi_torgb_bwd_bf16(const uint16_t* x, const float* w, const float
   if (!x || !w || !s || !g || !gx || !ws || !gw || !gs || N <= 0 || P <= 0 || C <= 0 || N > 65535) return FMI_ERR_BAD_ARG;
   const int64_t W = 3 * (int64_t)C + 8;
   if (ws_floats < 2 * N * W) return FMI_ERR_BAD_ARG;
-  if (!torgb_ok(C) || !al16(x) || !al16(gx) || !al16(w) || !al16(s) || !al16(ws)) return FMI_ERR_UNSUPPORTED;
+  if (!torgb_ok(C) || !fmi_al16(x) || !fmi_al16(gx) || !fmi_al16(w) || !fmi_al16(s) || !fmi_al16(ws)) return FMI_ERR_UNSUPPORTED;
   float* gwm = ws;                 // [N][W] per-sample sums
   float* parts = ws + N * W;       // [N][blocks][W]
   int64_t blocks = parts_for(P, N, W, ws_floats - N * W);

@@ -14,7 +14,7 @@
 //             shuffles, over the workgroup's waves through LDS, over workgroups by fp32 atomics; dbias rides along.
 //   backward: when BOTH gradients of the fused block (LeakyReLU in front, tanh behind) are wanted they come out of one x-stationary pass
 //             (thin_lrelu_bwd_kernel further down): x read once, dx written once, no atomics.
-#include "common.h"
+#include "bf16x8.h"
 #include <cstdlib>
 
 namespace {
@@ -394,10 +394,10 @@ __global__ void __launch_bounds__(256) thin_fwd_lds_kernel(ThinArgs a, int tiles
       for (int j = 0; j < NLDB; ++j) {
         const int p = (tid >> 2) + 64 * j;
         const thin_u32x4 u = stageb[j];
-        const float4 lo = lrelu4(make_float4(__uint_as_float(u[0] << 16), __uint_as_float(u[0] & 0xFFFF0000u), __uint_as_float(u[1] << 16),
-                                             __uint_as_float(u[1] & 0xFFFF0000u)), a.in_slope);
-        const float4 hi = lrelu4(make_float4(__uint_as_float(u[2] << 16), __uint_as_float(u[2] & 0xFFFF0000u), __uint_as_float(u[3] << 16),
-                                             __uint_as_float(u[3] & 0xFFFF0000u)), a.in_slope);
+        const float4 lo = lrelu4(make_float4(bf_lo(u[0]), bf_hi(u[0]), bf_lo(u[1]),
+                                             bf_hi(u[1])), a.in_slope);
+        const float4 hi = lrelu4(make_float4(bf_lo(u[2]), bf_hi(u[2]), bf_lo(u[3]),
+                                             bf_hi(u[3])), a.in_slope);
         if (p < NPIX) {
           *reinterpret_cast<float4*>(sx + p * LT_PITCH + 8 * (tid & 3)) = lo;
           *reinterpret_cast<float4*>(sx + p * LT_PITCH + 8 * (tid & 3) + 4) = hi;

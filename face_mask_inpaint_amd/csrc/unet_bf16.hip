@@ -3,29 +3,9 @@
 // NHWC bf16 tensors (uint16_t = raw bits), C % 8 == 0: one thread moves 8 channels (16 bytes), fp32 arithmetic, round-to-nearest-even
 // stores.  Parameters, logits and every reduction result stay fp32.  No atomics anywhere: both modes of fmi_set_deterministic run the
 // same code.
-#include "common.h"
+#include "bf16x8.h"
 #include "head.h"
 
-__device__ __forceinline__ float u_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float u_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ __forceinline__ uint32_t u_pack(float a, float b) {  // round to nearest even
-  uint32_t ua = __float_as_uint(a), ub = __float_as_uint(b);
-  ua += 0x7fffu + ((ua >> 16) & 1u);
-  ub += 0x7fffu + ((ub >> 16) & 1u);
-  return (ua >> 16) | (ub & 0xffff0000u);
-}
-__device__ __forceinline__ void u_unpack8(const uint4& v, float (&f)[8]) {
-  f[0] = u_lo(v.x), f[1] = u_hi(v.x), f[2] = u_lo(v.y), f[3] = u_hi(v.y);
-  f[4] = u_lo(v.z), f[5] = u_hi(v.z), f[6] = u_lo(v.w), f[7] = u_hi(v.w);
-}
-__device__ __forceinline__ uint4 u_pack8(const float (&f)[8]) {
-  return make_uint4(u_pack(f[0], f[1]), u_pack(f[2], f[3]), u_pack(f[4], f[5]), u_pack(f[6], f[7]));
-}
-// bit patterns of two bf16 values that are already exact (a maximum, a routed gradient): no rounding step
-__device__ __forceinline__ uint32_t u_bits2(float a, float b) { return (__float_as_uint(a) >> 16) | (__float_as_uint(b) & 0xffff0000u); }
-__device__ __forceinline__ uint4 u_bits8(const float (&f)[8]) {
-  return make_uint4(u_bits2(f[0], f[1]), u_bits2(f[2], f[3]), u_bits2(f[4], f[5]), u_bits2(f[6], f[7]));
-}
 
 // ---- 2 x 2 stride-2 max pooling, H and W even; the FIRST maximum of the window in row-major order wins and a later NaN replaces the
 // running maximum (ATen's rule, pool.hip's maxpool_kernel): a NaN reaches the output and takes the gradient ----
@@ -41,10 +21,10 @@ __global__ void __launch_bounds__(256) maxpool2_bf16_kernel(const uint4* __restr
     const int64_t n = r / OH;
     const uint4* p = x + ((n * H + oy * 2) * W + ox * 2) * C8 + c;
     float v0[8], v1[8], v2[8], v3[8], m[8];
-    u_unpack8(p[0], v0);
-    u_unpack8(p[C8], v1);
-    u_unpack8(p[(int64_t)W * C8], v2);
-    u_unpack8(p[(int64_t)W * C8 + C8], v3);
+    bf_unpack8(p[0], v0);
+    bf_unpack8(p[C8], v1);
+    bf_unpack8(p[(int64_t)W * C8], v2);
+    bf_unpack8(p[(int64_t)W * C8 + C8], v3);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       float t = v0[e];
@@ -53,7 +33,7 @@ __global__ void __launch_bounds__(256) maxpool2_bf16_kernel(const uint4* __restr
       if (u_takes(v3[e], t)) t = v3[e];
       m[e] = t;
     }
-    y[i] = u_bits8(m);
+    y[i] = bf_trunc8(m);
   }
 }
 // one thread per WINDOW: x and gy are read once, the four gx pixels of the window are written (the loser pixels as zeros)
@@ -69,11 +49,11 @@ __global__ void __launch_bounds__(256) maxpool2_bwd_bf16_kernel(const uint4* __r
     const int64_t n = r / OH;
     const int64_t o = ((n * H + oy * 2) * W + ox * 2) * C8 + c;
     float v0[8], v1[8], v2[8], v3[8], g[8], q[4][8];
-    u_unpack8(x[o], v0);
-    u_unpack8(x[o + C8], v1);
-    u_unpack8(x[o + (int64_t)W * C8], v2);
-    u_unpack8(x[o + (int64_t)W * C8 + C8], v3);
-    u_unpack8(gy[i], g);
+    bf_unpack8(x[o], v0);
+    bf_unpack8(x[o + C8], v1);
+    bf_unpack8(x[o + (int64_t)W * C8], v2);
+    bf_unpack8(x[o + (int64_t)W * C8 + C8], v3);
+    bf_unpack8(gy[i], g);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       int arg = 0;
@@ -84,15 +64,15 @@ __global__ void __launch_bounds__(256) maxpool2_bwd_bf16_kernel(const uint4* __r
 #pragma unroll
       for (int a = 0; a < 4; ++a) q[a][e] = arg == a ? g[e] : 0.f;
     }
-    gx[o] = u_bits8(q[0]);
-    gx[o + C8] = u_bits8(q[1]);
-    gx[o + (int64_t)W * C8] = u_bits8(q[2]);
-    gx[o + (int64_t)W * C8 + C8] = u_bits8(q[3]);
+    gx[o] = bf_trunc8(q[0]);
+    gx[o + C8] = bf_trunc8(q[1]);
+    gx[o + (int64_t)W * C8] = bf_trunc8(q[2]);
+    gx[o + (int64_t)W * C8 + C8] = bf_trunc8(q[3]);
   }
 }
 static int pool_args(const void* a, const void* b, const void* c, int N, int H, int W, int C) {
   if (!a || !b || !c || N <= 0 || H <= 0 || W <= 0 || C <= 0) return FMI_ERR_BAD_ARG;
-  if (C % 8 != 0 || (H & 1) || (W & 1) || !al16(a) || !al16(b) || !al16(c)) return FMI_ERR_UNSUPPORTED;
+  if (C % 8 != 0 || (H & 1) || (W & 1) || !fmi_al16(a) || !fmi_al16(b) || !fmi_al16(c)) return FMI_ERR_UNSUPPORTED;
   return FMI_OK;
 }
 extern "C" int fmi_maxpool2_bf16(const uint16_t* x, uint16_t* y, int N, int H, int W, int C, void* stream) {
@@ -151,13 +131,13 @@ __global__ void __launch_bounds__(256) up2_cat_bf16_kernel(const uint4* __restri
       const int y1 = ly.i0 + (ly.i0 < h - 1 ? 1 : 0), x1i = lx.i0 + (lx.i0 < w - 1 ? 1 : 0);
       const uint4* b = x1 + n * h * w * C1_8 + (c - C2_8);
       float v00[8], v01[8], v10[8], v11[8], o[8];
-      u_unpack8(b[((int64_t)ly.i0 * w + lx.i0) * C1_8], v00);
-      u_unpack8(b[((int64_t)ly.i0 * w + x1i) * C1_8], v01);
-      u_unpack8(b[((int64_t)y1 * w + lx.i0) * C1_8], v10);
-      u_unpack8(b[((int64_t)y1 * w + x1i) * C1_8], v11);
+      bf_unpack8(b[((int64_t)ly.i0 * w + lx.i0) * C1_8], v00);
+      bf_unpack8(b[((int64_t)ly.i0 * w + x1i) * C1_8], v01);
+      bf_unpack8(b[((int64_t)y1 * w + lx.i0) * C1_8], v10);
+      bf_unpack8(b[((int64_t)y1 * w + x1i) * C1_8], v11);
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] = ly.l0 * (lx.l0 * v00[e] + lx.l1 * v01[e]) + ly.l1 * (lx.l0 * v10[e] + lx.l1 * v11[e]);
-      out = u_pack8(o);
+      out = bf_pack8(o);
     }
     y[i] = out;
   }
@@ -207,20 +187,20 @@ __global__ void __launch_bounds__(256) up2_cat_bwd_bf16_kernel(const uint4* __re
         const float wx = lx.i0 == ix ? lx.l0 : (lx.i0 + 1 == ix ? lx.l1 : 0.f);
         if (wx == 0.f) continue;
         float gv[8];
-        u_unpack8(row[(int64_t)ox * CT], gv);
+        bf_unpack8(row[(int64_t)ox * CT], gv);
 #pragma unroll
         for (int e = 0; e < 8; ++e) t[e] = fmaf(wx, gv[e], t[e]);
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) s[e] = fmaf(wy, t[e], s[e]);
     }
-    gx1[j] = u_pack8(s);
+    gx1[j] = bf_pack8(s);
   }
 }
 static int up2_args(const void* a, const void* b, const void* c, int N, int h, int w, int C1, int H, int W, int C2) {
   if (!a || !b || !c || N <= 0 || h <= 0 || w <= 0 || C1 <= 0 || H <= 0 || W <= 0 || C2 <= 0) return FMI_ERR_BAD_ARG;
   if (H < 2 * h || W < 2 * w) return FMI_ERR_BAD_ARG;  // the border is never negative (unet_parts.py pads up to the skip's size)
-  if (C1 % 8 != 0 || C2 % 8 != 0 || !al16(a) || !al16(b) || !al16(c)) return FMI_ERR_UNSUPPORTED;
+  if (C1 % 8 != 0 || C2 % 8 != 0 || !fmi_al16(a) || !fmi_al16(b) || !fmi_al16(c)) return FMI_ERR_UNSUPPORTED;
   if (h > 16384 || w > 16384) return FMI_ERR_UNSUPPORTED;  // o (in - 1) stays an int
   return FMI_OK;
 }
@@ -252,7 +232,7 @@ __device__ __forceinline__ void head_logits(const uint4* __restrict__ x, const f
   for (int k = 0; k < K; ++k) acc[k] = 0.f;
   for (int c = sub; c < C8; c += 8) {
     float f[8];
-    u_unpack8(x[p * C8 + c], f);
+    bf_unpack8(x[p * C8 + c], f);
 #pragma unroll
     for (int k = 0; k < K; ++k)
 #pragma unroll
@@ -296,7 +276,7 @@ __global__ void __launch_bounds__(256) head1x1_bf16_kernel(const uint4* __restri
 }
 static int head_args(const void* x, const void* w, const void* b, const void* y, int64_t P, int C, int K) {
   if (!x || !w || !b || !y || P <= 0 || C <= 0 || K <= 0) return FMI_ERR_BAD_ARG;
-  if (C % 8 != 0 || C > HEAD_CMAX || K > HEAD_KMAX || !al16(x) || !al4(w) || !al4(b) || !al4(y)) return FMI_ERR_UNSUPPORTED;
+  if (C % 8 != 0 || C > HEAD_CMAX || K > HEAD_KMAX || !fmi_al16(x) || !al4(w) || !al4(b) || !al4(y)) return FMI_ERR_UNSUPPORTED;
   return FMI_OK;
 }
 template <bool ARGMAX>
@@ -344,7 +324,7 @@ __global__ void __launch_bounds__(256) head1x1_bwd_bf16_kernel(const float* __re
   if (rl < RL) {
     for (int64_t r = r0 + rl; r < r1; r += RL) {
       float xv[8], o[8], gk[K];
-      u_unpack8(x[r * C8 + cg], xv);
+      bf_unpack8(x[r * C8 + cg], xv);
 #pragma unroll
       for (int k = 0; k < K; ++k) gk[k] = g[r * K + k];
 #pragma unroll
@@ -358,7 +338,7 @@ __global__ void __launch_bounds__(256) head1x1_bwd_bf16_kernel(const float* __re
           aw[k][e] = fmaf(gk[k], xv[e], aw[k][e]);
         }
       }
-      gx[r * C8 + cg] = u_pack8(o);
+      gx[r * C8 + cg] = bf_pack8(o);
     }
   }
 #pragma unroll
@@ -384,7 +364,7 @@ __global__ void __launch_bounds__(256) head1x1_bwd_bf16_kernel(const float* __re
 extern "C" int fmi_head1x1_bwd_bf16(const float* g, const uint16_t* x, const float* w, uint16_t* gx, float* gw, float* gb, double* ws,
                                     int64_t ws_doubles, int64_t P, int C, int K, void* stream) {
   if (!g || !x || !w || !gx || !gw || !gb || !ws || P <= 0 || C <= 0 || K <= 0) return FMI_ERR_BAD_ARG;
-  if (C % 8 != 0 || C > HEAD_CMAX || K > HEAD_KMAX || !al16(x) || !al16(gx) || !al4(g) || !al4(w) || !al4(gw) || !al4(gb) ||
+  if (C % 8 != 0 || C > HEAD_CMAX || K > HEAD_KMAX || !fmi_al16(x) || !fmi_al16(gx) || !al4(g) || !al4(w) || !al4(gw) || !al4(gb) ||
       (reinterpret_cast<uintptr_t>(ws) & 7))
     return FMI_ERR_UNSUPPORTED;
   const int C8 = C / 8, nv = K * C + K;

@@ -9,7 +9,7 @@
 //    up-sampled coordinate lands on a real sample (poly-phase form);
 //  * any up / down / kernel size is accepted (the reference's CUDA kernel returns uninitialised memory
 //    outside six hard-coded modes, op/upfirdn2d_kernel.cu:172-268).
-#include "common.h"
+#include "bf16x8.h"
 #include <cstdlib>
 
 #define UF_TH 16
@@ -21,16 +21,8 @@ __device__ __forceinline__ int floordiv(int a, int b) {
   return q;
 }
 
-// element types: fp32, or bf16 stored as uint16_t (arithmetic is fp32 either way, results rounded to nearest even)
-__device__ __forceinline__ float uf_ld(const float* p, int64_t i) { return p[i]; }
-__device__ __forceinline__ float uf_ld(const uint16_t* p, int64_t i) { return __uint_as_float((uint32_t)p[i] << 16); }
-__device__ __forceinline__ void uf_st(float* p, int64_t i, float v) { p[i] = v; }
-__device__ __forceinline__ void uf_st(uint16_t* p, int64_t i, float v) {
-  uint32_t u = __float_as_uint(v);
-  if ((u & 0x7fffffffu) > 0x7f800000u) u |= 0x00400000u;      // quiet NaN keeps its payload bit
-  else u += 0x7fffu + ((u >> 16) & 1u);                        // round to nearest even
-  p[i] = (uint16_t)(u >> 16);
-}
+// element types: fp32, or bf16 stored as uint16_t (arithmetic is fp32 either way).  The input is a caller's tensor and may hold NaNs or
+// infinities: the bf16 stores use bf_st_nan (a NaN stays a quiet NaN instead of rounding into an infinity)
 
 struct UfParams {
   int major, in_h, in_w, out_h, out_w, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_y0;
@@ -55,14 +47,14 @@ __global__ void __launch_bounds__(256) upfirdn2d_kernel(const T* __restrict__ in
   const int ix0 = floordiv(ox0 * p.down_x - p.pad_x0, p.up_x);
   for (int t = tid; t < p.kh * p.kw; t += 256) {
     const int ky = t / p.kw, kx = t - ky * p.kw;
-    sk[t] = uf_ld(kernel, (p.kh - 1 - ky) * p.kw + (p.kw - 1 - kx));
+    sk[t] = bf_ld(kernel, (p.kh - 1 - ky) * p.kw + (p.kw - 1 - kx));
   }
   const T* ip = in + (int64_t)plane * p.in_h * p.in_w;
   for (int t = tid; t < p.tile_in_h * p.tile_in_w; t += 256) {
     const int ry = t / p.tile_in_w, rx = t - ry * p.tile_in_w;
     const int iy = iy0 + ry, ix = ix0 + rx;
     float v = 0.f;
-    if ((unsigned)iy < (unsigned)p.in_h && (unsigned)ix < (unsigned)p.in_w) v = uf_ld(ip, (int64_t)iy * p.in_w + ix);
+    if ((unsigned)iy < (unsigned)p.in_h && (unsigned)ix < (unsigned)p.in_w) v = bf_ld(ip, (int64_t)iy * p.in_w + ix);
     sx[t] = v;
   }
   __syncthreads();
@@ -89,7 +81,7 @@ __global__ void __launch_bounds__(256) upfirdn2d_kernel(const T* __restrict__ in
         acc += sx[ry * p.tile_in_w + rx] * sk[ky * p.kw + kx];
       }
     }
-    uf_st(op, (int64_t)oy * p.out_w + ox, acc);
+    bf_st_nan(op, (int64_t)oy * p.out_w + ox, acc);
   }
 }
 
@@ -109,7 +101,7 @@ __global__ void __launch_bounds__(256) upfirdn2d_fir_kernel(const T* __restrict_
 #pragma unroll
   for (int a = 0; a < KH; ++a)
 #pragma unroll
-    for (int b = 0; b < KW; ++b) kf[a][b] = uf_ld(kernel, (KH - 1 - a) * KW + (KW - 1 - b));
+    for (int b = 0; b < KW; ++b) kf[a][b] = bf_ld(kernel, (KH - 1 - a) * KW + (KW - 1 - b));
   const int tid = threadIdx.x;
   int b_ = blockIdx.x;
   const int tx = b_ % p.tiles_x;
@@ -123,7 +115,7 @@ __global__ void __launch_bounds__(256) upfirdn2d_fir_kernel(const T* __restrict_
     const int ry = t / IW, rx = t - ry * IW;
     const int iy = iy0 + ry, ix = ix0 + rx;
     float v = 0.f;
-    if ((unsigned)iy < (unsigned)p.in_h && (unsigned)ix < (unsigned)p.in_w) v = uf_ld(ip, (int64_t)iy * p.in_w + ix);
+    if ((unsigned)iy < (unsigned)p.in_h && (unsigned)ix < (unsigned)p.in_w) v = bf_ld(ip, (int64_t)iy * p.in_w + ix);
     sx[ry * LDW + rx] = v;
   }
   __syncthreads();
@@ -151,7 +143,7 @@ __global__ void __launch_bounds__(256) upfirdn2d_fir_kernel(const T* __restrict_
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
     const int oy = oy0 + ly0 + r;
-    if (oy < p.out_h) uf_st(op, (int64_t)oy * p.out_w + ox, acc[r]);
+    if (oy < p.out_h) bf_st_nan(op, (int64_t)oy * p.out_w + ox, acc[r]);
   }
 }
 
@@ -181,7 +173,7 @@ __global__ void __launch_bounds__(256) upfirdn2d_firw_kernel(const T* __restrict
 #pragma unroll
   for (int a = 0; a < KH; ++a)
 #pragma unroll
-    for (int b = 0; b < KW; ++b) kf[a][b] = uf_ld(kernel, (KH - 1 - a) * KW + (KW - 1 - b));
+    for (int b = 0; b < KW; ++b) kf[a][b] = bf_ld(kernel, (KH - 1 - a) * KW + (KW - 1 - b));
   const int tid = threadIdx.x;
   int b_ = blockIdx.x;
   const int tx = b_ % p.tiles_x;
@@ -212,7 +204,7 @@ __global__ void __launch_bounds__(256) upfirdn2d_firw_kernel(const T* __restrict
       if constexpr (BF) {
         const uf_h8 raw = *reinterpret_cast<const uf_h8*>(in + e0);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) f[2 * q] = __uint_as_float(raw.w[q] << 16), f[2 * q + 1] = __uint_as_float(raw.w[q] & 0xffff0000u);
+        for (int q = 0; q < 4; ++q) f[2 * q] = bf_lo(raw.w[q]), f[2 * q + 1] = bf_hi(raw.w[q]);
       } else {
         const uf_f4 raw = *reinterpret_cast<const uf_f4*>(in + e0);
 #pragma unroll
@@ -221,7 +213,7 @@ __global__ void __launch_bounds__(256) upfirdn2d_firw_kernel(const T* __restrict
     } else if (rowok) {  // vector sticks out of the tensor: element-wise
 #pragma unroll
       for (int e = 0; e < EV; ++e)
-        if (e0 + e >= 0 && e0 + e < pend) f[e] = uf_ld(in, e0 + e);
+        if (e0 + e >= 0 && e0 + e < pend) f[e] = bf_ld(in, e0 + e);
     }
     if constexpr (BF) {
       // rows whose first element is odd were loaded from one element earlier (word alignment): shift them left by one so that LDS
@@ -281,7 +273,7 @@ __global__ void __launch_bounds__(256) upfirdn2d_firw_kernel(const T* __restrict
     const int64_t o = (int64_t)oy * p.out_w + ox;
     if constexpr (BF) {
       uint16_t h[4];
-      for (int c = 0; c < 4; ++c) uf_st(h, c, acc[r][c]);
+      for (int c = 0; c < 4; ++c) bf_st_nan(h, c, acc[r][c]);
       *reinterpret_cast<uint2*>(op + o) = make_uint2((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16));
     } else {
       *reinterpret_cast<float4*>(op + o) = make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);

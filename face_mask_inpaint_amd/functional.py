@@ -89,6 +89,11 @@ def _L():
     return _lib.lib()
 
 
+def _typed(name, t):
+    """the library entry `name` for t's element type: fmi_<name>_bf16 or fmi_<name>_f32"""
+    return getattr(_L(), f"{name}_{'bf16' if t.dtype == torch.bfloat16 else 'f32'}")
+
+
 def _st():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -2421,7 +2426,7 @@ class _ScaleChannels(torch.autograd.Function):
         n, c = s.shape
         p = x.numel() // (n * c)
         y = torch.empty_like(x)
-        (_L().scale_channels_bf16 if x.dtype == BF16 else _L().scale_channels_f32)(_p(x), _p(s), _p(y), n, p, c, _st())
+        _typed("scale_channels", x)(_p(x), _p(s), _p(y), n, p, c, _st())
         ctx.save_for_backward(x, s)
         return y
 
@@ -2432,20 +2437,15 @@ class _ScaleChannels(torch.autograd.Function):
         n, c = s.shape
         p = x.numel() // (n * c)
         gx = gs = None
-        b16 = x.dtype == BF16
-        if not b16 and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and _scale_bwd_ok(g, x, s, c):
+        if ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and _scale_bwd_ok(g, x, s, c):
             return _scale_channels_bwd(g, x, s, n, p, c)
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
-            (_L().scale_channels_bf16 if b16 else _L().scale_channels_f32)(_p(g), _p(s), _p(gx), n, p, c, _st())
-        if ctx.needs_input_grad[1] and b16:
+            _typed("scale_channels", x)(_p(g), _p(s), _p(gx), n, p, c, _st())
+        if ctx.needs_input_grad[1]:
             gs = torch.empty_like(s)
             ws = _parts_ws(x.device, max(2048, n) * c)
-            _L().scale_channels_gs_bf16(_p(g), _p(x), _p(gs), _p(ws), ws.numel(), n, p, c, _st())
-        elif ctx.needs_input_grad[1]:
-            gs = torch.empty_like(s)
-            ws = _parts_ws(x.device, max(2048, n) * c)
-            _L().scale_channels_gs_f32(_p(g), _p(x), _p(gs), _p(ws), ws.numel(), n, p, c, _st())
+            _typed("scale_channels_gs", x)(_p(g), _p(x), _p(gs), _p(ws), ws.numel(), n, p, c, _st())
         return gx, gs
 
 
@@ -2454,15 +2454,17 @@ def scale_channels(x, s):
 
 
 class _ScaleChannelsAdd(torch.autograd.Function):
-    """y[n,p,c] = x[n,p,c] * s[n,c] + res[n,p,c] (fp32): the SE gate and the residual add of an IR-SE block in one pass"""
+    """y[n,p,c] = x[n,p,c] * s[n,c] + res[n,p,c] (fp32 or bf16 activations, fp32 gates): the SE gate and the residual add of an IR-SE
+    block in one pass"""
 
     @staticmethod
     def forward(ctx, x, s, res):
-        _chk(x, s, res)
+        _chk(x, res, dtype=x.dtype)
+        _chk(s)
         n, c = s.shape
         p = x.numel() // (n * c)
         y = torch.empty_like(x)
-        _L().scale_channels_add_f32(_p(x), _p(s), _p(res), _p(y), n, p, c, _st())
+        _typed("scale_channels_add", x)(_p(x), _p(s), _p(res), _p(y), n, p, c, _st())
         ctx.save_for_backward(x, s)
         return y
 
@@ -2478,48 +2480,29 @@ class _ScaleChannelsAdd(torch.autograd.Function):
             return gx, gs, (g if ctx.needs_input_grad[2] else None)
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
-            _L().scale_channels_f32(_p(g), _p(s), _p(gx), n, p, c, _st())
+            _typed("scale_channels", x)(_p(g), _p(s), _p(gx), n, p, c, _st())
         if ctx.needs_input_grad[1]:
             gs = torch.empty_like(s)
             ws = _parts_ws(x.device, max(2048, n) * c)
-            _L().scale_channels_gs_f32(_p(g), _p(x), _p(gs), _p(ws), ws.numel(), n, p, c, _st())
+            _typed("scale_channels_gs", x)(_p(g), _p(x), _p(gs), _p(ws), ws.numel(), n, p, c, _st())
         return gx, gs, (g if ctx.needs_input_grad[2] else None)
-
-
-class _ScaleChannelsAddBF16(torch.autograd.Function):
-    """bf16 twin of _ScaleChannelsAdd (fp32 gates)"""
-
-    @staticmethod
-    def forward(ctx, x, s, res):
-        _chk(x, res, dtype=BF16)
-        _chk(s)
-        n, c = s.shape
-        p = x.numel() // (n * c)
-        y = torch.empty_like(x)
-        _L().scale_channels_add_bf16(_p(x), _p(s), _p(res), _p(y), n, p, c, _st())
-        ctx.save_for_backward(x, s)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        x, s = ctx.saved_tensors
-        g = g.contiguous()
-        n, c = s.shape
-        p = x.numel() // (n * c)
-        gx = torch.empty_like(x)
-        _L().scale_channels_bf16(_p(g), _p(s), _p(gx), n, p, c, _st())
-        gs = torch.empty_like(s)
-        ws = _parts_ws(x.device, max(2048, n) * c)
-        _L().scale_channels_gs_bf16(_p(g), _p(x), _p(gs), _p(ws), ws.numel(), n, p, c, _st())
-        return gx, gs, g
 
 
 def scale_channels_add(x, s, res):
     if x.dtype == BF16 and x.shape == res.shape and x.shape[-1] % 8 == 0:
-        return _ScaleChannelsAddBF16.apply(x.contiguous(), s.contiguous(), res.contiguous())
+        return _ScaleChannelsAdd.apply(x.contiguous(), s.contiguous(), res.contiguous())
     if x.dtype != torch.float32 or x.shape[-1] % 4 or x.shape != res.shape:
         return add(scale_channels(x, s), res)
     return _ScaleChannelsAdd.apply(x.contiguous(), s.contiguous(), res.contiguous())
+
+
+def _gap_pass_backward(ctx, gp, gx_pass):
+    """gx = g_x' + g_pooled[n][c] / (H W) in one pass, in the type of x"""
+    n, h, w, c = ctx.shape
+    gx_pass = gx_pass.contiguous()
+    gx = torch.empty_like(gx_pass)
+    _typed("add_bcast", gx_pass)(_p(gx_pass), _p(gp.contiguous()), _p(gx), n, h * w, c, _st())
+    return gx
 
 
 class _GlobalAvgPoolPassBF16(torch.autograd.Function):
@@ -2536,12 +2519,7 @@ class _GlobalAvgPoolPassBF16(torch.autograd.Function):
         ctx.shape = x.shape
         return pooled, x.view_as(x)
 
-    @staticmethod
-    def backward(ctx, gp, gx_pass):
-        n, h, w, c = ctx.shape
-        gx = torch.empty(ctx.shape, device=gp.device, dtype=BF16)
-        _L().add_bcast_bf16(_p(gx_pass.contiguous()), _p(gp.contiguous()), _p(gx), n, h * w, c, _st())
-        return gx
+    backward = staticmethod(_gap_pass_backward)
 
 
 def global_avg_pool_pass_bf16(x):
@@ -2563,12 +2541,7 @@ class _GlobalAvgPoolPassF32(torch.autograd.Function):
         ctx.shape = x.shape
         return y, x.view_as(x)
 
-    @staticmethod
-    def backward(ctx, gp, gx_pass):
-        n, h, w, c = ctx.shape
-        gx = torch.empty(ctx.shape, device=gp.device, dtype=torch.float32)
-        _L().add_bcast_f32(_p(gx_pass.contiguous()), _p(gp.contiguous()), _p(gx), n, h * w, c, _st())
-        return gx
+    backward = staticmethod(_gap_pass_backward)
 
 
 def global_avg_pool_pass(x):
@@ -2656,7 +2629,7 @@ class _NoiseBiasAct(torch.autograd.Function):
         c = x.shape[-1]
         y = torch.empty_like(x)
         with _prof(f"bytes:noise_bias_act|{tuple(x.shape)}", 2.0 * x.element_size() * x.numel()):
-            (_L().noise_bias_act_bf16 if x.dtype == BF16 else _L().noise_bias_act_f32)(
+            _typed("noise_bias_act", x)(
                 _p(x), _p(bias), _p(noise), _p(nw), _p(y), x.numel() // c, c, alpha, scale, _st())
         ctx.save_for_backward(y, noise)
         ctx.cfg = (alpha, scale, bias is not None, nw is not None)
@@ -2708,7 +2681,7 @@ class _UpFirDnNHWC(torch.autograd.Function):
             if ctx.sep:
                 _L().blur_act_bf16(_p(x), _p(kernel), _p(y), n, h, w, c, pad[0], pad[1], pad[0], pad[1], None, None, None, None, 1.0, 1.0, 1, _st())
             else:
-                (_L().upfirdn2d_nhwc_bf16 if x.dtype == BF16 else _L().upfirdn2d_nhwc_f32)(_p(x), _p(kernel), _p(y), n, h, w, c, kh, kw, up, up, down, down, pad[0], pad[1], pad[0], pad[1], _st())
+                _typed("upfirdn2d_nhwc", x)(_p(x), _p(kernel), _p(y), n, h, w, c, kh, kw, up, up, down, down, pad[0], pad[1], pad[0], pad[1], _st())
         ctx.save_for_backward(kernel)
         ctx.cfg = (up, down, pad, (n, h, w, c), (oh, ow))
         return y
@@ -2727,7 +2700,7 @@ class _UpFirDnNHWC(torch.autograd.Function):
             if ctx.sep:
                 _L().blur_act_bf16(_p(g.contiguous()), _p(gk), _p(gx), n, oh, ow, c, gx0, gx1, gy0, gy1, None, None, None, None, 1.0, 1.0, 1, _st())
             else:
-                (_L().upfirdn2d_nhwc_bf16 if g.dtype == BF16 else _L().upfirdn2d_nhwc_f32)(_p(g.contiguous()), _p(gk), _p(gx), n, oh, ow, c, kh, kw, down, down, up, up, gx0, gx1, gy0, gy1, _st())
+                _typed("upfirdn2d_nhwc", g)(_p(g.contiguous()), _p(gk), _p(gx), n, oh, ow, c, kh, kw, down, down, up, up, gx0, gx1, gy0, gy1, _st())
         return gx, None, None, None, None, None
 
 
@@ -2763,7 +2736,7 @@ class _PReLU(torch.autograd.Function):
         _chk(a)
         c = x.shape[-1]
         y = torch.empty_like(x)
-        (_L().prelu_bf16 if x.dtype == BF16 else _L().prelu_f32)(_p(x), _p(a), _p(y), x.numel() // c, c, _st())
+        _typed("prelu", x)(_p(x), _p(a), _p(y), x.numel() // c, c, _st())
         ctx.save_for_backward(x, a)
         return y
 
@@ -2793,7 +2766,7 @@ class _Subsample(torch.autograd.Function):
         _chk(x, dtype=x.dtype)
         n, h, w, c = x.shape
         y = torch.empty((n, (h - 1) // stride + 1, (w - 1) // stride + 1, c), device=x.device, dtype=x.dtype)
-        (_L().subsample_bf16 if x.dtype == BF16 else _L().subsample_f32)(_p(x), _p(y), n, h, w, c, stride, 0, _st())
+        _typed("subsample", x)(_p(x), _p(y), n, h, w, c, stride, 0, _st())
         ctx.cfg = (x.shape, stride)
         return y
 
@@ -2801,7 +2774,7 @@ class _Subsample(torch.autograd.Function):
     def backward(ctx, g):
         (n, h, w, c), stride = ctx.cfg
         gx = torch.empty((n, h, w, c), device=g.device, dtype=g.dtype)
-        (_L().subsample_bf16 if g.dtype == BF16 else _L().subsample_f32)(_p(g.contiguous()), _p(gx), n, h, w, c, stride, 1, _st())
+        _typed("subsample", g)(_p(g.contiguous()), _p(gx), n, h, w, c, stride, 1, _st())
         return gx, None
 
 
@@ -2822,20 +2795,17 @@ class _BatchNormTrain(torch.autograd.Function):
         """slope != 1: lrelu(BatchNorm(x), slope) in the same pass each way (0 = ReLU), as instance_norm_act does.
         passthrough: x itself is returned as a fourth output for x's OTHER consumer (the identity shortcut of an IR block); its
         gradient then arrives here and joins gx inside the backward kernel instead of in a separate accumulation pass"""
-        b16 = x.dtype == BF16  # bf16 activations (IR-SE50 body of the pSp encoder): fp32 statistics / parameters, bf16 in and out
-        _chk(x, dtype=x.dtype)
+        _chk(x, dtype=x.dtype)  # bf16 activations (IR-SE50 body of the pSp encoder): fp32 statistics / parameters, bf16 in and out
         _chk(gamma, beta)
-        lib = _L()
         c = x.shape[-1]
         if x.shape[0] % groups:
             raise FmiError("grouped BatchNorm: the batch does not divide into the groups")
         rows = x.numel() // c // groups
         sums, ws = _norm_ws(x.device, groups, c)
         stats = torch.empty((groups, c, 2), device=x.device, dtype=torch.float32)
-        (lib.instnorm_stats_bf16 if b16 else lib.instnorm_stats_f32)(_p(x), C.c_void_p(sums.data_ptr()), _p(stats), groups, rows, c, eps,
-                                                                      C.c_void_p(ws.data_ptr()), ws.numel(), _st())
+        _typed("instnorm_stats", x)(_p(x), C.c_void_p(sums.data_ptr()), _p(stats), groups, rows, c, eps, C.c_void_p(ws.data_ptr()), ws.numel(), _st())
         y = torch.empty_like(x)
-        (lib.instnorm_apply_bf16 if b16 else lib.instnorm_apply_f32)(_p(x), _p(stats), _p(gamma), _p(beta), _p(y), groups, rows, c, slope, _st())
+        _typed("instnorm_apply", x)(_p(x), _p(stats), _p(gamma), _p(beta), _p(y), groups, rows, c, slope, _st())
         ctx.save_for_backward(x, stats, gamma, beta)
         ctx.groups, ctx.slope = groups, slope
         ctx.mark_non_differentiable(stats, sums)

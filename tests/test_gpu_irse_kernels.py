@@ -1,4 +1,4 @@
-"""GPU: the bandwidth kernels between the convolutions of the IR-SE50 body (csrc/norm.hip, sg2.hip, enc_bf16.hip, sg2_bf16.hip, pool.hip),
+"""GPU: the bandwidth kernels between the convolutions of the IR-SE50 body (csrc/norm.hip, chan.hip, sg2_bf16.hip, pool.hip),
 one by one, against the float64 references of tests/irse_reference.py.
 
 The references get float64 copies of the very operands a kernel read: for bf16 the rounded values; for the BatchNorm apply and backward
@@ -133,12 +133,12 @@ def plan_norm_apply(n, hw):
 
 
 def _sum_parts_chain(nparts):
-    """sum_parts_f32_kernel (sg2.hip) / sum_parts_kernel (sg2_bf16.hip): a lane walks ceil(nparts / 16) parts, 3 tree levels, 16 lanes"""
+    """sum_parts_kernel<T> (sum_parts.h): a lane walks ceil(nparts / 16) parts, 3 tree levels, 16 lanes"""
     return _cdiv(nparts, 16) + 3 + 16
 
 
 def plan_prelu_bwd_f32(rows, c, det=False):
-    """sg2.hip fmi_prelu_bwd_f32() with FF.prelu's workspace of 1024 c floats: (path, blocks, L)"""
+    """chan.hip fmi_prelu_bwd_f32() with FF.prelu's workspace of 1024 c floats: (path, blocks, L)"""
     c4 = c // 4
     if c % 4 == 0 and c4 <= 256 and c4 & (c4 - 1) == 0:
         rpb, blocks = _split(rows, min(_cdiv(rows, 64), 1024))
@@ -149,19 +149,19 @@ def plan_prelu_bwd_f32(rows, c, det=False):
 
 
 def plan_prelu_bwd_bf16(rows, c):
-    """enc_bf16.hip fmi_prelu_bwd_bf16() with FF.prelu's workspace of 512 c floats; sum_rows_f32_kernel adds the parts in one chain"""
+    """chan.hip fmi_prelu_bwd_bf16() with FF.prelu's workspace of 512 c floats; sum_rows_f32_kernel adds the parts in one chain"""
     rpb, blocks = _split(rows, min(_cdiv(rows, 64), 512))
     rl = 256 // (c // 8)
     return blocks, _cdiv(rpb, rl) + rl + blocks
 
 
 def _gs_finish_chain(nparts):
-    """scale_channels_gs_finish_kernel (sg2.hip): four accumulators and their tree"""
+    """scale_channels_gs_finish_kernel (chan.hip): four accumulators and their tree"""
     return _cdiv(nparts, 4) + 3 + 2
 
 
 def plan_scale_bwd_f32(n, p, c):
-    """sg2.hip fmi_scale_channels_bwd_f32() with FF._scale_channels_bwd's workspace of max(4096, n) c floats"""
+    """chan.hip fmi_scale_channels_bwd_f32() with FF._scale_channels_bwd's workspace of max(4096, n) c floats"""
     ws_floats = max(4096, n) * c  # functional._scale_channels_bwd
     cap = min(ws_floats // (n * c), _cdiv(4096, n))  # the launcher: what the workspace holds, at most ceil(4096 / N)
     rpb, blocks = _split(p, min(_cdiv(p, 64), cap))
@@ -170,7 +170,7 @@ def plan_scale_bwd_f32(n, p, c):
 
 
 def plan_scale_gs_f32(n, p, c, ws=True, det=False):
-    """sg2.hip fmi_scale_channels_gs_f32(); ws: FF's workspace of max(2048, n) c floats, otherwise fp32 atomics"""
+    """chan.hip fmi_scale_channels_gs_f32(); ws: FF's workspace of max(2048, n) c floats, otherwise fp32 atomics"""
     blocks = _cdiv(p, 128)
     ws_floats = max(2048, n) * c  # functional._ScaleChannels.backward
     cap = min(ws_floats // (n * c), _cdiv(2048, n)) if ws else 1024  # the launcher: what the workspace holds, at most ceil(2048 / N)
@@ -182,7 +182,7 @@ def plan_scale_gs_f32(n, p, c, ws=True, det=False):
 
 
 def plan_scale_gs_bf16(n, p, c):
-    """sg2_bf16.hip fmi_scale_channels_gs_bf16() / parts_for() with FF's workspace of max(2048, n) c floats"""
+    """chan.hip fmi_scale_channels_gs_bf16() / sum_parts.h parts_for() with FF's workspace of max(2048, n) c floats"""
     ws_floats = max(2048, n) * c  # functional._ScaleChannels.backward
     b = min(_cdiv(p, 64), _cdiv(2048, n), ws_floats // (n * c))  # parts_for(): want, then what the workspace holds
     rpb, blocks = _split(p, b)
@@ -207,7 +207,7 @@ def plan_pool_f32(n, h, w, c, det=False):
 
 
 def plan_pool_bf16(n, p, c):
-    """enc_bf16.hip fmi_global_avgpool_bf16() with FF's workspace of 64 n c floats: (parts, L)"""
+    """chan.hip fmi_global_avgpool_bf16() with FF's workspace of 64 n c floats: (parts, L)"""
     rpb, blocks = _split(p, min(_cdiv(p, 64), 64))
     rl = 256 // (c // 8)
     return blocks, _cdiv(rpb, rl) + rl + blocks + 1
@@ -226,11 +226,12 @@ def test_plans_reach_the_branches_the_cases_are_named_for():
     assert plan_norm_reduce(1, 252, 64)[:2] == (64, 4)                               # four blocks of 64, tail loops only (PL = 16)
     assert plan_norm_reduce(1, 2046, 64)[2] == 4                                     # 64 rows over 16 lanes: the 4-deep loop body
     assert 256 // (1024 // 4) == 1                                                   # CG = 256, one pixel lane
-    assert plan_norm_reduce(1, 7232, 8)[1] == 113                                    # > 112 parts: 8-deep loop of sum_parts_f64_kernel
+    assert plan_norm_reduce(1, 7232, 8)[1] == 113                                    # > 112 parts: 8-deep loop of sum_parts_kernel<double>
     assert plan_norm_reduce(2, 32896, 8)[0] == 128                                   # rows_per_block doubles in the reduction
     assert plan_norm_apply(1, 262656) == 32                                          # ... and in the apply launches
     assert plan_norm_reduce(1, 4480, 8, ws=False)[:2] == (512, 9)                    # several 512-row chunks of fp64 atomics
-    assert plan_prelu_bwd_f32(7232, 64)[:2] == ("vec", 113)                          # 8-deep loop of sum_parts_f32_kernel
+    assert plan_prelu_bwd_f32(7232, 64)[:2] == ("vec", 113)                          # 8-deep loop of sum_parts_kernel<float>, one group
+    assert plan_scale_gs_bf16(3, 9000, 8)[0] == 141                                  # ... and with three groups (blockIdx.y)
     assert plan_prelu_bwd_f32(300, 132)[:2] == ("scalar", 3) and plan_prelu_bwd_f32(300, 12)[0] == "scalar"
     assert plan_prelu_bwd_bf16(40000, 8)[0] > 500                                    # sum_rows_f32_kernel walks ~512 parts
     assert plan_pool_f32(2, 16, 16, 64)[0] == "stream" and plan_pool_f32(3, 8, 8, 512)[0] == "stream"
@@ -784,8 +785,8 @@ def test_se_gate_bf16(dev, FF, c, p, n, add):
 @pytest.mark.parametrize("n,p,c", [(2, 10, 12), (1, 5, 12), (3, 252, 12), (2, 37, 100)])
 def test_se_gate_bf16_channels_not_a_multiple_of_8(dev, FF, n, p, c):
     """C % 8 != 0: FF.scale_channels_add leaves its fused bf16 kernel for scale_channels + add, whose eight-channel kernels do not cover
-    such a C either; the library's one-element-per-thread forms do (sg2_bf16.hip scale_channels_bf16_scalar_kernel and
-    scale_channels_gs_bf16_scalar_kernel: 4 row lanes, then a 2-level tree; enc_bf16.hip add_bf16_scalar_kernel when the element count
+    such a C either; the library's one-element-per-thread forms do (chan.hip scale_channels_scalar_kernel<uint16_t> and
+    scale_channels_gs_bf16_scalar_kernel: 4 row lanes, then a 2-level tree; add_bf16_scalar_kernel when the element count
     is no multiple of 8, as at (1, 5, 12)).  C = 100 takes two 64-channel stripes of the gs kernel, the second one partly idle.  The
     product is rounded to bf16 before the residual is added: two bf16 roundings"""
     x, s, res, g = _gate_inputs(n, p, c, 399 + p, BF16)
@@ -871,3 +872,119 @@ def test_subsample(dev, FF, extent, stride, c, dtype):
     g = torch.randn(y.shape, generator=gen).to(dtype)
     y.backward(g.to(dev))
     assert torch.equal(xd.grad.cpu(), R.subsample(x, stride, g).gx)
+
+
+# ---- which kernel an entry takes, and what it refuses ------------------------------------------------------------------------------
+def _off_by_one(t, dev):
+    """the values of t on the device as a contiguous view that starts one element into a 16-byte-aligned buffer"""
+    buf = torch.empty(t.numel() + 16, device=dev, dtype=t.dtype)
+    assert buf.data_ptr() % 16 == 0
+    v = buf[1:1 + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 != 0
+    return v
+
+
+def test_f32_forward_chunk_and_scalar_kernels(dev, FF, lib):
+    """fmi_scale_channels_f32 reaches its chunk kernel (C % 4 == 0 and x, y, s on 16 bytes) and its one-element kernel two ways: by width
+    (C = 6) and by alignment (C = 8, x one float into a buffer); fmi_prelu_f32 likewise by alignment.  Each against float64, and the
+    aligned and the misaligned run of the same values bit for bit against each other"""
+    for n, p, c in [(2, 3, 8), (2, 5, 6)]:
+        x, s, _, _ = _gate_inputs(n, p, c, 600 + c, torch.float32)
+        r = R.scale_channels(x.double(), s.double())
+        xd, sd = x.to(dev), s.to(dev)
+        forms = [xd] if c % 4 else [xd, _off_by_one(x, dev)]
+        ys = []
+        for xf in forms:
+            y = _nan((n, p, c), dev)
+            lib.scale_channels_f32(FF._p(xf), FF._p(sd), FF._p(y), n, p, c, FF._st())
+            _within(y, r.y, _elem_tol(r.y, r.y_mag, torch.float32), f"scale_channels fp32 C={c} x at {xf.data_ptr() % 16}")
+            ys.append(y)
+        assert len(ys) == 1 or torch.equal(ys[0], ys[1]), "scale_channels fp32: chunk and scalar kernel differ"
+    rows, c = 6, 8
+    x, a, _ = _prelu_inputs(rows, c, 608, torch.float32)
+    r = R.prelu(x.double(), a.double())
+    ad, ys = a.to(dev), []
+    for xf in (x.to(dev), _off_by_one(x, dev)):
+        y = _nan((rows, c), dev)
+        lib.prelu_f32(FF._p(xf), FF._p(ad), FF._p(y), rows, c, FF._st())
+        _within(y, r.y, _elem_tol(r.y, r.y_mag, torch.float32), f"PReLU fp32 x at {xf.data_ptr() % 16}")
+        ys.append(y)
+    assert torch.equal(ys[0], ys[1]), "PReLU fp32: chunk and scalar kernel differ"
+
+
+def test_bf16_chunk_entries_refuse_a_misaligned_operand(dev, FF, lib):
+    """the bf16 entries have no one-element form for C % 8 == 0: a tensor that starts one element into a buffer is refused, and nothing
+    is launched (the output keeps its fill)"""
+    n, p, c = 1, 2, 8
+    x, s, res, _ = _gate_inputs(n, p, c, 620, BF16)
+    xd, sd, rd, xo = x.to(dev), s.to(dev), res.to(dev), _off_by_one(x, dev)
+    fill = torch.full((n, p, c), 7.0, device=dev, dtype=BF16)
+    y = fill.clone()
+    calls = {
+        "scale_channels_add": lambda: lib.scale_channels_add_bf16(FF._p(xo), FF._p(sd), FF._p(rd), FF._p(y), n, p, c, FF._st()),
+        "add_bcast": lambda: lib.add_bcast_bf16(FF._p(xo), FF._p(sd), FF._p(y), n, p, c, FF._st()),
+        "prelu": lambda: lib.prelu_bf16(FF._p(xo), FF._p(sd), FF._p(y), n * p, c, FF._st()),
+    }
+    for name, call in calls.items():
+        with pytest.raises(FF.FmiError, match="unsupported"):
+            call()
+        assert torch.equal(y, fill), name + ": the refused call wrote its output"
+    lib.scale_channels_add_bf16(FF._p(xd), FF._p(sd), FF._p(rd), FF._p(y), n, p, c, FF._st())  # the aligned twin of the first call runs
+    assert not torch.equal(y, fill)
+
+
+# ---- the two bf16 roundings stay where they are ------------------------------------------------------------------------------------
+def _bf16_bits_host(f32):
+    """fp32 tensor -> bf16 bit patterns (int64) by the rule of bf_round_nan (csrc/bf16x8.h) in integer arithmetic: a NaN stays a quiet NaN
+    with its sign, everything else -- infinities included -- rounds to nearest even"""
+    u = f32.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    nan = (u & 0x7FFFFFFF) > 0x7F800000
+    rne = (u + 0x7FFF + ((u >> 16) & 1)) >> 16
+    return torch.where(nan, (u | 0x00400000) >> 16, rne) & 0xFFFF
+
+
+def _bits_of(bf):
+    return bf.contiguous().view(torch.int16).to(torch.int64).cpu() & 0xFFFF
+
+
+def _from_bits(bits):
+    return (bits - ((bits & 0x8000) << 1)).to(torch.int16).view(BF16)
+
+
+def test_user_tensor_entries_quiet_a_nan_and_round_to_nearest_even(dev, FF, lib):
+    """fmi_fused_bias_act_bf16 and fmi_upfirdn2d_bf16 take a caller's tensor: 1 x 8 channels x 4 x 4 with +-inf, +-NaN, the largest
+    finite bf16 and the images of two fp32 ties (0x3f808000: even lower neighbour, 0x3f818000: odd) under the host rule.  With identity
+    settings (no bias, slope 1, scale 1; one tap of 1.0) the output bits are the host rule of the input, every element.  A bf16 INPUT
+    cannot hold a tie, so a second pass scales by 1.5 (scale, or one tap of 1.5): 1.5 (1 + 2^-7) and 1.5 (1 + 3 2^-7) are ties inside
+    the kernel with an odd and an even lower neighbour, 1.5 x 0x7f7f overflows to an infinity; NaN payloads under a multiplication are
+    the hardware's, so there the NaN elements are only required to stay NaN"""
+    special = torch.tensor([0x7F800000, 0xFF800000, 0x7FC00000, 0xFFC00000, 0x7F7F0000, 0xFF7F0000, 0x3F808000, 0x3F818000, 0xBF808000,
+                            0xBF818000, 0x3F810000, 0x3F830000, 0xBF810000, 0xBF830000], dtype=torch.int64)
+    f = torch.randn(8 * 16, generator=torch.Generator().manual_seed(640))
+    f[:special.numel()] = (special - ((special & 0x80000000) << 1)).to(torch.int32).view(torch.float32)
+    x = _from_bits(_bf16_bits_host(f)).reshape(8, 4, 4)  # [major = N C, H, W]
+    assert _bits_of(x)[0, 1, 2:4].tolist() == [0x3F80, 0x3F82]  # the ties went to their even neighbours
+    xd = x.to(dev)
+    wide = x.float()
+    nan = torch.isnan(wide)
+
+    def check(out, factor, what):
+        got = _bits_of(out)
+        want = _bf16_bits_host(wide * factor).reshape(got.shape)
+        if factor == 1.0:
+            assert torch.equal(got, want), what
+        else:
+            assert torch.equal(got[~nan], want[~nan]) and bool(torch.isnan(out.float().cpu()[nan]).all()), what
+            assert want.reshape(-1)[10:12].tolist() == [0x3FC2, 0x3FC4] and want.reshape(-1)[4] == 0x7F80  # ties up and down, overflow
+
+    for factor in (1.0, 1.5):
+        for form, xin in (("16-byte", xd), ("one-element", xd.reshape(-1)[1:])):  # the second starts 2 bytes off: fused_bias_act_kernel
+            y = torch.zeros_like(xin)
+            lib.fused_bias_act_bf16(FF._p(xin), None, None, FF._p(y), xin.numel(), 1, 1, 3, 0, 1.0, factor, FF._st())
+            full = torch.cat([xd.reshape(-1)[:1], y]) if form == "one-element" else y  # element 0, +inf, was not part of that call
+            check(full.reshape(8, 4, 4), factor, f"fused_bias_act bf16 {form} x {factor}")
+        tap = torch.full((1, 1), factor, device=dev, dtype=BF16)
+        y = torch.zeros_like(xd)
+        lib.upfirdn2d_bf16(FF._p(xd), FF._p(tap), FF._p(y), 8, 4, 4, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, FF._st())
+        check(y, factor, f"upfirdn2d bf16 x {factor}")
