@@ -20,6 +20,7 @@ from .modules.pluralistic_model import base_function
 
 MASK_DETECTOR_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
 GENERATOR_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
+FEATURE_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
 
 
 def get_args(argv=None):
@@ -46,6 +47,11 @@ def get_args(argv=None):
     p.add_argument("--generator_dtype", type=str, default="fp32", choices=("fp32", "bf16"),
                    help="this build's extra: activation type of the generator's decoder blocks, attention and Output block (bf16: inference "
                         "on the bf16 kernels; needs a token count at attn1 that is a multiple of 128, which --old_model does not give)")
+    # not --encoder_*: process_params would sweep it into define_e's keywords
+    p.add_argument("--feature_dtype", type=str, default="fp32", choices=("fp32", "bf16"),
+                   help="this build's extra: activation type of the two encoders and the guided attention (bf16: inference on the bf16 "
+                        "kernels; needs H and W to be multiples of 8 and a token count at the guided attention that is a multiple of 128, "
+                        "which --old_model does not give)")
     p.add_argument("--encoder_type", type=str, default="pluralistic")
     p.add_argument("--encoder_ngf", type=int, default=32)
     p.add_argument("--encoder_z_nc", type=int, default=128)
@@ -114,6 +120,12 @@ def build(args, device):
     if gdt == "bf16" and args.old_model:
         raise FF.FmiError("--generator_dtype bf16 does not go with --old_model: its 218 x 178 input gives a token count at attn1 that is not a "
                           "multiple of 128, which the bf16 attention kernel needs; run --old_model in fp32")
+    fdt = getattr(args, "feature_dtype", "fp32")
+    if fdt not in FEATURE_DTYPES:
+        raise FF.FmiError(f"feature_dtype must be one of {sorted(FEATURE_DTYPES)}, got {fdt!r}")
+    if fdt == "bf16" and args.old_model:
+        raise FF.FmiError("--feature_dtype bf16 does not go with --old_model: its 218 x 178 input is not a multiple of 8 and runs without the "
+                          "prior, which the bf16 encoders and guided attention do not take; run --old_model in fp32")
     dt = getattr(args, "mask_detector_dtype", "fp32")
     if dt not in MASK_DETECTOR_DTYPES:
         raise FF.FmiError(f"mask_detector_dtype must be one of {sorted(MASK_DETECTOR_DTYPES)}, got {dt!r}")
@@ -124,7 +136,8 @@ def build(args, device):
     mask_detector = mask_detector.to(device).eval()
     encoder_params, decoder_params = process_params(args)
     kw = dict(out_size=(218, 178)) if args.old_model else {}
-    generator = ReferenceFill(None, encoder_params, decoder_params, use_att=bool(args.use_att), decoder_dtype=GENERATOR_DTYPES[gdt], **kw).to(device)
+    generator = ReferenceFill(None, encoder_params, decoder_params, use_att=bool(args.use_att), decoder_dtype=GENERATOR_DTYPES[gdt],
+                              feature_dtype=FEATURE_DTYPES[fdt], **kw).to(device)
     if args.pt_ckpt_path:
         generator.load_state_dict(torch.load(args.pt_ckpt_path, map_location="cpu", weights_only=True), strict=False)
     return generator.eval(), mask_detector

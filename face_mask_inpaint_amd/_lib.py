@@ -81,6 +81,11 @@ SIGNATURES = {
     "fmi_se_gate_f32": [vp, i32, i64, f32, vp, vp, vp, i32, i32, vp],
     "fmi_irse_tail_bf16": [vp] * 8 + [i32] * 7 + [vp],
     "fmi_irse_stem_bf16": [vp] * 5 + [i64, i32, vp],
+    "fmi_conv2d_thin_in_fwd_bf16": [PD, vp, vp, vp, f32, vp, vp],
+    "fmi_conv2d_c32_fwd_bf16": [PD, vp, vp, vp, f32, vp, vp],
+    "fmi_resblock_tail_bf16": [vp] * 5 + [i32] * 5 + [f32, vp],
+    "fmi_picnet_stem_tail_bf16": [vp] * 6 + [i32] * 5 + [f32, vp],
+    "fmi_guided_attention_fwd_bf16": [vp] * 5 + [i32] * 5 + [vp],
     "fmi_blur_act_bf16": [vp, vp, vp] + [i32] * 8 + [vp, vp, vp, vp, f32, f32, i32, vp],
     "fmi_torgb_fwd_bf16": [vp, vp, vp, vp, vp, vp, i32, i64, i32, vp],
     "fmi_torgb_bwd_bf16": [vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, i32, i64, i32, vp],
@@ -196,7 +201,7 @@ SIGNATURES = {
 STATUS = {0: "ok", 1: "bad argument", 2: "unsupported shape/mode", 3: "kernel launch failed"}
 
 
-PREDICATES = {"fmi_debug_bf16_tile": [i32], "fmi_set_deterministic": [i32], "fmi_get_deterministic": [], "fmi_conv2d_thin_supported": [PD], "fmi_conv2d_bf16_supported": [PD], "fmi_conv2d_thin_lrelu_supported": [PD], "fmi_conv2d_thin_lrelu_bwd_ws_bytes": [PD], "fmi_conv_transpose2d_pair_bwd_supported": [PD, i32, i32], "fmi_conv_transpose2d_pair_bwd_ws_bytes": [PD, i32, i32], "fmi_attention_fwd_uses_pieces": [i32] * 5, "fmi_attention_bwd_uses_pieces": [i32] * 5, "fmi_attention_fwd_waves": [i32] * 2, "fmi_attention_fwd_bf16_waves": [i32] * 2, "fmi_attention_bwd_structure": [i32] * 2}
+PREDICATES = {"fmi_debug_bf16_tile": [i32], "fmi_set_deterministic": [i32], "fmi_get_deterministic": [], "fmi_conv2d_thin_supported": [PD], "fmi_conv2d_bf16_supported": [PD], "fmi_conv2d_thin_lrelu_supported": [PD], "fmi_conv2d_thin_lrelu_bwd_ws_bytes": [PD], "fmi_conv_transpose2d_pair_bwd_supported": [PD, i32, i32], "fmi_conv_transpose2d_pair_bwd_ws_bytes": [PD, i32, i32], "fmi_attention_fwd_uses_pieces": [i32] * 5, "fmi_attention_bwd_uses_pieces": [i32] * 5, "fmi_attention_fwd_waves": [i32] * 2, "fmi_attention_fwd_bf16_waves": [i32] * 2, "fmi_guided_attention_fwd_bf16_waves": [i32] * 2, "fmi_attention_bwd_structure": [i32] * 2}
 
 
 class FmiError(RuntimeError):

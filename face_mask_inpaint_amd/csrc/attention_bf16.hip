@@ -23,10 +23,14 @@
 template <int D, int NCT>
 constexpr int attn_fwd_bf16_lds = 2 * 64 * ((2 * D + 16) + (2 * NCT * 32 + 64));
 
-template <int D, int NCT, int NW>
+// GUIDED (ExampleGuidedAttention, example_guided_att.py:21-41): the V tile is [ref | src], each CT / 2 channels wide -- a 16-byte chunk of
+// a row comes from v (= ref) for the first CT / 2 channels and from v2 (= src) for the rest -- so ONE softmax serves both value maps,
+// and the epilogue blends the first half with ref by the soft mask m [N,T]: o[:CT/2] = (1 - m) (A ref) + m ref, o[CT/2:] = A src.
+template <int D, int NCT, int NW, bool GUIDED = false>
 __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_bf16_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ v,
                                                                    uint16_t* __restrict__ o, float* __restrict__ lse,
-                                                                   const float* __restrict__ gamma, const uint16_t* __restrict__ res, int T) {
+                                                                   const float* __restrict__ gamma, const uint16_t* __restrict__ res, int T,
+                                                                   const uint16_t* __restrict__ v2, const float* __restrict__ mask) {
   constexpr int CT = NCT * 32, KEYS = 64;
   constexpr int KP = 2 * D + 16, VP = 2 * CT + 64;          // row pitches (bytes)
   constexpr int KBYTES = KEYS * KP, STAGE = KBYTES + KEYS * VP;
@@ -44,7 +48,9 @@ __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_bf16_kernel(const uint16_
   const int n = blockIdx.y;
   const int q0 = blockIdx.x * (NW * 32) + wid * 32;
   const uint16_t* qb = q + (int64_t)n * T * D;
-  const uint16_t* vb = v + (int64_t)n * T * CT;
+  constexpr int CV = GUIDED ? CT / 2 : CT;                  // channels of one value map
+  const uint16_t* vb = v + (int64_t)n * T * CV;
+  const uint16_t* vb2 = GUIDED ? v2 + (int64_t)n * T * CV : nullptr;
 
   // this lane's query fragment: B[k = d][col = query], d = 16 kk + 8 lh + j
   bf16x8_t qp[D / 16];
@@ -71,7 +77,10 @@ __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_bf16_kernel(const uint16_
     for (int i = 0; i < NVL; ++i) {
       const int f = tid + NTH * i;
       const int key = f / (CT / 8), ch = f % (CT / 8);
-      rv[i] = *reinterpret_cast<const u32x4_t*>(vb + (int64_t)(k0 + key) * CT + 8 * ch);
+      if constexpr (GUIDED)
+        rv[i] = *reinterpret_cast<const u32x4_t*>((ch < CV / 8 ? vb + 8 * ch : vb2 + 8 * (ch - CV / 8)) + (int64_t)(k0 + key) * CV);
+      else
+        rv[i] = *reinterpret_cast<const u32x4_t*>(vb + (int64_t)(k0 + key) * CT + 8 * ch);
     }
   };
   auto lstore = [&](int st) {
@@ -171,6 +180,7 @@ __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_bf16_kernel(const uint16_
   const float inv = 1.f / lsum;
   const float gm = gamma ? gamma[0] : 0.f;
   const int64_t row = (int64_t)n * T + q0 + l31;
+  const float mk = GUIDED ? mask[row] : 0.f;
 #pragma unroll
   for (int c = 0; c < NCT; ++c) {
 #pragma unroll
@@ -179,7 +189,16 @@ __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_bf16_kernel(const uint16_
       float f[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) f[e] = acc[c][4 * g + e] * inv;
-      if (gamma) {
+      if constexpr (GUIDED) {
+        if (c < NCT / 2) {  // (1 - m) (A ref) + m ref in fp32 before the one rounding; m = 1 returns ref bit for bit
+          const uint2 r = *reinterpret_cast<const uint2*>(v + row * CV + c * 32 + 8 * g + 4 * lh);
+          const float om = 1.f - mk;
+          f[0] = fmaf(om, f[0], mk * bf_lo(r.x));
+          f[1] = fmaf(om, f[1], mk * bf_hi(r.x));
+          f[2] = fmaf(om, f[2], mk * bf_lo(r.y));
+          f[3] = fmaf(om, f[3], mk * bf_hi(r.y));
+        }
+      } else if (gamma) {
         const uint2 r = *reinterpret_cast<const uint2*>(res + off);
         f[0] = fmaf(gm, f[0], bf_lo(r.x));
         f[1] = fmaf(gm, f[1], bf_hi(r.x));
@@ -206,8 +225,30 @@ extern "C" int fmi_attention_fwd_bf16(const uint16_t* q, const uint16_t* v, uint
   const dim3 grid(T / (nw * 32), N), block(nw * 64);
   hipStream_t st = (hipStream_t)stream;
 #define ATTB16_LAUNCH(DD, NN, WW) \
-  fmi_launch_lds<attn_fwd_bf16_kernel<DD, NN, WW>>(grid, block, attn_fwd_bf16_lds<DD, NN>, st, q, v, o, lse, gamma, residual, T)
+  fmi_launch_lds<attn_fwd_bf16_kernel<DD, NN, WW>>(grid, block, attn_fwd_bf16_lds<DD, NN>, st, q, v, o, lse, gamma, residual, T, (const uint16_t*)nullptr, \
+                                                   (const float*)nullptr)
   const int rc = D == 64 ? (nw == 8 ? ATTB16_LAUNCH(64, 8, 8) : ATTB16_LAUNCH(64, 8, 4)) : (nw == 8 ? ATTB16_LAUNCH(32, 4, 8) : ATTB16_LAUNCH(32, 4, 4));
 #undef ATTB16_LAUNCH
+  return rc != FMI_OK ? rc : fmi_launch_status();
+}
+
+// The guided attention and its blend in one launch (example_guided_att.py:21-41): q [N,T,D], src / ref [N,T,C], out [N,T,2C] bf16, mask fp32
+// [N,T].  The dispatch is the plain forward's: eight waves where whole workgroups still fill the chip, else four.
+extern "C" int fmi_guided_attention_fwd_bf16_waves(int N, int T) { return fmi_attention_fwd_bf16_waves(N, T); }
+
+extern "C" int fmi_guided_attention_fwd_bf16(const uint16_t* q, const uint16_t* src, const uint16_t* ref, const float* mask, uint16_t* out, int N,
+                                             int T, int D, int C, int waves, void* stream) {
+  if (!q || !src || !ref || !mask || !out || N <= 0 || T <= 0 || D <= 0 || C <= 0) return FMI_ERR_BAD_ARG;
+  if (T % 128 != 0 || !(D == 32 && C == 128) || N > 65535) return FMI_ERR_UNSUPPORTED;
+  if (waves != 0 && waves != 4 && !(waves == 8 && T % 256 == 0)) return FMI_ERR_UNSUPPORTED;
+  if ((((uintptr_t)q | (uintptr_t)src | (uintptr_t)ref | (uintptr_t)out) & 15) != 0 || ((uintptr_t)mask & 3) != 0) return FMI_ERR_BAD_ARG;
+  const int nw = waves ? waves : fmi_guided_attention_fwd_bf16_waves(N, T);
+  const dim3 grid(T / (nw * 32), N), block(nw * 64);
+  hipStream_t st = (hipStream_t)stream;
+#define ATTG16_LAUNCH(WW)                                                                                                                        \
+  fmi_launch_lds<attn_fwd_bf16_kernel<32, 8, WW, true>>(grid, block, attn_fwd_bf16_lds<32, 8>, st, q, ref, out, (float*)nullptr, (const float*)nullptr, \
+                                                        (const uint16_t*)nullptr, T, src, mask)
+  const int rc = nw == 8 ? ATTG16_LAUNCH(8) : ATTG16_LAUNCH(4);
+#undef ATTG16_LAUNCH
   return rc != FMI_OK ? rc : fmi_launch_status();
 }

@@ -223,11 +223,12 @@ def p3_of(t: torch.Tensor, lrelu_from: Optional[torch.Tensor] = None, slope: flo
 class PackedWeight:
     """Per-call packed effective weight of one conv: wf [taps][C][K] (autograd tensor), wt [taps][K][C]."""
 
-    __slots__ = ("wf", "wt", "rows", "C", "kh", "kw", "w3")
+    __slots__ = ("wf", "wt", "rows", "C", "kh", "kw", "w3", "wnk")
 
     def __init__(self, wf, wt, rows, Cc, kh, kw, w3=(None, None)):
         self.wf, self.wt, self.rows, self.C, self.kh, self.kw = wf, wt, rows, Cc, kh, kw
         self.w3 = w3  # (wf3, wt3): the same two packs as bf16 piece images (fmi_conv_desc.w3), or None where the shape has none
+        self.wnk = None  # the bf16 forward pack [K][taps][C], cut on first use by the bf16 encoder's convolutions (_wnk_of)
 
 
 W3_ENABLED = True  # write the bf16 piece images of every eligible pack (False: the kernels split the weight fragments themselves)
@@ -1505,6 +1506,130 @@ def irse_stem_bf16(x, scale, shift):
     z = torch.empty_like(y)
     _L().irse_stem_bf16(_p(x), _p(scale), _p(shift), _p(y), _p(z), x.numel() // c, c, _st())
     return y, z
+
+
+# ---- bf16 PICNet encoders and guided attention (ResEncoder(compute_dtype=torch.bfloat16), ExampleGuidedAttention on bf16 maps):
+# inference forms, no autograd nodes -- the caller (ResEncoder.check_inference) has refused grad mode.  Activations bf16 NHWC, the image
+# and the distribution heads fp32, parameters fp32; the bf16 weight packs are cut from the fp32 packs that weight_scope prepared. ----
+_SLOPE_VECS = {}
+
+
+def _slope_vec(device, k, slope):
+    """a [K] fp32 vector filled with ``slope`` (the per-column LeakyReLU of fmi_conv2d_fwd_chan_bf16), kept per (device, K, slope)"""
+    key = (str(device), int(k), float(slope))
+    v = _SLOPE_VECS.get(key)
+    if v is None:
+        v = _SLOPE_VECS[key] = torch.full((k,), float(slope), device=device, dtype=torch.float32)
+    return v
+
+
+def _wnk_of(pw: PackedWeight):
+    """the bf16 forward pack of pw, cut once per prepared weight (a PackedWeight lives for one weight_scope, or as long as a frozen
+    weight stays unchanged)"""
+    if pw.wnk is None:
+        pw.wnk = _pack_bf16(pw.wf)
+    return pw.wnk
+
+
+def conv2d_thin_in_bf16(x, pw: PackedWeight, bias, slope):
+    """lrelu(conv3x3(x) + bias, slope) from an fp32 NHWC image with at most 4 channels to a bf16 map of 32 or 64 channels, one launch"""
+    _chk(x, bias)
+    n, h, w, c = x.shape
+    k = pw.wf.shape[2]
+    if (pw.kh, pw.kw) != (3, 3) or c > 4 or k not in (32, 64):
+        raise FmiError(f"the bf16 stem convolution takes a 3 x 3 layer from at most 4 to 32 or 64 channels, got {c} -> {k} k{pw.kh}x{pw.kw}")
+    d, oh, ow = conv_desc(n, h, w, c, k, 3, 3, 1, 1)
+    y = torch.empty((n, h, w, k), device=x.device, dtype=BF16)
+    with _prof(f"conv_fwd_bf16|{n}x{h}x{w} {c}->{k} k3s1 thin-in", 2.0 * n * h * w * k * c * 9):
+        _L().conv2d_thin_in_fwd_bf16(C.byref(d), _p(x), _p(pw.wf), _p(bias), float(slope), _p(y), _st())
+    return y
+
+
+def conv2d_enc_bf16(x, pw: PackedWeight, bias, pad, slope=1.0):
+    """lrelu(conv(x) + bias, slope) on a bf16 NHWC map in one launch (slope 1: conv + bias): the 32-channel layers on
+    fmi_conv2d_c32_fwd_bf16, the layers with C and K multiples of 64 on fmi_conv2d_fwd_chan_bf16; anything else is refused"""
+    _chk(x, dtype=BF16)
+    _chk(bias)
+    n, h, w, c = x.shape
+    k = pw.wf.shape[2]
+    d, oh, ow = conv_desc(n, h, w, c, k, pw.kh, pw.kw, 1, pad)
+    wnk = _wnk_of(pw)
+    if c == 32 and k in (32, 64):
+        y = torch.empty((n, oh, ow, k), device=x.device, dtype=BF16)
+        with _prof(f"conv_fwd_bf16|{n}x{h}x{w} {c}->{k} k{pw.kh}s1 c32", 2.0 * n * oh * ow * k * c * pw.kh * pw.kw):
+            _L().conv2d_c32_fwd_bf16(C.byref(d), _p(x), _p(wnk), _p(bias), float(slope), _p(y), _st())
+        return y
+    if c % 64 or k % 64:
+        raise FmiError(f"the bf16 encoder convolutions take 32 -> 32 / 64 channels or C % 64 == 0 and K % 64 == 0, got {c} -> {k}; "
+                       "these run in fp32 only")
+    return conv2d_chan_bf16(x, wnk, pw.kh, pw.kw, 1, pad, bias=bias, slope=None if slope == 1.0 else _slope_vec(x.device, k, slope))
+
+
+def conv2d_plain_bf16(x, pw: PackedWeight, pad):
+    """conv(x) without a bias on a bf16 NHWC map (fmi_conv2d_fwd_bf16), no autograd node"""
+    _chk(x, dtype=BF16)
+    n, h, w, c = x.shape
+    k = pw.wf.shape[2]
+    d, oh, ow = conv_desc(n, h, w, c, k, pw.kh, pw.kw, 1, pad)
+    if not _L().conv2d_bf16_supported(C.byref(d)):
+        raise FmiError(f"the bf16 convolution needs C % 32 == 0 and K % 32 == 0, got {c} -> {k}; these run in fp32 only")
+    y = torch.empty((n, oh, ow, k), device=x.device, dtype=BF16)
+    wnk = _wnk_of(pw)
+    with _prof(f"conv_fwd_bf16|{n}x{h}x{w} {c}->{k} k{pw.kh}s1", 2.0 * n * oh * ow * k * c * pw.kh * pw.kw):
+        _L().conv2d_fwd_bf16(C.byref(d), _p(x), _p(wnk), None, _p(y), None, 0, _st())
+    return y
+
+
+def resblock_tail_bf16(main, shortcut, pool, slope, raw=True, act=True, f32=False):
+    """the ResBlock tail in one pass (fmi_resblock_tail_bf16): v = main + shortcut [, 2 x 2 mean]; returns (bf16 v, bf16 lrelu(v, slope),
+    fp32 v), None for the outputs not asked for"""
+    _chk(main, shortcut, dtype=BF16)
+    n, h, w, c = main.shape
+    if shortcut.shape != main.shape or c % 8 or (pool and (h % 2 or w % 2)):
+        raise FmiError(f"resblock_tail_bf16: main {tuple(main.shape)}, shortcut {tuple(shortcut.shape)}, pool {bool(pool)} (C % 8 == 0, even H and W "
+                       "with pool)")
+    shape = (n, h // 2, w // 2, c) if pool else (n, h, w, c)
+    y_raw = torch.empty(shape, device=main.device, dtype=BF16) if raw else None
+    y_act = torch.empty(shape, device=main.device, dtype=BF16) if act else None
+    y_f32 = torch.empty(shape, device=main.device, dtype=torch.float32) if f32 else None
+    _L().resblock_tail_bf16(_p(main), _p(shortcut), _p(y_raw), _p(y_act), _p(y_f32), n, h, w, c, 1 if pool else 0, float(slope), _st())
+    return y_raw, y_act, y_f32
+
+
+def picnet_stem_tail_bf16(h, img, wb, bias, slope, raw=True, act=True):
+    """the stem's tail in one pass (fmi_picnet_stem_tail_bf16): pool2(h) + bypass1x1(pool2(img)) + bias from the bf16 conv2 output h and
+    the fp32 image; wb fp32 [C][K].  Returns (bf16 v, bf16 lrelu(v, slope))"""
+    _chk(h, dtype=BF16)
+    _chk(img, wb, bias)
+    n, hh, ww, k = h.shape
+    c = img.shape[3]
+    if img.shape[:3] != h.shape[:3] or c > 4 or tuple(wb.shape) != (c, k) or k % 8 or hh % 2 or ww % 2:
+        raise FmiError(f"picnet_stem_tail_bf16: h {tuple(h.shape)}, image {tuple(img.shape)}, bypass weights {tuple(wb.shape)} (C <= 4, K % 8 == 0, "
+                       "even H and W)")
+    shape = (n, hh // 2, ww // 2, k)
+    y_raw = torch.empty(shape, device=h.device, dtype=BF16) if raw else None
+    y_act = torch.empty(shape, device=h.device, dtype=BF16) if act else None
+    _L().picnet_stem_tail_bf16(_p(h), _p(img), _p(wb), _p(bias), _p(y_raw), _p(y_act), n, hh, ww, c, k, float(slope), _st())
+    return y_raw, y_act
+
+
+GUIDED_ATTENTION_BF16_SHAPES = ((32, 128),)  # (d_qk, C) of fmi_guided_attention_fwd_bf16
+
+
+def guided_attention_bf16(q, src, ref, m):
+    """cat[(1 - m) (A ref) + m ref, A src] with A = softmax(q q^T) evaluated once, one launch: q [N,T,D], src / ref [N,T,C] bf16, m fp32
+    [N,T] -> bf16 [N,T,2C]"""
+    _chk(q, src, ref, dtype=BF16)
+    _chk(m)
+    n, t, d = q.shape
+    c = src.shape[2]
+    if t % 128 or (d, c) not in GUIDED_ATTENTION_BF16_SHAPES or ref.shape != src.shape or m.numel() != n * t:
+        raise FmiError(f"the bf16 guided attention needs a token count that is a multiple of 128 and (d_qk, C) = (32, 128), got T = {t}, "
+                       f"(d_qk, C) = ({d}, {c}); these run in fp32 only")
+    out = torch.empty((n, t, 2 * c), device=q.device, dtype=BF16)
+    with _prof(f"attn_guided_fwd_bf16|T{t} d{d} C{c} b{n}", 2.0 * n * t * t * (d + 2 * c)):
+        _L().guided_attention_fwd_bf16(_p(q), _p(src), _p(ref), _p(m), _p(out), n, t, d, c, 0, _st())
+    return out
 
 
 class _Resize(torch.autograd.Function):

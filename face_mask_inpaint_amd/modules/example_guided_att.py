@@ -4,10 +4,11 @@ names (``conv.weight``, ``out_conv.weight/bias``) and forward(src_mask, src_feat
 one softmax pass; the mask blend and the channel concat are one kernel."""
 from __future__ import annotations
 
+import torch
 from torch import nn
 
 from .. import functional as FF
-from ..weights import weight_scope
+from ..weights import packed, weight_scope
 from .pluralistic_model.external_function import run_conv
 
 
@@ -19,10 +20,33 @@ class ExampleGuidedAttention(nn.Module):
         if out_channels is not None:
             self.out_conv = nn.Conv2d(in_channels * 2, out_channels, 1)
 
+    def bf16_unfit(self):
+        """why the bf16 form cannot run this module (None: it can)"""
+        c = self.conv.in_channels
+        if (c // 4, c) not in FF.GUIDED_ATTENTION_BF16_SHAPES:
+            return f"(img_f // 4, img_f) in {set(FF.GUIDED_ATTENTION_BF16_SHAPES)} at the guided attention (got ({c // 4}, {c}))"
+        if self.out_channels is not None:
+            return "a guided attention without out_conv"
+        return None
+
+    def _nhwc_bf16(self, mask_nhw, src, ref):
+        """inference on bf16 feature maps, two launches: the query convolution, then both attentions from one softmax with the mask blend
+        in the epilogue (fmi_guided_attention_fwd_bf16); the result is bf16 [N,H,W,2C]"""
+        n, h, w, c = src.shape
+        unfit = self.bf16_unfit()
+        if unfit or ref.dtype != torch.bfloat16 or (h * w) % 128:
+            raise FF.FmiError(f"the bf16 guided attention needs {unfit or 'bf16 src and ref maps with a token count that is a multiple of 128'}"
+                              f" (got {h} x {w} = {h * w} tokens); these run in fp32 only")
+        q = FF.conv2d_plain_bf16(src, packed(self.conv), 0)
+        out = FF.guided_attention_bf16(q.view(n, h * w, -1), src.view(n, h * w, c), ref.view(n, h * w, c), mask_nhw.contiguous().view(n, h * w))
+        return out.view(n, h, w, 2 * c)
+
     def nhwc(self, mask_nhw, src, ref):
         """mask [N,H,W] (soft), src / ref [N,H,W,C] -> [N,H,W,2C] (or out_channels)."""
         with weight_scope(self):
             n, h, w, c = src.shape
+            if src.dtype == torch.bfloat16:
+                return self._nhwc_bf16(mask_nhw, src, ref)
             q = run_conv(self.conv, src)
             src_att, ref_att = FF.self_attention(q.view(n, h * w, -1), [src.view(n, h * w, c), ref.view(n, h * w, c)])
             out = FF.guide_blend_cat(ref_att.view(n, h, w, c), ref, src_att.view(n, h, w, c), mask_nhw)

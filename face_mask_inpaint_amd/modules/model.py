@@ -16,12 +16,28 @@ def scale_img(img, size):
 
 
 class ReferenceFill(nn.Module):
-    def __init__(self, mask_detector, encoder_params, decoder_params, use_att=True, out_size=(256, 256), decoder_dtype=torch.float32):
+    def __init__(self, mask_detector, encoder_params, decoder_params, use_att=True, out_size=(256, 256), decoder_dtype=torch.float32,
+                 feature_dtype=torch.float32):
         """decoder_dtype=torch.bfloat16 (this build's extra, inference only): ResGenerator's decoder blocks, attention and Output block
-        on the bf16 kernels; both encoders, the guided attention and the latent path stay fp32, and so do all parameters"""
+        on the bf16 kernels.  feature_dtype=torch.bfloat16 (likewise, independent of decoder_dtype): both ResEncoders and the guided
+        attention on the bf16 kernels -- the image enters in fp32, the distribution heads leave in fp32, the attention's output is cast to
+        fp32 once for ``encoded + f``.  The latent path and all parameters stay fp32 either way."""
         super().__init__()
+        if feature_dtype not in (torch.float32, torch.bfloat16):
+            raise FF.FmiError(f"feature_dtype must be torch.float32 or torch.bfloat16, got {feature_dtype}")
+        self.feature_dtype = feature_dtype
         self.mask_detector = mask_detector
         self.encoder_type = encoder_params.pop("type")
+        enc_kw = {}
+        if feature_dtype == torch.bfloat16:
+            why = None
+            if self.encoder_type != "pluralistic":
+                why = f"the pluralistic ResEncoder (got encoder_type {self.encoder_type!r})"
+            elif not use_att:
+                why = "use_att=True (the use_att=False blend has no bf16 kernel)"
+            if why:
+                raise FF.FmiError(f"ReferenceFill(feature_dtype=torch.bfloat16) needs {why}; these run in fp32 only")
+            enc_kw = dict(compute_dtype=feature_dtype)
         if self.encoder_type == "drn":  # model.py:47-59
             from .drn import drn_c_42
 
@@ -30,14 +46,19 @@ class ReferenceFill(nn.Module):
             self.ref_encoder = drn_c_42(pretrained=False, out_map=True)
             self.ref_encoder.fc = torch.nn.Conv2d(self.ref_encoder.out_dim, encoder_params["img_f"], kernel_size=1, stride=1, padding=0, bias=True)
         elif self.encoder_type == "pluralistic":
-            self.src_encoder = network.define_e(**encoder_params, encoder_type="src")
-            self.ref_encoder = network.define_e(**encoder_params, encoder_type="ref")
+            self.src_encoder = network.define_e(**encoder_params, encoder_type="src", **enc_kw)
+            self.ref_encoder = network.define_e(**encoder_params, encoder_type="ref", **enc_kw)
         else:
             raise NotImplementedError
         self.decoder = network.define_g(**decoder_params, compute_dtype=decoder_dtype)
         self.use_att = use_att
         if use_att:
             self.attention = ExampleGuidedAttention(encoder_params["img_f"])
+            if feature_dtype == torch.bfloat16:
+                unfit = self.attention.bf16_unfit()
+                if unfit:
+                    raise FF.FmiError(f"ReferenceFill(feature_dtype=torch.bfloat16) needs {unfit}; these run in fp32 only")
+                object.__setattr__(self.attention.conv, "_fmi_no_w3", True)  # runs on bf16 activations: no fp32 piece images of its pack
         self.pool = nn.AdaptiveAvgPool2d(out_size)
         self._out_size = tuple(out_size)
 
@@ -48,6 +69,19 @@ class ReferenceFill(nn.Module):
         alone; ``no_prior=True`` (what PICNet_inference.py:107 passes for --old_model) decodes without z and rescales the image to
         218 x 178 with scale_img instead of pooling."""
         self.decoder.check_inference(src_image, ref_image)
+        if self.feature_dtype == torch.bfloat16:  # every refusal of the bf16 feature path: before any device call or SpectralNorm step
+            self.src_encoder.check_inference(src_image, ref_image)
+            self.ref_encoder.check_inference(src_image, ref_image)
+            self.src_encoder.check_inference(*self.attention.parameters())
+            if no_prior:
+                raise FF.FmiError("ReferenceFill(feature_dtype=torch.bfloat16) has no no_prior (--old_model) form: its 218 x 178 input does not "
+                                  "divide into the bf16 kernels' tiles; these run in fp32 only")
+            h, w = src_image.shape[2], src_image.shape[3]
+            self.src_encoder.check_extent(h, w)
+            down = self.src_encoder._down
+            if ((h // down) * (w // down)) % 128:
+                raise FF.FmiError(f"the bf16 guided attention needs a token count that is a multiple of 128: a {h // down} x {w // down} feature map "
+                                  f"gives {(h // down) * (w // down)} tokens; these run in fp32 only")
         if src_mask is None:
             if self.mask_detector is None:
                 raise ValueError("src_mask is required when no mask_detector is attached")
@@ -71,6 +105,8 @@ class ReferenceFill(nn.Module):
             m = FF.resize_bilinear(src_mask.contiguous().unsqueeze(-1), fh, fw).view(n, fh, fw)
             if self.use_att:
                 enc = self.attention.nhwc(m, src_feat, ref_feat)
+                if enc.dtype != torch.float32:
+                    enc = enc.float()  # the one cast at the decoder boundary: encoded + f is an fp32 sum
             else:  # (1 - m) * src + m * ref  (model.py:100-101)
                 enc = FF.add(FF.mask_mul(src_feat, m, True), FF.mask_mul(ref_feat, m, False))
             if skip_z:

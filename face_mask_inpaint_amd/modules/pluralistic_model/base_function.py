@@ -154,6 +154,30 @@ class ResBlock(_NhwcBlock):
         self.shortcut = nn.Sequential(self.bypass)
         self._slope = _slope(nonlinearity)
 
+    def bf16_unfit(self):
+        """why the bf16 form cannot run this block (None: it can) -- checked at construction by ResEncoder(compute_dtype=torch.bfloat16)"""
+        if self._norms is not None:
+            return "norm 'none'"
+        for name in ("conv1", "conv2", "bypass"):
+            c = _conv(getattr(self, name))
+            ci, co = c.in_channels, c.out_channels
+            if not ((ci == 32 and co in (32, 64)) or (ci % 64 == 0 and co % 64 == 0)):
+                return f"{name} with 32 -> 32 / 64 channels or widths that are multiples of 64 (got {ci} -> {co})"
+        return None
+
+    def nhwc_bf16(self, x_raw, x_act, raw=True, act=True, f32=False):
+        """inference on bf16 activations (ResEncoder(compute_dtype=torch.bfloat16)), norm 'none': x_raw = the block's input, x_act =
+        lrelu(x_raw) as the previous tail stored it.  conv1 with bias and LeakyReLU in its output stage, the 1x1 bypass, conv2 with its
+        bias, then one tail pass: main + shortcut [2x2 mean] written raw (the next bypass, the feature), activated (the next conv1) and /
+        or in fp32 (the distribution head).  Four launches; returns (raw, act, f32), None where not asked for."""
+        if self._norms is not None:
+            raise FF.FmiError("the bf16 ResBlock is the norm 'none' form (encoder norm 'none'); these run in fp32 only")
+        c1, c2, cb = _conv(self.conv1), _conv(self.conv2), _conv(self.bypass)
+        h = FF.conv2d_enc_bf16(x_act, packed(c1), c1.bias, 1, self._slope)
+        s = FF.conv2d_enc_bf16(x_raw, packed(cb), cb.bias, 0)
+        h = FF.conv2d_enc_bf16(h, packed(c2), c2.bias, 1)
+        return FF.resblock_tail_bf16(h, s, self.sample, self._slope, raw, act, f32)
+
     def nhwc(self, x):
         with weight_scope(self):
             # x has two consumers (the main path and the 1x1 bypass): the bypass reads the pass-through copy the main path's first op
@@ -186,6 +210,15 @@ class ResBlockEncoderOptimized(_NhwcBlock):
         self.model = nn.Sequential(self.conv1, nonlinearity, self.conv2, nn.AvgPool2d(kernel_size=2, stride=2))
         self.shortcut = nn.Sequential(nn.AvgPool2d(kernel_size=2, stride=2), self.bypass)
         self._slope = _slope(nonlinearity)
+
+    def nhwc_bf16(self, img):
+        """inference from the fp32 image to bf16 activations (ResEncoder(compute_dtype=torch.bfloat16)) in three launches: conv1 reads the
+        fp32 image and stores lrelu(conv1 + bias) in bf16, conv2 with its bias, and the tail -- pool2(h) + bypass(pool2(img)) + bias with
+        the three-term 1x1 convolution evaluated in the tail itself.  Returns (raw, lrelu(raw)) for the next block's bypass and conv1."""
+        c1, c2, cb = _conv(self.conv1), _conv(self.conv2), _conv(self.bypass)
+        h = FF.conv2d_thin_in_bf16(img, packed(c1), c1.bias, self._slope)
+        h = FF.conv2d_enc_bf16(h, packed(c2), c2.bias, 1)
+        return FF.picnet_stem_tail_bf16(h, img, packed(cb).wf[0], cb.bias, self._slope)
 
     def nhwc(self, x):
         with weight_scope(self):

@@ -17,8 +17,8 @@ from .external_function import SpectralNorm, run_conv
 
 
 def define_e(encoder_type="src", input_nc=3, ngf=64, z_nc=512, img_f=512, L=6, layers=5, norm="none", activation="ReLU",
-             use_spect=True, use_coord=False, init_type="orthogonal", gpu_ids=[]):
-    net = ResEncoder(input_nc, ngf, z_nc, img_f, L, layers, norm, activation, use_spect, use_coord, encoder_type)
+             use_spect=True, use_coord=False, init_type="orthogonal", gpu_ids=[], compute_dtype=torch.float32):
+    net = ResEncoder(input_nc, ngf, z_nc, img_f, L, layers, norm, activation, use_spect, use_coord, encoder_type, compute_dtype=compute_dtype)
     return init_net(net, init_type, activation, gpu_ids)
 
 
@@ -41,11 +41,19 @@ def define_d(input_nc=3, ndf=64, img_f=512, layers=6, norm="none", activation="L
 
 class ResEncoder(nn.Module):
     """network.py:76-178.  forward(img) -> ([mu, softplus(std)], feature); the fused training path uses
-    ``nhwc_raw`` which returns the un-split distribution head so that split/softplus/rsample happen in one kernel."""
+    ``nhwc_raw`` which returns the un-split distribution head so that split/softplus/rsample happen in one kernel.
+    ``compute_dtype=torch.bfloat16`` (this build's extra, inference only): the stem's first convolution reads the fp32 image, every
+    activation stored after it is bf16, the feature map comes back in bf16 and the un-split distribution head in fp32, written by the last
+    block's tail.  Parameters, state_dict keys and SpectralNorm state are those of the fp32 build."""
 
     def __init__(self, input_nc=3, ngf=64, z_nc=128, img_f=1024, L=6, layers=6, norm="none", activation="ReLU",
-                 use_spect=True, use_coord=False, encoder_type="src"):
+                 use_spect=True, use_coord=False, encoder_type="src", compute_dtype=torch.float32):
         super().__init__()
+        if compute_dtype not in (torch.float32, torch.bfloat16):
+            raise FF.FmiError(f"compute_dtype must be torch.float32 or torch.bfloat16, got {compute_dtype}")
+        self.compute_dtype = compute_dtype
+        if compute_dtype == torch.bfloat16:
+            self._check_bf16(input_nc, ngf, norm)
         self.layers, self.z_nc, self.L = layers, z_nc, L
         self.ecnoder_type = encoder_type  # (sic) attribute name of the reference
         norm_layer = get_norm_layer(norm_type=norm)
@@ -67,10 +75,65 @@ class ResEncoder(nn.Module):
             self.posterior = ResBlock(ngf * mult, 2 * z_nc, ngf * mult, norm_layer, nonlinearity, "none", use_spect, use_coord)
         else:
             raise NotImplementedError(encoder_type)
+        self._down = 2 ** (1 + (layers - 1) // 2)  # the stem and every second encoder block halve the map
+        if compute_dtype == torch.bfloat16:
+            self._check_bf16(input_nc, ngf, norm, blocks=True)
+            for m in self.modules():
+                if isinstance(m, nn.Conv2d):
+                    object.__setattr__(m, "_fmi_no_w3", True)  # these run on bf16 activations: no fp32 piece images of their packs
+
+    def _check_bf16(self, input_nc, ngf, norm, blocks=False):
+        """the shapes the bf16 kernels take, refused at construction (the arguments before any block is built, the blocks' widths after):
+        there is no fp32 detour for a block that does not fit"""
+        why = None
+        if norm != "none":
+            why = f"encoder norm 'none' (got {norm!r})"
+        elif ngf != 32:
+            why = f"ngf == 32, the width of the stem's kernels (got {ngf})"
+        elif input_nc > 4:
+            why = f"an image of at most 4 channels (got {input_nc})"
+        elif blocks:
+            for name, block in self.named_children():
+                unfit = block.bf16_unfit() if isinstance(block, ResBlock) else None
+                if unfit:
+                    why = f"{name}.{unfit}"
+                    break
+        if why:
+            raise FF.FmiError(f"ResEncoder(compute_dtype=torch.bfloat16) needs {why}; these run in fp32 only")
+
+    def check_inference(self, *inputs):
+        """the bf16 encoder has no backward: refuse, before any device work, a call that autograd would record"""
+        if self.compute_dtype == torch.bfloat16 and torch.is_grad_enabled() and (
+                any(t is not None and t.requires_grad for t in inputs) or any(p.requires_grad for p in self.parameters())):
+            raise FF.FmiError("the bf16 encoder (compute_dtype=torch.bfloat16) is inference only -- no bf16 backward exists: call it under "
+                              "torch.no_grad(), or build the encoder with compute_dtype=torch.float32 to train")
+
+    def check_extent(self, h, w):
+        """the bf16 path halves the map log2(_down) times with 2x2 means: refused on the host where H or W does not divide"""
+        if self.compute_dtype == torch.bfloat16 and (h % self._down or w % self._down):
+            raise FF.FmiError(f"the bf16 encoder needs H and W to be multiples of {self._down}, got {h} x {w}; these run in fp32 only")
+
+    def _nhwc_raw_bf16(self, img):
+        raw, act = self.block0.nhwc_bf16(img)
+        for i in range(self.layers - 1):
+            raw, act, _ = getattr(self, "encoder" + str(i)).nhwc_bf16(raw, act)
+        feat = raw
+        if self.ecnoder_type == "src":
+            for i in range(self.L):
+                raw, act, _ = getattr(self, "infer_prior" + str(i)).nhwc_bf16(raw, act)
+            head = self.prior
+        else:
+            head = self.posterior
+        _, _, o = head.nhwc_bf16(raw, act, raw=False, act=False, f32=True)  # the fp32 head leaves the tail itself: no cast afterwards
+        return o, feat
 
     def nhwc_raw(self, img):
         """returns (o [N,h,w,2*z_nc] = un-split (mu, raw std), feature [N,h,w,C])"""
+        self.check_inference(img)
+        self.check_extent(img.shape[1], img.shape[2])
         with weight_scope(self):
+            if self.compute_dtype == torch.bfloat16:
+                return self._nhwc_raw_bf16(img)
             out = self.block0.nhwc(img)
             for i in range(self.layers - 1):
                 out = getattr(self, "encoder" + str(i)).nhwc(out)

@@ -834,6 +834,47 @@ int fmi_irse_tail_bf16(const uint16_t* r, const float* gate, const uint16_t* sc,
  * BatchNorm (helpers.py:86 / :108) evaluated on the fp32 x.  C % 8 == 0. */
 int fmi_irse_stem_bf16(const float* x, const float* scale, const float* shift, uint16_t* y, uint16_t* z, int64_t rows, int C, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Inference form of the PICNet encoders and the guided attention on bf16 NHWC activations (ResEncoder(compute_dtype=bf16),
+ * ExampleGuidedAttention on bf16 maps), csrc/picnet_enc_bf16.hip and csrc/attention_bf16.hip.  Replaces base_function.py:242-305
+ * (ResBlock with norm 'none', ResBlockEncoderOptimized) and example_guided_att.py:21-41 of the reference.  fp32 parameters and
+ * accumulation, one round-to-nearest-even per stored bf16 value, no atomics: every result is bit-reproducible.  The layers with C and K
+ * multiples of 64 run on fmi_conv2d_fwd_chan_bf16 (scale NULL, slope a [K] vector of 0.1 for conv1).  A ResBlock is conv1, bypass,
+ * conv2, tail = 4 launches, the stem 3, the guided attention 2.  Every entry refuses bad arguments (FMI_ERR_BAD_ARG: NULL pointers,
+ * non-positive extents, a descriptor whose OH / OW do not follow from it) and unsupported shapes or misaligned pointers
+ * (FMI_ERR_UNSUPPORTED) before any HIP call.
+ * ---------------------------------------------------------------------- */
+/* the stem's conv1 (base_function.py:278, :283): y = lrelu(conv3x3(x) + bias, slope), zero padding 1, stride 1.  x fp32 [N,H,W,C <= 4],
+ * wf fp32 [9][C][K] (the fp32 forward pack), bias fp32 [K] or NULL, y bf16 [N,H,W,K], K in {32, 64}; fp32 FMAs.  The LeakyReLU of
+ * model[1] lives here because conv2 is the only consumer.  y 16-byte aligned. */
+int fmi_conv2d_thin_in_fwd_bf16(const fmi_conv_desc* d, const float* x, const float* wf, const float* bias, float slope, uint16_t* y,
+                                void* stream);
+/* the 32-channel layers (base_function.py:254-256 at ngf 32, :279): y = lrelu(conv(x) + bias, slope); slope = 1 is the plain convolution.
+ * x bf16 [N,H,W,32], wnk bf16 [K][kh*kw][32] (fmi_pack_weight_bf16), bias fp32 [K] or NULL, y bf16 [N,H,W,K].  C == 32, K in {32, 64},
+ * 3x3 pad 1 or 1x1 pad 0, stride 1, dense pixel pitches; 16-byte aligned pointers.  bf16 MFMA, fp32 accumulation; the whole weight set
+ * stays in registers for the launch and the map is read once. */
+int fmi_conv2d_c32_fwd_bf16(const fmi_conv_desc* d, const uint16_t* x, const uint16_t* wnk, const float* bias, float slope, uint16_t* y,
+                            void* stream);
+/* the block tail (base_function.py:266-271): v = main + shortcut in fp32, with pool = 1 the 2x2 mean of that sum (pool(a) + pool(b) =
+ * pool(a + b)).  main / shortcut bf16 [N,H,W,C]; outputs [N,H',W',C] with H' = H / 2 under pool: y_raw = bf16(v), y_act =
+ * bf16(lrelu(v, slope)), y_f32 = v.  A NULL output is skipped; all three NULL: FMI_ERR_BAD_ARG.  C % 8 == 0, H and W even with pool. */
+int fmi_resblock_tail_bf16(const uint16_t* main_, const uint16_t* shortcut, uint16_t* y_raw, uint16_t* y_act, float* y_f32, int N, int H, int W,
+                           int C, int pool, float slope, void* stream);
+/* the stem's tail (base_function.py:296-305): v = pool2(h) + bypass1x1(pool2(img)) + bias.  h bf16 [N,H,W,K] (conv2's output), img fp32
+ * [N,H,W,C <= 4], wb fp32 [C][K], bias fp32 [K] or NULL; y_raw / y_act bf16 [N,H/2,W/2,K] as above (one may be NULL).  K % 8 == 0, H
+ * and W even. */
+int fmi_picnet_stem_tail_bf16(const uint16_t* h, const float* img, const float* wb, const float* bias, uint16_t* y_raw, uint16_t* y_act, int N,
+                              int H, int W, int C, int K, float slope, void* stream);
+/* ExampleGuidedAttention's two attentions and its blend in one launch (example_guided_att.py:21-41), A = softmax_j(q_i . q_j) evaluated
+ * once:  out[..., :C] = (1 - m) (A ref) + m ref,  out[..., C:] = A src.  q [N,T,D], src / ref [N,T,C], out [N,T,2C] bf16; mask fp32 [N,T]
+ * (the soft mask after the bilinear resize).  The blend is evaluated in fp32 before the one rounding; m == 1 returns ref bit for bit.
+ * The kernel is fmi_attention_fwd_bf16's with a V tile [ref | src]; same lazy reference maximum.  Supported: T % 128 == 0, (D, C) =
+ * (32, 128), N <= 65535; waves as there, 0 = fmi_guided_attention_fwd_bf16_waves(N, T) (8 if T % 256 == 0 and (T/256) N >= 256, else
+ * 4).  NULL pointers or q / src / ref / out off 16-byte alignment: FMI_ERR_BAD_ARG. */
+int fmi_guided_attention_fwd_bf16_waves(int N, int T);
+int fmi_guided_attention_fwd_bf16(const uint16_t* q, const uint16_t* src, const uint16_t* ref, const float* mask, uint16_t* out, int N, int T,
+                                  int D, int C, int waves, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
