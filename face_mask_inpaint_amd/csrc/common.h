@@ -77,6 +77,9 @@ static inline int fmi_launch_status() {
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// thinin.hip: the streaming kernels behind fmi_conv2d_thin_input_dgrad_f32 (thinconv.hip), FMI_ERR_UNSUPPORTED for shapes they leave alone
+int fmi_thin_in_dgrad_try(const fmi_conv_desc* d, const float* dy, const float* wt, float* dx, void* stream);
+
 // grid size for grid-stride bandwidth kernels: enough workgroups to fill 256 CUs x 8, capped
 static inline int fmi_bw_grid(int64_t work_items, int block) {
   int64_t g = ceil_div64(work_items, block);

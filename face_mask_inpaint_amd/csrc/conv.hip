@@ -182,6 +182,10 @@ extern "C" int fmi_conv2d_fwd_f32(const fmi_conv_desc* d, const float* x, const 
 #ifndef FMI_HOST_EMU
   if (batch_w == 1 && fmi_conv2d_thin_supported(d) && aligned16(x))
     return finish(fmi_conv2d_thin_fwd_f32(d, x, wf, bias, residual, y, act, stream));
+  // thin INPUT (C <= 4: the image-facing first layers), 3x3 on a large map: streaming FMA kernel (thinin.hip).  The 1x1 form is a 9 - 13 us
+  // launch either way and did not clear the keep-only-if-faster rule (profiles/thin_in.txt): it stays on the generic path
+  if (batch_w == 1 && d->kh == 3 && fmi_conv2d_thin_in_routed(d) && aligned16(y) && aligned16(residual))
+    return finish(fmi_conv2d_thin_in_fwd_f32(d, x, wf, bias, residual, y, act, stream));
 #endif
   const ConvGeom g = fwd_geom(d, x, batch_w > 1 ? 1 : d->N);
   // bf16 piece images of the weights (fmi_weight_prepare_f32 writes them): [3][taps][C / 8][K][8]
@@ -211,7 +215,8 @@ static int dgrad_impl(const fmi_conv_desc* d, const float* dy, const float* wt, 
 #ifndef FMI_HOST_EMU
   if (batch_w == 1 && !bias && !residual && !mask && fmi_conv2d_thin_supported(d) && aligned16(dx))
     return finish(fmi_conv2d_thin_dgrad_f32(d, dy, wt, dx, stream));
-  if (batch_w == 1 && !bias && !residual && !mask && d->C <= 4 && d->x_cstride == d->C) {  // thin INPUT: VGG16's first layer
+  // thin INPUT: VGG16's first layer (the entry's 1x1 form is not routed here: see the forward)
+  if (batch_w == 1 && !bias && !residual && !mask && d->C <= 4 && d->x_cstride == d->C && d->kh == 3) {
     const int rc_thin = fmi_conv2d_thin_input_dgrad_f32(d, dy, wt, dx, stream);
     if (rc_thin != FMI_ERR_UNSUPPORTED) return finish(rc_thin);
   }

@@ -1148,9 +1148,15 @@ extern "C" int fmi_conv2d_thin_lrelu_dgrad_f32(const fmi_conv_desc* d, const flo
 }
 
 /* Adjoint of a THIN-INPUT convolution (C_in <= 4, e.g. VGG16's first layer 3 -> 64, whose input gradient d loss / d image the
- * generator needs): dx[N,H,W,C<=4] = thin-output convolution of dy[N,H,W,K] with wt[tap][K][C] and flipped taps (zero padding). */
+ * generator needs): dx[N,H,W,C<=4] = thin-output convolution of dy[N,H,W,K] with wt[tap][K][C] and flipped taps (zero padding).
+ * Dense tensors with K = 8 .. 64 on maps of at least 131072 pixels, and the 1x1 form at any size, run on the streaming kernels of
+ * thinin.hip; everything else on the 4x4x1-MFMA form here. */
 extern "C" int fmi_conv2d_thin_input_dgrad_f32(const fmi_conv_desc* d, const float* dy, const float* wt, float* dx, void* stream) {
   if (!d || !dy || !wt || !dx) return FMI_ERR_BAD_ARG;
+  {  // dense layers with K = 8 .. 64, 3x3 on a large map or 1x1: the streaming FMA kernels of thinin.hip
+    const int rc = fmi_thin_in_dgrad_try(d, dy, wt, dx, stream);
+    if (rc != FMI_ERR_UNSUPPORTED) return rc;
+  }
   const int cg = d->K / 4;
   if (d->dil > 1 || d->C < 1 || d->C > 4 || d->kh != 3 || d->kw != 3 || d->stride != 1 || d->pad != 1 || d->pad_mode != 0 || d->K % 4 != 0 || cg < 1 ||
       cg > 16 || (cg & (cg - 1)) != 0 || d->y_cstride % 4 != 0 || d->H < 3 || d->W < 3 || d->OH != d->H || d->OW != d->W ||

@@ -429,25 +429,35 @@ class _Conv2d(torch.autograd.Function):
             gx = gpass
         if ctx.needs_input_grad[1]:
             d, _, _ = conv_desc(n, h, w, c, k, kh, kw, stride, pad, pad_mode, dil=dil)
-            gwf = _zeros_like(wf)
             want_gb = ctx.has[0] and ctx.needs_input_grad[2]
-            # both operands as piece images (x's from the forward, dy's shared with the adjoint above): the weight gradient runs without
-            # split arithmetic; the bias gradient then takes its own pass
-            if ctx.x3 is not None and pad_mode == 0 and c % 32 == 0 and k % 16 == 0 and p3_wanted(gy.numel() // k, c, k, kh * kw):
-                gy3 = p3_of(gy, colsum=gb_of_split)
-                if gy3 is not None:
-                    d.w3 = None
-                    d.x3, d.y3 = ctx.x3.data_ptr(), gy3.data_ptr()
-                    want_gb_fused = False
+            if lib.conv2d_thin_in_routed(C.byref(d)) and gy.data_ptr() % 16 == 0:
+                # thin input (C <= 4) on a large map: dW and dbias from one read of dy, written (not accumulated) through a fixed-order row sum
+                gwf = torch.empty(wf.shape, device=x.device, dtype=torch.float32)
+                if want_gb:
+                    gb = torch.empty(k, device=x.device, dtype=torch.float32)
+                ws_bytes = lib.conv2d_thin_in_wgrad_ws_bytes(C.byref(d))
+                ws = _parts_ws(x.device, ws_bytes // 4)
+                with _prof(f"conv_wgrad|{n}x{h}x{w} {c}->{k} k{kh}s{stride}", 2.0 * gy.numel() * c * kh * kw):
+                    lib.conv2d_thin_in_wgrad_f32(C.byref(d), _p(x), _p(gy), _p(gwf), _p(gb), _p(ws), ws_bytes, _st())
+            else:
+                gwf = _zeros_like(wf)
+                # both operands as piece images (x's from the forward, dy's shared with the adjoint above): the weight gradient runs without
+                # split arithmetic; the bias gradient then takes its own pass
+                if ctx.x3 is not None and pad_mode == 0 and c % 32 == 0 and k % 16 == 0 and p3_wanted(gy.numel() // k, c, k, kh * kw):
+                    gy3 = p3_of(gy, colsum=gb_of_split)
+                    if gy3 is not None:
+                        d.w3 = None
+                        d.x3, d.y3 = ctx.x3.data_ptr(), gy3.data_ptr()
+                        want_gb_fused = False
+                    else:
+                        want_gb_fused = want_gb
                 else:
                     want_gb_fused = want_gb
-            else:
-                want_gb_fused = want_gb
-            fuse = want_gb_fused and (kh * kw * c) % 4 == 0
-            if fuse:
-                gb = _zeros(k, x.device, torch.float32)
-            with _prof(f"conv_wgrad|{n}x{h}x{w} {c}->{k} k{kh}s{stride}", 2.0 * gy.numel() * c * kh * kw):
-                lib.conv2d_wgrad_f32(C.byref(d), _p(x), _p(gy), _p(gwf), _p(gb) if fuse else None, 1, 0, _st())
+                fuse = want_gb_fused and (kh * kw * c) % 4 == 0
+                if fuse:
+                    gb = _zeros(k, x.device, torch.float32)
+                with _prof(f"conv_wgrad|{n}x{h}x{w} {c}->{k} k{kh}s{stride}", 2.0 * gy.numel() * c * kh * kw):
+                    lib.conv2d_wgrad_f32(C.byref(d), _p(x), _p(gy), _p(gwf), _p(gb) if fuse else None, 1, 0, _st())
         if ctx.has[0] and ctx.needs_input_grad[2] and gb is None:
             if gb_of_split:  # summed by the pass that cut dy's pieces
                 gb = gb_of_split[0]

@@ -210,8 +210,36 @@ int fmi_conv2d_thin_lrelu_bwd_ws_bytes(const fmi_conv_desc* d);
 int fmi_conv2d_thin_lrelu_bwd_f32(const fmi_conv_desc* d, const float* x, float in_slope, const float* dy, const float* y, const float* wt,
                                   float* dx, float* dwf, float* dbias, void* ws, int64_t ws_bytes, void* stream);
 /* adjoint of a thin-INPUT 3x3 convolution (C <= 4, K = 4..64 a power of two, stride 1, pad 1, zeros): dx = thin-output convolution of
- * dy with flipped taps -- the input gradient of VGG16's first layer (loss.py:45-65); fmi_conv2d_dgrad_f32 routes to it by itself */
+ * dy with flipped taps -- the input gradient of VGG16's first layer (loss.py:45-65); fmi_conv2d_dgrad_f32 routes to it by itself.
+ * Dense tensors (x_cstride == C, y_cstride == K) with K = 8 .. 64 run on the streaming kernel of csrc/thinin.hip (dy rows staged once in
+ * LDS, plain fp32 FMAs) from 131072 pixels on (fmi_conv2d_thin_in_routed) and, at any size, in the 1x1 pad-0 form, which no other kernel
+ * behind this entry takes; the results of every other shape are unchanged. */
 int fmi_conv2d_thin_input_dgrad_f32(const fmi_conv_desc* d, const float* dy, const float* wt, float* dx, void* stream);
+/* Thin-INPUT convolutions (csrc/thinin.hip): 1 <= C <= 4 with x dense (x_cstride == C), K % 8 == 0, 8 <= K <= 64 with y dense
+ * (y_cstride == K), 3x3 pad 1 or 1x1 pad 0, stride 1, no dilation, zero padding, OH == H, OW == W, N*H*W < 2^31 -- the image-facing first
+ * layers of the encoders, the discriminator and VGG16.  fmi_conv2d_thin_in_supported says 1 for this class (0 for NULL): what the two
+ * entries below accept.  fmi_conv2d_thin_in_routed says 1 for the part of it that the library's own dispatch (fmi_conv2d_fwd_f32,
+ * fmi_conv2d_dgrad_f32; both for the 3x3 form only) and functional._Conv2d.backward (weight gradient, 3x3 and 1x1) send to these
+ * kernels: N*H*W >= 131072 pixels, the smallest map at which they were timed against the generic path; smaller maps are launch-bound
+ * and keep the path (and the bits) they had, and so do the 1x1 forward and input gradient, 9 - 13 us launches either way.  Streaming
+ * kernels on plain fp32 FMAs.  Any other geometry: FMI_ERR_UNSUPPORTED; NULL descriptor or required pointer: FMI_ERR_BAD_ARG; both
+ * before anything is launched.
+ *   fwd  : y = act(conv(x, wf) + bias + residual), wf[taps][C][K], bias / residual may be NULL, act = 0 none / 1 tanh / 2 relu.  y and
+ *          residual 16-byte aligned (else FMI_ERR_UNSUPPORTED).  fmi_conv2d_fwd_f32 routes to it by itself (routed 3x3 shapes).
+ *   wgrad: dwf[taps][C][K] = x^T dy and, when dbias != NULL, dbias[K] = sum dy, both from ONE read of dy.  Both are WRITTEN, not
+ *          accumulated: nothing has to be zeroed.  Persistent workgroups store one row of partial sums each into ws and a finishing launch
+ *          adds the rows in a fixed order: no atomics, bit-identical from run to run and in either mode.  dy 16-byte aligned (else
+ *          FMI_ERR_UNSUPPORTED).  ws: device memory, 16-byte aligned, fmi_conv2d_thin_in_wgrad_ws_bytes(d) =
+ *            min(ceil(N * H * ceil(W / 4) / (256 / P)), 1024) * (taps*C*K + K) * 4 bytes, P = K / 4 rounded up to a power of two
+ *          (0 for a shape outside the class); contents irrelevant.  A ws of fewer rows only lowers the number of workgroups; shorter
+ *          than one row, misaligned or NULL: FMI_ERR_BAD_ARG.  fmi_conv2d_wgrad_f32 keeps the generic path for these shapes. */
+int fmi_conv2d_thin_in_supported(const fmi_conv_desc* d);
+int fmi_conv2d_thin_in_routed(const fmi_conv_desc* d);
+int fmi_conv2d_thin_in_fwd_f32(const fmi_conv_desc* d, const float* x, const float* wf, const float* bias, const float* residual, float* y,
+                               int act, void* stream);
+int fmi_conv2d_thin_in_wgrad_ws_bytes(const fmi_conv_desc* d);
+int fmi_conv2d_thin_in_wgrad_f32(const fmi_conv_desc* d, const float* x, const float* dy, float* dwf, float* dbias, void* ws,
+                                 int64_t ws_bytes, void* stream);
 /* ------------------------------------------------------------------------
  * bf16 convolution family (fp32 accumulate) for the StyleGAN2 decoder of the pSp path in configs C3 / C5
  * (stylegan2/model.py:241-279: the grouped conv2d / conv_transpose2d of ModulatedConv2d.forward).  Activations are bf16 NHWC
