@@ -83,6 +83,8 @@ SIGNATURES = {
     "fmi_se_gate_f32": [vp, i32, i64, f32, vp, vp, vp, i32, i32, vp],
     "fmi_irse_tail_bf16": [vp] * 8 + [i32] * 7 + [vp],
     "fmi_irse_stem_bf16": [vp] * 5 + [i64, i32, vp],
+    "fmi_conv2d_grouped_fwd_bf16": [PD, i32, i64, vp, vp, vp, f32, vp, vp, vp],
+    "fmi_fpn_merge_bf16": [vp] * 4 + [i32] * 6 + [vp],
     "fmi_conv2d_thin_in_fwd_bf16": [PD, vp, vp, vp, f32, vp, vp],
     "fmi_conv2d_c32_fwd_bf16": [PD, vp, vp, vp, f32, vp, vp],
     "fmi_resblock_tail_bf16": [vp] * 5 + [i32] * 5 + [f32, vp],

@@ -147,6 +147,15 @@ struct ConvSetB {
 // the workspace: [block][0] = its rows of the sample its first row lies in, [block][1] = its rows of the next sample.  Every row of the
 // workspace is written by exactly one wave, in full: no initialisation, no atomics, the same bits every run.
 struct EpNoneB {};
+// EpGroupB: G convolutions of one launch (the map2style heads of one pyramid level, psp_encoders.py:13-37 of the reference).  The group is
+// the grid's y index -- a launch of this stage has ONE phase, set.ph[0], shared by all groups -- and offsets x, the weights, the bias and
+// y; set.N is the number of output columns of one group.  v = acc + bias[g][k], y = v > 0 ? v : slope * v, one rounding to bf16.
+struct EpGroupB {
+  const float* bias;  // [G][Nout] or null (= 0)
+  float slope;
+  int64_t x_off;      // elements between the first channels of consecutive groups inside a pixel of x (0: one shared map)
+  int64_t w_off;      // elements between the weight packs of consecutive groups
+};
 struct EpChanB {
   const float* scale;  // [Nout] or null (= 1)
   const float* bias;   // [Nout] or null (= 0)
@@ -159,11 +168,26 @@ __global__ void __launch_bounds__(T::NT) conv_bf16_kernel(ConvSetB set, CH ch) {
   const float* const zchunk = fmi_zero_chunk_ptr();  // the zero chunk's address: read from the GOT ONCE (see fmi_zero_chunk_ptr)
   constexpr int BM = T::BM, BN = T::BN, NT = T::NT;
   const int lid = xcd_remap(blockIdx.x, gridDim.x);
-  if (lid >= set.ph[blockIdx.y].tiles) return;  // whole workgroup
-  const ConvKB la = set.ph[blockIdx.y].la;
-  const ConvWKB lb = set.ph[blockIdx.y].lb;
-  const ConvEpB ep = set.ph[blockIdx.y].ep;
-  const int M = set.ph[blockIdx.y].M, K = set.ph[blockIdx.y].K, N = set.N, tiles_n = set.tiles_n;
+  constexpr bool GRP = std::is_same<CH, EpGroupB>::value;
+  const unsigned phi = GRP ? 0u : blockIdx.y;  // unsigned as before: the other stages compile to the code they had
+  const int grp = GRP ? (int)blockIdx.y : 0;
+  if (lid >= set.ph[phi].tiles) return;  // whole workgroup
+  const ConvKB la = [&] {
+    ConvKB a = set.ph[phi].la;
+    if constexpr (GRP) a.p += (int64_t)grp * ch.x_off;
+    return a;
+  }();
+  const ConvWKB lb = [&] {
+    ConvWKB b = set.ph[phi].lb;
+    if constexpr (GRP) b.p += (int64_t)grp * ch.w_off;
+    return b;
+  }();
+  const ConvEpB ep = [&] {
+    ConvEpB e = set.ph[phi].ep;
+    if constexpr (GRP) e.y += (int64_t)grp * set.N;
+    return e;
+  }();
+  const int M = set.ph[phi].M, K = set.ph[phi].K, N = set.N, tiles_n = set.tiles_n;
   constexpr int CPR = BK / 8;            // 16-byte chunks per image row
   constexpr int NLA = (BM * CPR + NT - 1) / NT, NLB = (BN * CPR + NT - 1) / NT;
   constexpr int STAGE = (BM + BN) * BK;  // bf16 elements
@@ -299,6 +323,37 @@ __global__ void __launch_bounds__(T::NT) conv_bf16_kernel(ConvSetB set, CH ch) {
 
   // epilogue: 4 x 4 transpose inside each quad of lanes -> one row, four consecutive columns per lane, 8-byte bf16 stores
   const int c = l31 & 3, colq = l31 & ~3;
+  if constexpr (GRP) {  // N % 4 == 0, 8-byte aligned rows of y, 16-byte aligned bias (the host checks)
+    const float* const bias = ch.bias ? ch.bias + (int64_t)grp * N : nullptr;
+#pragma unroll
+    for (int i = 0; i < T::TM; ++i) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int row = m0 + wm + i * 32 + 8 * g + 4 * lh + c;
+        int n_s = 0;
+        const int64_t off = row < M ? ep.row_off(row, n_s) : 0;
+#pragma unroll
+        for (int j = 0; j < T::TN; ++j) {
+          float a[4] = {acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
+          quad_transpose(a, c);
+          const int col = n0 + wn + j * 32 + colq;
+          if (row >= M || col >= N) continue;
+          const float4 b = bias ? *reinterpret_cast<const float4*>(bias + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+          const float bv[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float v = a[e] + bv[e];
+            a[e] = v > 0.f ? v : ch.slope * v;
+          }
+          uint2 v;
+          v.x = bf_pack2(a[0], a[1]);
+          v.y = bf_pack2(a[2], a[3]);
+          *reinterpret_cast<uint2*>(ep.y + off + col) = v;
+        }
+      }
+    }
+    return;
+  }
   if constexpr (std::is_same<CH, EpChanB>::value) {
     static_assert(T::TM == 2, "a wave owns one 64-row block of the column-sum workspace");
     // the lane's columns are the same for all of its rows: the three per-column vectors once per 32-column group
@@ -628,6 +683,49 @@ extern "C" int fmi_conv2d_fwd_chan_bf16(const fmi_conv_desc* d, const uint16_t* 
   set.ph[0].tiles = (int)tiles;
   if (bn == 64) hipLaunchKernelGGL((conv_bf16_kernel<TB128x64, 64, 2, EpChanB>), dim3((unsigned)tiles, 1, 1), dim3(TB128x64::NT), 0, st, set, ch);
   else hipLaunchKernelGGL((conv_bf16_kernel<TB128x128, 64, 2, EpChanB>), dim3((unsigned)tiles, 1, 1), dim3(TB128x128::NT), 0, st, set, ch);
+  return fmi_launch_status();
+}
+/* The tile path of fmi_conv2d_grouped_fwd_bf16 (style_heads_bf16.hip, which has checked every argument): G convolutions as one launch
+ * of conv_bf16_kernel with the grouped output stage, grid = (tiles of one group, G).  d->C / d->K are per group; x_off / w_off are the
+ * element offsets between consecutive groups inside a pixel of x and between their weight packs.  A shared map (x_off == 0) arrives here
+ * as ONE group of G*K columns: the stacked packs are its [G*K][taps][C] weight as they lie.  The tile follows launch_conv_bf16's measured
+ * table, with the groups counted into the workgroups of a candidate. */
+int fmi_conv_bf16_grouped_tiles(const fmi_conv_desc* d, int G, int64_t x_off, int64_t w_off, const uint16_t* x, const uint16_t* wnk,
+                                const float* bias, float slope, uint16_t* y, void* stream) {
+  ConvGeom g{};
+  g.N = d->N; g.IH = d->H; g.IW = d->W; g.C = d->C; g.cstride = d->x_cstride;
+  g.GH = d->OH; g.GW = d->OW; g.S = d->stride;
+  g.nty = d->kh; g.ntx = d->kw; g.dy0 = -d->pad; g.dx0 = -d->pad; g.ystep = 1; g.xstep = 1;
+  g.kh0 = 0; g.kw0 = 0; g.khstep = 1; g.kwstep = 1; g.kw = d->kw;
+  g.pad_mode = 0; g.vec = 6;
+  g.dGW = make_fastdiv(g.GW); g.dG = make_fastdiv(g.GH * g.GW); g.dC = make_fastdiv(g.nty * g.ntx); g.dntx = make_fastdiv(g.ntx);
+  g.img_bs = 0;
+  ConvSetB set{};
+  set.ph[0].la = ConvKB{x, g};
+  set.ph[0].lb = ConvWKB{wnk, g, d->K, d->kh * d->kw};
+  set.ph[0].ep = ConvEpB{y, nullptr, d->OH, d->OW, 1, 0, 0, d->OH, d->OW, d->y_cstride, d->K, g.dGW, g.dG, 1};
+  set.ph[0].M = g.Mdim();
+  set.ph[0].K = g.Kdim();
+  set.N = d->K;
+  set.ksplit = 1;
+  set.ws = nullptr;
+  const EpGroupB ch{bias, slope, x_off, w_off};
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t M = set.ph[0].M;
+  auto wgs = [&](int bm, int bn) { return ceil_div64(M, bm) * ceil_div64(d->K, bn) * G; };
+#define FMI_LAUNCH_G(TILE)                                                                                                             \
+  do {                                                                                                                                 \
+    const int64_t tn = ceil_div64(d->K, TILE::BN), tiles = ceil_div64(M, TILE::BM) * tn;                                               \
+    if (tiles > 0x7fffffffLL) return FMI_ERR_UNSUPPORTED;                                                                              \
+    set.tiles_n = (int)tn;                                                                                                             \
+    set.ph[0].tiles = (int)tiles;                                                                                                      \
+    hipLaunchKernelGGL((conv_bf16_kernel<TILE, 64, 2, EpGroupB>), dim3((unsigned)tiles, (unsigned)G, 1), dim3(TILE::NT), 0, st, set, ch); \
+  } while (0)
+  if (d->K > 128 && wgs(256, 256) >= 200) FMI_LAUNCH_G(TB256x256);
+  else if (d->K > 64 && wgs(128, 128) >= 512) FMI_LAUNCH_G(TB128x128);
+  else if (d->K > 64 && wgs(64, 128) >= 256) FMI_LAUNCH_G(TB64x128);
+  else FMI_LAUNCH_G(TB64x64);
+#undef FMI_LAUNCH_G
   return fmi_launch_status();
 }
 /* dx = adjoint of the convolution described by d applied to dy; wck = weights packed [C][kh*kw][K] */

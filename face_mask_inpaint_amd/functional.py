@@ -1518,6 +1518,52 @@ def irse_stem_bf16(x, scale, shift):
     return y, z
 
 
+# ---- bf16 map2style heads of the pSp encoder for inference (GradualStyleEncoder(style_heads_eval_dtype='bf16')): the heads of one pyramid
+# level run together, one launch per layer; no autograd nodes -- the caller has refused grad mode. ----
+STYLE_SKINNY_ROWS = 128  # FMI_STYLE_SKINNY_ROWS (include/fmi_hip.h)
+
+
+def conv2d_grouped_bf16(x, wnk, bias, kh, stride, pad, slope=1.0, shared=False, out=None, first=0):
+    """G convolutions in one launch (fmi_conv2d_grouped_fwd_bf16): lrelu(conv_g(x_g) + bias[g], slope) for g < G.  wnk bf16
+    [G][K][kh kh][C], bias fp32 [G][K] or None.  ``shared``: x is [N,H,W,C] and every group reads it; otherwise x is [N,H,W,G*C] and
+    group g reads its C channels.  Returns bf16 [N,OH,OW,G*K] -- or, with ``out`` (fp32 [N, slots, K], a 1x1 convolution of a 1x1 map:
+    the heads' EqualLinear), writes group g into out[:, first + g] and returns ``out``."""
+    _chk(x, wnk, dtype=BF16)
+    _chk(bias, out)
+    n, h, w, cx = x.shape
+    g, k, taps, c = wnk.shape
+    if taps != kh * kh or cx != (c if shared else g * c) or (bias is not None and tuple(bias.shape) != (g, k)):
+        raise FmiError(f"conv2d_grouped_bf16: x {tuple(x.shape)}, weights {tuple(wnk.shape)}, bias {None if bias is None else tuple(bias.shape)}, "
+                       f"k{kh}, shared={shared}")
+    d, oh, ow = conv_desc(n, h, w, c, k, kh, kh, stride, pad, x_cs=cx, y_cs=g * k)
+    if out is not None:
+        if out.dim() != 3 or out.shape[0] != n * oh * ow or out.shape[2] != k or first < 0 or first + g > out.shape[1]:
+            raise FmiError(f"conv2d_grouped_bf16: {g} groups of {n * oh * ow} x {k} do not fit slots {first}.. of out {tuple(out.shape)}")
+        d.y_cstride = out.shape[1] * k
+        y16, y32 = None, _p(out, first * k)
+    else:
+        y = torch.empty((n, oh, ow, g * k), device=x.device, dtype=BF16)
+        y16, y32 = _p(y), None
+    with _prof(f"conv_grouped_bf16|{n}x{h}x{w} {g}x({c}->{k}) k{kh}s{stride}" + (" shared" if shared else ""), 2.0 * n * oh * ow * g * k * c * kh * kh):
+        _L().conv2d_grouped_fwd_bf16(C.byref(d), g, 0 if shared else c, _p(x), _p(wnk), _p(bias), float(slope), y16, y32, _st())
+    return out if out is not None else y
+
+
+def fpn_merge_bf16(lateral, coarse=None, want_f32=True):
+    """p = bilinear(coarse, align_corners=True, to lateral's size) + lateral in one pass (fmi_fpn_merge_bf16); coarse None: p = lateral.
+    Returns (p fp32 or None without ``want_f32``, p bf16); fp32 NHWC inputs."""
+    _chk(lateral, coarse)
+    n, h, w, c = lateral.shape
+    if coarse is not None and (coarse.shape[0] != n or coarse.shape[3] != c):
+        raise FmiError(f"fpn_merge_bf16: lateral {tuple(lateral.shape)}, coarse {tuple(coarse.shape)}")
+    ch, cw = (coarse.shape[1], coarse.shape[2]) if coarse is not None else (0, 0)
+    p32 = torch.empty_like(lateral) if want_f32 else None
+    p16 = torch.empty(lateral.shape, device=lateral.device, dtype=BF16)
+    with _prof(f"fpn_merge_bf16|{n}x{h}x{w}x{c}", 9.0 * lateral.numel() if coarse is not None else 0.0):
+        _L().fpn_merge_bf16(_p(lateral), _p(coarse), _p(p32), _p(p16), n, h, w, ch, cw, c, _st())
+    return p32, p16
+
+
 # ---- bf16 PICNet encoders and guided attention (ResEncoder(compute_dtype=torch.bfloat16), ExampleGuidedAttention on bf16 maps):
 # inference forms, no autograd nodes -- the caller (ResEncoder.check_inference) has refused grad mode.  Activations bf16 NHWC, the image
 # and the distribution heads fp32, parameters fp32; the bf16 weight packs are cut from the fp32 packs that weight_scope prepared. ----

@@ -9,7 +9,7 @@ from torch import nn
 from torch.nn import BatchNorm2d, Conv2d, Module, PReLU, Sequential
 
 from .... import functional as FF
-from ....weights import weight_scope
+from ....weights import packed, weight_scope
 from ...example_guided_att import ExampleGuidedAttention
 from ...pluralistic_model.external_function import run_conv
 from ..stylegan2.model import EqualLinear
@@ -37,6 +37,54 @@ class GradualStyleBlock(Module):
 
     def forward(self, x):
         return self.nhwc(FF.to_nhwc(x))
+
+
+def _level_packs(heads, holder=None, key=None):
+    """The operands of ``style_level_bf16`` for the heads of one level: per layer the stacked bf16 weights [G][K][9][C] (concatenated from
+    the per-convolution packs, helpers._wnk) and fp32 biases [G][K], the EqualLinears as bf16(weight * scale) [G][K][1][C] and
+    bias * lr_mul [G][K], and the LeakyReLU slope.  The caller holds weight_scope.  With ``holder`` (the encoder) they are kept under
+    ``key`` while every source pack is the same object as when they were stacked -- helpers._wnk's rule: a frozen weight's pack lives
+    while the weight is unchanged (weights.invalidate_packs forgets it), a trainable one is new every forward -- and no bias or linear
+    weight is trainable or has changed (storage + version counter)."""
+    depth = len(heads[0].convs) // 2
+    layers = [[h.convs[2 * i] for h in heads] for i in range(depth)]
+    src = [packed(c).wf for layer in layers for c in layer]
+    small = [t for h in heads for t in ([c.bias for c in h.convs if isinstance(c, Conv2d)] + [h.linear.weight, h.linear.bias]) if t is not None]
+    ver = None if any(t.requires_grad for t in small) else tuple((t.data_ptr(), t._version) for t in small)
+    store = getattr(holder, "_fmi_head_packs", None) if holder is not None else None
+    kept = store.get(key) if store is not None else None
+    if kept is not None and ver is not None and kept[1] == ver and len(kept[0]) == len(src) and all(a is b for a, b in zip(kept[0], src)):
+        return kept[2]
+    with torch.no_grad():
+        conv_w, conv_b = [], []
+        for layer in layers:
+            conv_w.append(torch.stack([helpers._wnk(c) for c in layer]))
+            conv_b.append(torch.stack([c.bias.detach() for c in layer]).contiguous() if layer[0].bias is not None else None)
+            for c in layer:  # the stacked copy is the one that is read from now on
+                object.__setattr__(c, "_fmi_wnk", None)
+        lin_w = torch.stack([(h.linear.weight.detach() * h.linear.scale).to(torch.bfloat16) for h in heads]).unsqueeze(2).contiguous()
+        lin_b = torch.stack([h.linear.bias.detach() * h.linear.lr_mul for h in heads]).contiguous() if heads[0].linear.bias is not None else None
+    ops = (conv_w, conv_b, lin_w, lin_b, float(heads[0].convs[1].negative_slope))
+    if holder is not None:
+        if store is None:
+            store = {}
+            object.__setattr__(holder, "_fmi_head_packs", store)
+        store[key] = (src, ver, ops) if ver is not None else None
+    return ops
+
+
+def style_level_bf16(heads, p16, latents, first=0, holder=None):
+    """The map2style heads of ONE pyramid level (psp_encoders.py:13-37 for each of them, the loops of :140-151) on the bf16 NHWC map
+    ``p16``, one launch per layer for all of them: layer 1 on the shared map, every deeper layer on the stacked outputs, and the
+    EqualLinears straight into slots first .. first + len(heads) - 1 of ``latents`` (fp32 [N, n_styles, K]).  Inference only; the caller
+    holds weight_scope over the heads."""
+    conv_w, conv_b, lin_w, lin_b, slope = _level_packs(heads, holder, (first, len(heads)))
+    x = p16
+    for i, (w, b) in enumerate(zip(conv_w, conv_b)):
+        x = FF.conv2d_grouped_bf16(x, w, b, 3, 2, 1, slope=slope, shared=(i == 0))
+    if x.shape[1] != 1 or x.shape[2] != 1:
+        raise FF.FmiError(f"a level map of {tuple(p16.shape[1:3])} does not reduce to 1 x 1 in {len(conv_w)} stride-2 layers")
+    return FF.conv2d_grouped_bf16(x, lin_w, lin_b, 1, 1, 0, shared=False, out=latents, first=first)
 
 
 class GradualStyleEncoder(Module):
@@ -72,6 +120,13 @@ class GradualStyleEncoder(Module):
         if edt not in ("fp32", "bf16"):
             raise FF.FmiError(f"encoder_eval_dtype must be 'fp32' or 'bf16', got {edt!r}")
         self.eval_body_dtype = torch.bfloat16 if edt == "bf16" else torch.float32
+        # opts.style_heads_eval_dtype ("fp32" default / "bf16"): the map2style heads of an EVAL-mode forward -- bf16 runs the heads of a
+        # pyramid level together on bf16 activations, one launch per layer (style_level_bf16; no backward).  Independent of the two
+        # options above: the level maps arrive in fp32 either way, and the lateral convolutions and the attention blocks stay fp32
+        sdt = getattr(opts, "style_heads_eval_dtype", "fp32")
+        if sdt not in ("fp32", "bf16"):
+            raise FF.FmiError(f"style_heads_eval_dtype must be 'fp32' or 'bf16', got {sdt!r}")
+        self.eval_heads_dtype = torch.bfloat16 if sdt == "bf16" else torch.float32
         self._widths = tuple(_widths)
         self.use_attention = opts.use_attention
         if opts.use_attention:
@@ -118,7 +173,50 @@ class GradualStyleEncoder(Module):
     def _infer_bf16(self):
         return self.eval_body_dtype == torch.bfloat16 and not self.training
 
+    def _heads_bf16(self):
+        return self.eval_heads_dtype == torch.bfloat16 and not self.training
+
+    def _latents_bf16(self, c1, c2, c3):
+        """FPN + heads of the bf16 inference form: three map hand-overs and log2(spatial) + 1 launches per level, written straight into
+        the [N, n_styles, K] tensor (the fp32 form: psp_encoders.py:140-151, 2 depth + 1 launches per head and a torch.stack)"""
+        latents = torch.empty((c3.shape[0], self.style_count, c3.shape[3]), device=c3.device, dtype=torch.float32)
+        bounds = [0, min(self.coarse_ind, self.style_count), min(self.middle_ind, self.style_count), self.style_count]
+        p = None
+        for lvl, lateral in enumerate((None, self.latlayer1, self.latlayer2)):
+            if lateral is None:
+                p, p16 = c3, FF.fpn_merge_bf16(c3, None, want_f32=False)[1]
+            else:
+                p, p16 = FF.fpn_merge_bf16(run_conv(lateral, c2 if lvl == 1 else c1), p, want_f32=lvl == 1)
+            lo, hi = bounds[lvl], bounds[lvl + 1]
+            if hi > lo:
+                style_level_bf16([self.styles[j] for j in range(lo, hi)], p16, latents, lo, holder=self)
+        return latents
+
+    def _latents(self, c1, c2, c3):
+        """the head section: FPN merges + map2style heads from the three level maps (fp32 NHWC); the caller holds weight_scope"""
+        if self._heads_bf16():
+            return self._latents_bf16(c1, c2, c3)
+        latents = [self.styles[j].nhwc(c3) for j in range(self.coarse_ind)]
+        p2 = self._upsample_add(c3, run_conv(self.latlayer1, c2))
+        latents += [self.styles[j].nhwc(p2) for j in range(self.coarse_ind, self.middle_ind)]
+        p1 = self._upsample_add(p2, run_conv(self.latlayer2, c1))
+        latents += [self.styles[j].nhwc(p1) for j in range(self.middle_ind, self.style_count)]
+        return torch.stack(latents, dim=1)
+
     def forward(self, x, ref=None, mask=None):
+        heads16 = self._heads_bf16()
+        if heads16:  # refused before any device call, like the body's inference form
+            if torch.is_grad_enabled():
+                raise FF.FmiError("GradualStyleEncoder with style_heads_eval_dtype='bf16' is inference only (no backward): call it under "
+                                  "torch.no_grad() or detach the input")
+            if any(w % 64 for w in self._widths):
+                raise FF.FmiError(f"the bf16 style heads need every width to be a multiple of 64, got {self._widths}")
+        if getattr(self, "_fmi_heads_b16", None) != heads16:  # the heads' convolutions need no fp32 piece images while they run on bf16 activations
+            for h in self.styles:
+                for m in h.convs:
+                    if isinstance(m, nn.Conv2d):
+                        object.__setattr__(m, "_fmi_no_w3", heads16)
+            object.__setattr__(self, "_fmi_heads_b16", heads16)
         if self._infer_bf16():  # refused before any device call; there is no fp32 detour
             if torch.is_grad_enabled():
                 raise FF.FmiError("GradualStyleEncoder with encoder_eval_dtype='bf16' is inference only (no backward): call it under "
@@ -153,9 +251,4 @@ class GradualStyleEncoder(Module):
                 c1 = self._blend(mask_1, r1, c1)
             else:
                 c1, c2, c3 = self._pyramid(FF.to_nhwc(x))
-            latents = [self.styles[j].nhwc(c3) for j in range(self.coarse_ind)]
-            p2 = self._upsample_add(c3, run_conv(self.latlayer1, c2))
-            latents += [self.styles[j].nhwc(p2) for j in range(self.coarse_ind, self.middle_ind)]
-            p1 = self._upsample_add(p2, run_conv(self.latlayer2, c1))
-            latents += [self.styles[j].nhwc(p1) for j in range(self.middle_ind, self.style_count)]
-            return torch.stack(latents, dim=1)
+            return self._latents(c1, c2, c3)

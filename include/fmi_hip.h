@@ -903,6 +903,37 @@ int fmi_guided_attention_fwd_bf16_waves(int N, int T);
 int fmi_guided_attention_fwd_bf16(const uint16_t* q, const uint16_t* src, const uint16_t* ref, const float* mask, uint16_t* out, int N, int T,
                                   int D, int C, int waves, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Inference form of the map2style heads of the pSp encoder on bf16 NHWC activations: the G heads of one pyramid level run together, one
+ * launch per layer (csrc/style_heads_bf16.hip and the grouped output stage of csrc/conv_bf16.hip).  Replaces, of the reference,
+ * psp_encoders.py:13-37 (GradualStyleBlock: log2(spatial) x [Conv2d 3x3 stride 2 + LeakyReLU], EqualLinear), psp_encoders.py:97-98
+ * (_upsample_add), psp_encoders.py:140-151 (the loops over the heads of a level, torch.stack) and stylegan2/model.py EqualLinear
+ * (F.linear(x, weight * scale, bias * lr_mul)).  fp32 parameters and accumulation, one round-to-nearest-even per stored bf16 value, no
+ * atomics: every result is bit-reproducible.  Every entry returns FMI_ERR_BAD_ARG / FMI_ERR_UNSUPPORTED before any HIP call.
+ * ---------------------------------------------------------------------- */
+#define FMI_STYLE_SKINNY_ROWS 128 /* fmi_conv2d_grouped_fwd_bf16: calls with at most this many output rows take the weight-streaming kernel */
+/* G convolutions in one launch (psp_encoders.py:13-37 for all heads of a level, psp_encoders.py:140-151): group g reads channels
+ * [g * x_group_off, g * x_group_off + C) of every pixel of x (x_group_off = 0: all groups read the same map, layer 1 of a level;
+ * x_group_off = C: layers 2 and later) and writes columns [g*K, (g+1)*K) of every pixel of y; d->C / d->K are per group, d->x_cstride /
+ * d->y_cstride the pixel pitches (x_cstride >= (G-1) * x_group_off + C, y_cstride >= G*K; columns outside [0, G*K) are never written).
+ * wnk: bf16 [G][K][kh*kw][C]; bias: fp32 [G][K] or NULL.  y = v > 0 ? v : slope * v with v = acc + bias (slope = 1: no activation).
+ * Exactly one of y16 (bf16) and y32 (fp32) is non-NULL, else FMI_ERR_BAD_ARG; so are NULL operands, G <= 0, x_group_off not in {0, C}
+ * and a descriptor whose OH / OW do not follow.  Supported: 3x3 pad 1 stride 2 or 1x1 pad 0 stride 1; C % 64 == 0, K % 64 == 0; 16-byte
+ * aligned operands; pitches that are multiples of 8; y32 for 1x1 only -- the EqualLinear of all heads of a level (stylegan2/model.py
+ * EqualLinear, psp_encoders.py:36; wnk = bf16(weight * scale), bias = bias * lr_mul) written straight into its slots of the
+ * [N, n_styles, K] latent tensor: y32 = latents + first*K, y_cstride = n_styles*K.  Everything else: FMI_ERR_UNSUPPORTED.
+ * rows = N*OH*OW > FMI_STYLE_SKINNY_ROWS with y16: the 128-byte-row tile kernel of csrc/conv_bf16.hip, one grid row per group.
+ * rows <= FMI_STYLE_SKINNY_ROWS, and every y32 call: a kernel that streams each group's weights once -- grid (K/16, G, ceil(rows/64)),
+ * four waves that split the reduction and meet through LDS in a fixed order. */
+int fmi_conv2d_grouped_fwd_bf16(const fmi_conv_desc* d, int G, int64_t x_group_off, const uint16_t* x, const uint16_t* wnk,
+                                const float* bias, float slope, uint16_t* y16, float* y32, void* stream);
+/* _upsample_add (psp_encoders.py:97-98) and the hand-over to the heads in one pass: p = bilinear(coarse, align_corners=True, to H x W) +
+ * lateral, written as fp32 p32 (may be NULL) and bf16 p16.  coarse NULL: the plain conversion p = lateral (the coarsest map).  lateral,
+ * p32, p16 are [N,H,W,C], coarse is [N,CH,CW,C]; C % 8 == 0, 16-byte aligned pointers (else FMI_ERR_UNSUPPORTED).  NULL lateral / p16
+ * or a non-positive extent: FMI_ERR_BAD_ARG. */
+int fmi_fpn_merge_bf16(const float* lateral, const float* coarse, float* p32, uint16_t* p16, int N, int H, int W, int CH, int CW, int C,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
