@@ -27,39 +27,13 @@ static int check_desc(const fmi_conv_desc* d) {
   return FMI_OK;
 }
 
-// forward-geometry gather: anchors = output pixels of the conv
-static ConvGeom fwd_geom(const fmi_conv_desc* d, const float* x, int n_eff) {
-  ConvGeom g{};
-  g.N = n_eff; g.IH = d->H; g.IW = d->W; g.C = d->C; g.cstride = d->x_cstride;
-  g.GH = d->OH; g.GW = d->OW; g.S = d->stride;
-  const int dl = d->dil > 1 ? d->dil : 1;  // dilation = the tap step of the gather (modules/drn.py)
-  g.nty = d->kh; g.ntx = d->kw; g.dy0 = -d->pad; g.dx0 = -d->pad; g.ystep = dl; g.xstep = dl;
-  g.kh0 = 0; g.kw0 = 0; g.khstep = 1; g.kwstep = 1; g.kw = d->kw;
-  g.pad_mode = d->pad_mode;
-  g.vec = (d->C % 4 == 0) && (d->x_cstride % 4 == 0) && aligned16(x);
-  g.dGW = make_fastdiv(g.GW); g.dG = make_fastdiv(g.GH * g.GW); g.dC = make_fastdiv(g.C); g.dntx = make_fastdiv(g.ntx);
-  g.img_bs = (int64_t)d->H * d->W * d->x_cstride;
-  return g;
-}
-
-// adjoint-geometry gather of sub-pixel phase (py, px): anchors = the pixels of dx congruent to (py, px) modulo the stride, taps = the
-// kernel taps that reach them (none: nty = 0, ntx = 1, an empty reduction)
-static ConvGeom adj_geom(const fmi_conv_desc* d, const float* dy, int n_eff, int py, int px) {
-  const int s = d->stride, dl = d->dil > 1 ? d->dil : 1;
-  ConvGeom g{};
-  g.N = n_eff; g.IH = d->OH; g.IW = d->OW; g.C = d->K; g.cstride = d->y_cstride;
-  g.GH = (d->H - py + s - 1) / s; g.GW = (d->W - px + s - 1) / s; g.S = 1;
-  g.kh0 = (py + d->pad) % s; g.kw0 = (px + d->pad) % s;
-  g.nty = g.kh0 < d->kh ? (d->kh - g.kh0 + s - 1) / s : 0;
-  g.ntx = g.kw0 < d->kw ? (d->kw - g.kw0 + s - 1) / s : 0;
-  g.dy0 = (py + d->pad - g.kh0) / s; g.dx0 = (px + d->pad - g.kw0) / s;
-  g.ystep = -dl; g.xstep = -dl; g.khstep = s; g.kwstep = s; g.kw = d->kw;  // dl > 1 only with s == 1 (the caller checks)
-  g.pad_mode = 0;
-  g.vec = (d->K % 4 == 0) && (d->y_cstride % 4 == 0) && aligned16(dy);
-  g.dGW = make_fastdiv(g.GW); g.dG = make_fastdiv(g.GH * g.GW); g.dC = make_fastdiv(g.C);
-  g.dntx = make_fastdiv(g.ntx > 0 ? g.ntx : 1);
-  g.img_bs = (int64_t)d->OH * d->OW * d->y_cstride;
-  if (g.nty == 0 || g.ntx == 0) { g.nty = 0; g.ntx = 1; }
+// the fields the shared builders (gemm_core.h) leave to the family, as the fp32 gathers read them; img = the gathered tensor
+static ConvGeom f32_geom(ConvGeom g, const fmi_conv_desc* d, const float* img) {
+  const int dl = d->dil > 1 ? d->dil : 1;  // dilation = the tap step of the gather (modules/drn.py); adjoint: only with stride 1 (the caller checks)
+  g.ystep *= dl; g.xstep *= dl;
+  g.vec = (g.C % 4 == 0) && (g.cstride % 4 == 0) && aligned16(img);  // 1 = four channels are one float4 load
+  g.dC = make_fastdiv(g.C);                                          // reduction index -> tap
+  g.img_bs = (int64_t)g.IH * g.IW * g.cstride;                       // per-sample weight mode: one sample of the image
   return g;
 }
 
@@ -187,7 +161,7 @@ extern "C" int fmi_conv2d_fwd_f32(const fmi_conv_desc* d, const float* x, const 
   if (batch_w == 1 && d->kh == 3 && fmi_conv2d_thin_in_routed(d) && aligned16(y) && aligned16(residual))
     return finish(fmi_conv2d_thin_in_fwd_f32(d, x, wf, bias, residual, y, act, stream));
 #endif
-  const ConvGeom g = fwd_geom(d, x, batch_w > 1 ? 1 : d->N);
+  const ConvGeom g = f32_geom(fwd_geom(d, batch_w > 1 ? 1 : d->N), d, x);
   // bf16 piece images of the weights (fmi_weight_prepare_f32 writes them): [3][taps][C / 8][K][8]
   const void* w3 = weight_pieces(d, batch_w, d->C);
   ConvEp ep{y, bias, residual, d->OH, d->OW, 1, 0, 0, d->OH, d->OW, d->y_cstride, act, g.dGW, g.dG, (int64_t)d->OH * d->OW * d->y_cstride};
@@ -234,7 +208,7 @@ static int dgrad_impl(const fmi_conv_desc* d, const float* dy, const float* wt, 
   if (s > 1 && batch_w == 1) {
     for (int py = 0; py < s && !strided_split; ++py)
       for (int px = 0; px < s && !strided_split; ++px) {
-        const ConvGeom g = adj_geom(d, dy, n_eff, py, px);
+        const ConvGeom g = adj_geom(d, n_eff, py, px);
         if (g.GH > 0 && g.GW > 0 && conv_ksplit(g.Mdim(), d->C, g.Kdim()) > 1) strided_split = true;
       }
     if (strided_split) {
@@ -258,7 +232,7 @@ static int dgrad_impl(const fmi_conv_desc* d, const float* dy, const float* wt, 
 #endif
   for (int py = 0; py < s; ++py) {
     for (int px = 0; px < s; ++px) {
-      const ConvGeom g = adj_geom(d, dy, n_eff, py, px);
+      const ConvGeom g = f32_geom(adj_geom(d, n_eff, py, px), d, dy);
       if (g.GH <= 0 || g.GW <= 0) continue;
       ConvEp ep{dx, bias, residual, g.GH, g.GW, s, py, px, d->H, d->W, d->x_cstride, 0, g.dGW, g.dG,
                 (int64_t)d->H * d->W * d->x_cstride};
@@ -328,7 +302,7 @@ extern "C" int fmi_conv2d_wgrad_f32(const fmi_conv_desc* d, const float* x, cons
     return launch_wgrad_p3(d, (const uint16_t*)d->x3, (const uint16_t*)d->y3, dwf, (hipStream_t)stream);
 #endif
   const int n_eff = batch_w > 1 ? 1 : d->N;
-  ConvGeom g = fwd_geom(d, x, n_eff);
+  ConvGeom g = f32_geom(fwd_geom(d, n_eff), d, x);
   // the bias gradient rides along as one extra output row (needs a float4-aligned row index and shared weights)
   const bool fuse_bias = dbias && batch_w == 1 && (g.Kdim() % 4 == 0);
   if (dbias && !fuse_bias) return FMI_ERR_UNSUPPORTED;

@@ -596,27 +596,30 @@ extern "C" int fmi_conv2d_bf16_supported(const fmi_conv_desc* d) {
   return d->C % 32 == 0 && d->K % 32 == 0 && d->x_cstride % 8 == 0 && d->y_cstride % 8 == 0;
 }
 
+// The one-phase ConvSetB of a plain forward convolution: geometry, both loaders, the addressing of the output stage, M, K and the unsplit
+// defaults of N / ksplit / ws (launch_conv_bf16 sets those three again).  vec_flag: y takes the 8-byte stores (ConvEpB::vec).
+static ConvSetB fwd_set_b(const fmi_conv_desc* d, const uint16_t* x, const uint16_t* wnk, uint16_t* y, const float* colscale, int vec_flag) {
+  ConvGeom g = fwd_geom(d, d->N);      // check_desc_b: no dilation, pad_mode 0.  img_bs stays 0: no per-sample weights in this family
+  g.vec = d->C % 64 == 0 ? 6 : 5;      // here: log2 of the reduction tile BK (the fp32 family keeps a float4 flag in this field)
+  g.dC = make_fastdiv(g.nty * g.ntx);  // here: divides by the number of TAPS (ConvKB::tile; the weight gradients and fp32 divide by C)
+  ConvSetB set{};
+  set.ph[0].la = ConvKB{x, g};
+  set.ph[0].lb = ConvWKB{wnk, g, d->K, d->kh * d->kw};
+  set.ph[0].ep = ConvEpB{y, colscale, d->OH, d->OW, 1, 0, 0, d->OH, d->OW, d->y_cstride, d->K, g.dGW, g.dG, vec_flag};
+  set.ph[0].M = g.Mdim();
+  set.ph[0].K = g.Kdim();
+  set.N = d->K;
+  set.ksplit = 1;
+  return set;
+}
+
 static int conv2d_fwd_bf16_impl(const fmi_conv_desc* d, const uint16_t* x, const uint16_t* wnk, const float* colscale, uint16_t* y, float* ws,
                                int64_t ws_floats, const EpActB* act, void* stream) {
   int rc = check_desc_b(d);
   if (rc) return rc;
   if (!x || !wnk || !y) return FMI_ERR_BAD_ARG;
   if (d->C % 32 != 0 || d->x_cstride % 8 != 0 || !fmi_al16(x) || !fmi_al16(wnk)) return FMI_ERR_UNSUPPORTED;
-  ConvGeom g{};
-  g.N = d->N; g.IH = d->H; g.IW = d->W; g.C = d->C; g.cstride = d->x_cstride;
-  g.GH = d->OH; g.GW = d->OW; g.S = d->stride;
-  g.nty = d->kh; g.ntx = d->kw; g.dy0 = -d->pad; g.dx0 = -d->pad; g.ystep = 1; g.xstep = 1;
-  g.kh0 = 0; g.kw0 = 0; g.khstep = 1; g.kwstep = 1; g.kw = d->kw;
-  g.pad_mode = 0; g.vec = d->C % 64 == 0 ? 6 : 5;  // log2 of the reduction tile
-  g.dGW = make_fastdiv(g.GW); g.dG = make_fastdiv(g.GH * g.GW); g.dC = make_fastdiv(g.nty * g.ntx); g.dntx = make_fastdiv(g.ntx);
-  g.img_bs = 0;
-  ConvSetB set{};
-  set.ph[0].la = ConvKB{x, g};
-  set.ph[0].lb = ConvWKB{wnk, g, d->K, d->kh * d->kw};
-  set.ph[0].ep = ConvEpB{y, colscale, d->OH, d->OW, 1, 0, 0, d->OH, d->OW, d->y_cstride, d->K, g.dGW, g.dG,
-                         (d->K % 4 == 0 && d->y_cstride % 4 == 0 && ((uintptr_t)y & 7) == 0) ? 1 : 0};
-  set.ph[0].M = g.Mdim();
-  set.ph[0].K = g.Kdim();
+  ConvSetB set = fwd_set_b(d, x, wnk, y, colscale, (d->K % 4 == 0 && d->y_cstride % 4 == 0 && ((uintptr_t)y & 7) == 0) ? 1 : 0);
   const int64_t out_elems = (int64_t)d->N * d->OH * d->OW * d->y_cstride;
   if (ws && (((uintptr_t)ws & 15) || ((uintptr_t)y & 7))) ws = nullptr;
   if (d->C % 64 == 0) return launch_conv_bf16<64>(set, 1, d->K, y, ws, ws_floats, out_elems, (hipStream_t)stream, act);
@@ -656,23 +659,7 @@ extern "C" int fmi_conv2d_fwd_chan_bf16(const fmi_conv_desc* d, const uint16_t* 
   if (d->x_cstride % 8 != 0 || d->y_cstride % 4 != 0 || !fmi_al16(x) || !fmi_al16(wnk) || ((uintptr_t)y & 7) || !fmi_al16(scale) ||
       !fmi_al16(bias) || !fmi_al16(slope) || !fmi_al16(colsum))
     return FMI_ERR_UNSUPPORTED;
-  ConvGeom g{};
-  g.N = d->N; g.IH = d->H; g.IW = d->W; g.C = d->C; g.cstride = d->x_cstride;
-  g.GH = d->OH; g.GW = d->OW; g.S = d->stride;
-  g.nty = d->kh; g.ntx = d->kw; g.dy0 = -d->pad; g.dx0 = -d->pad; g.ystep = 1; g.xstep = 1;
-  g.kh0 = 0; g.kw0 = 0; g.khstep = 1; g.kwstep = 1; g.kw = d->kw;
-  g.pad_mode = 0; g.vec = 6;
-  g.dGW = make_fastdiv(g.GW); g.dG = make_fastdiv(g.GH * g.GW); g.dC = make_fastdiv(g.nty * g.ntx); g.dntx = make_fastdiv(g.ntx);
-  g.img_bs = 0;
-  ConvSetB set{};
-  set.ph[0].la = ConvKB{x, g};
-  set.ph[0].lb = ConvWKB{wnk, g, d->K, d->kh * d->kw};
-  set.ph[0].ep = ConvEpB{y, nullptr, d->OH, d->OW, 1, 0, 0, d->OH, d->OW, d->y_cstride, d->K, g.dGW, g.dG, 1};
-  set.ph[0].M = g.Mdim();
-  set.ph[0].K = g.Kdim();
-  set.N = d->K;
-  set.ksplit = 1;
-  set.ws = nullptr;
+  ConvSetB set = fwd_set_b(d, x, wnk, y, nullptr, 1);  // C % 64 == 0 (above): 64-deep reduction tiles
   const EpChanB ch{scale, bias, slope, colsum};
   hipStream_t st = (hipStream_t)stream;
   // both tiles have 128 rows in two 64-row wave blocks (the column sums' granularity); 64 output columns take the narrow one
@@ -692,23 +679,7 @@ extern "C" int fmi_conv2d_fwd_chan_bf16(const fmi_conv_desc* d, const uint16_t* 
  * table, with the groups counted into the workgroups of a candidate. */
 int fmi_conv_bf16_grouped_tiles(const fmi_conv_desc* d, int G, int64_t x_off, int64_t w_off, const uint16_t* x, const uint16_t* wnk,
                                 const float* bias, float slope, uint16_t* y, void* stream) {
-  ConvGeom g{};
-  g.N = d->N; g.IH = d->H; g.IW = d->W; g.C = d->C; g.cstride = d->x_cstride;
-  g.GH = d->OH; g.GW = d->OW; g.S = d->stride;
-  g.nty = d->kh; g.ntx = d->kw; g.dy0 = -d->pad; g.dx0 = -d->pad; g.ystep = 1; g.xstep = 1;
-  g.kh0 = 0; g.kw0 = 0; g.khstep = 1; g.kwstep = 1; g.kw = d->kw;
-  g.pad_mode = 0; g.vec = 6;
-  g.dGW = make_fastdiv(g.GW); g.dG = make_fastdiv(g.GH * g.GW); g.dC = make_fastdiv(g.nty * g.ntx); g.dntx = make_fastdiv(g.ntx);
-  g.img_bs = 0;
-  ConvSetB set{};
-  set.ph[0].la = ConvKB{x, g};
-  set.ph[0].lb = ConvWKB{wnk, g, d->K, d->kh * d->kw};
-  set.ph[0].ep = ConvEpB{y, nullptr, d->OH, d->OW, 1, 0, 0, d->OH, d->OW, d->y_cstride, d->K, g.dGW, g.dG, 1};
-  set.ph[0].M = g.Mdim();
-  set.ph[0].K = g.Kdim();
-  set.N = d->K;
-  set.ksplit = 1;
-  set.ws = nullptr;
+  ConvSetB set = fwd_set_b(d, x, wnk, y, nullptr, 1);  // C % 64 == 0 (the caller checks): 64-deep reduction tiles
   const EpGroupB ch{bias, slope, x_off, w_off};
   hipStream_t st = (hipStream_t)stream;
   const int64_t M = set.ph[0].M;
@@ -741,22 +712,11 @@ extern "C" int fmi_conv2d_dgrad_bf16(const fmi_conv_desc* d, const uint16_t* dy,
   int nph = 0;
   for (int py = 0; py < s; ++py) {
     for (int px = 0; px < s; ++px) {
-      const int GH = (d->H - py + s - 1) / s, GW = (d->W - px + s - 1) / s;
+      ConvGeom g = adj_geom(d, d->N, py, px);  // img_bs stays 0: no per-sample weights in this family
+      const int GH = g.GH, GW = g.GW;
       if (GH <= 0 || GW <= 0) continue;
-      ConvGeom g{};
-      g.N = d->N; g.IH = d->OH; g.IW = d->OW; g.C = d->K; g.cstride = d->y_cstride;
-      g.GH = GH; g.GW = GW; g.S = 1;
-      g.kh0 = (py + d->pad) % s; g.kw0 = (px + d->pad) % s;
-      g.nty = g.kh0 < d->kh ? (d->kh - g.kh0 + s - 1) / s : 0;
-      g.ntx = g.kw0 < d->kw ? (d->kw - g.kw0 + s - 1) / s : 0;
-      g.dy0 = (py + d->pad - g.kh0) / s; g.dx0 = (px + d->pad - g.kw0) / s;
-      g.ystep = -1; g.xstep = -1; g.khstep = s; g.kwstep = s; g.kw = d->kw;
-      g.pad_mode = 0; g.vec = d->K % 64 == 0 ? 6 : 5;  // log2 of the reduction tile
-      g.dGW = make_fastdiv(GW); g.dG = make_fastdiv(GH * GW);
-      g.dntx = make_fastdiv(g.ntx > 0 ? g.ntx : 1);
-      g.img_bs = 0;
-      if (g.nty == 0 || g.ntx == 0) { g.nty = 0; g.ntx = 1; }
-      g.dC = make_fastdiv(g.nty * g.ntx > 0 ? g.nty * g.ntx : 1);
+      g.vec = d->K % 64 == 0 ? 6 : 5;                                      // here: log2 of the reduction tile
+      g.dC = make_fastdiv(g.nty * g.ntx > 0 ? g.nty * g.ntx : 1);          // here: divides by the number of TAPS (1: the empty phase)
       ConvPhaseB& P = set.ph[nph++];
       P.la = ConvKB{dy, g};
       P.lb = ConvWKB{wck, g, d->C, d->kh * d->kw};
@@ -969,11 +929,8 @@ extern "C" int fmi_conv2d_wgrad_bf16(const fmi_conv_desc* d, const uint16_t* x, 
   WgArgsB a{};
   a.x = x; a.dy = dy; a.dwf = dwf;
   ConvGeom& g = a.g;
-  g.N = d->N; g.IH = d->H; g.IW = d->W; g.C = d->C; g.cstride = d->x_cstride;
-  g.GH = d->OH; g.GW = d->OW; g.S = d->stride;
-  g.nty = d->kh; g.ntx = d->kw; g.dy0 = -d->pad; g.dx0 = -d->pad; g.ystep = 1; g.xstep = 1;
-  g.kh0 = 0; g.kw0 = 0; g.khstep = 1; g.kwstep = 1; g.kw = d->kw;
-  g.dGW = make_fastdiv(g.GW); g.dG = make_fastdiv(g.GH * g.GW); g.dC = make_fastdiv(g.C); g.dntx = make_fastdiv(g.ntx);
+  g = fwd_geom(d, d->N);     // vec and img_bs stay 0: the weight gradient reads neither
+  g.dC = make_fastdiv(g.C);  // here: divides by C (output row -> tap), as in the fp32 family
   a.Kout = d->K; a.ycs = d->y_cstride; a.Mrows = d->kh * d->kw * d->C; a.P = d->N * d->OH * d->OW;
   // the eight-phase kernel (wgrad_bf16_8ph.h): 256 x 256 tiles, one workgroup per CU -- for wide layers with a long pixel range
   {

@@ -912,12 +912,9 @@ static int launch_wgrad_p3(const fmi_conv_desc* d, const uint16_t* x3, const uin
   WgP3Args a{};
   a.x3 = x3; a.dy3 = dy3; a.dwf = dwf;
   ConvGeom& g = a.g;
-  const int dl = d->dil > 1 ? d->dil : 1;
-  g.N = d->N; g.IH = d->H; g.IW = d->W; g.C = d->C; g.cstride = d->C;
-  g.GH = d->OH; g.GW = d->OW; g.S = d->stride;
-  g.nty = d->kh; g.ntx = d->kw; g.dy0 = -d->pad; g.dx0 = -d->pad; g.ystep = dl; g.xstep = dl;
-  g.kh0 = 0; g.kw0 = 0; g.khstep = 1; g.kwstep = 1; g.kw = d->kw;
-  g.dGW = make_fastdiv(g.GW); g.dG = make_fastdiv(g.GH * g.GW); g.dC = make_fastdiv(g.C); g.dntx = make_fastdiv(g.ntx);
+  g = fwd_geom(d, d->N);  // dense x, zero padding (wgrad_p3_ok): cstride = C, pad_mode = 0; vec and img_bs are not read here
+  g.ystep = g.xstep = d->dil > 1 ? d->dil : 1;  // dilation = the tap step of the gather
+  g.dC = make_fastdiv(g.C);                     // output row -> tap
   a.Kout = d->K; a.Mrows = d->kh * d->kw * d->C; a.P = d->N * d->OH * d->OW;
   if (wgrad3x3_p3_ok(d)) {
     Wg3x3Args w{};

@@ -144,10 +144,7 @@ struct DenseX {  // row/column index contiguous in memory
 
 // Geometry of one implicit-GEMM launch.  Rows enumerate a grid [N][GH][GW] of "anchor" positions;
 // tap t = (i, j), i < nty, j < ntx, reads the image at (gy*S + dy0 + ystep*i, gx*S + dx0 + xstep*j)
-// and uses weight tap (kh0 + khstep*i)*kw + (kw0 + kwstep*j).
-//   forward conv : anchors = output pixels, S = stride, dy0 = -pad, steps = +1, all kh*kw taps
-//   adjoint, phase (py,px) of stride s: anchors = x pixels (gy*s+py, gx*s+px), image = dy, S = 1,
-//                  kh = kh0 + s*i with (py + pad - kh0) % s == 0, dy0 = (py+pad-kh0)/s, ystep = -1
+// and uses weight tap (kh0 + khstep*i)*kw + (kw0 + kwstep*j).  fwd_geom / adj_geom below build it.
 struct ConvGeom {
   int N, IH, IW, C, cstride;  // gathered image (NHWC), C channels used, pixel pitch cstride
   int GH, GW, S;
@@ -159,6 +156,34 @@ struct ConvGeom {
   __host__ __device__ __forceinline__ int Kdim() const { return nty * ntx * C; }
   __host__ __device__ __forceinline__ int Mdim() const { return N * GH * GW; }
 };
+// The builders of every convolution family (conv.hip, conv_p3.h, conv_bf16.hip) fill what means the same to all gathers.  vec, dC and img_bs
+// stay ZERO: each family reads them its own way ("Shared convolution set-up") and sets them where it calls.  The tap steps are
+// +-1; the fp32 family multiplies them by the dilation.
+// forward: anchors = output pixels, S = stride, dy0 = -pad, all kh*kw taps
+static inline ConvGeom fwd_geom(const fmi_conv_desc* d, int n_eff) {
+  ConvGeom g{};
+  g.N = n_eff; g.IH = d->H; g.IW = d->W; g.C = d->C; g.cstride = d->x_cstride; g.GH = d->OH; g.GW = d->OW; g.S = d->stride;
+  g.nty = d->kh; g.ntx = d->kw; g.dy0 = -d->pad; g.dx0 = -d->pad; g.ystep = 1; g.xstep = 1;
+  g.kh0 = 0; g.kw0 = 0; g.khstep = 1; g.kwstep = 1; g.kw = d->kw; g.pad_mode = d->pad_mode;
+  g.dGW = make_fastdiv(g.GW); g.dG = make_fastdiv(g.GH * g.GW); g.dntx = make_fastdiv(g.ntx);
+  return g;
+}
+// adjoint, phase (py, px) of stride s: anchors = x pixels (gy*s+py, gx*s+px), image = dy, S = 1, kh = kh0 + s*i with
+// (py + pad - kh0) % s == 0, dy0 = (py+pad-kh0)/s, zero padding; a phase no tap reaches has nty = 0, ntx = 1: an empty reduction
+static inline ConvGeom adj_geom(const fmi_conv_desc* d, int n_eff, int py, int px) {
+  const int s = d->stride;
+  ConvGeom g{};
+  g.N = n_eff; g.IH = d->OH; g.IW = d->OW; g.C = d->K; g.cstride = d->y_cstride;
+  g.GH = (d->H - py + s - 1) / s; g.GW = (d->W - px + s - 1) / s; g.S = 1;
+  g.kh0 = (py + d->pad) % s; g.kw0 = (px + d->pad) % s;
+  g.nty = g.kh0 < d->kh ? (d->kh - g.kh0 + s - 1) / s : 0;
+  g.ntx = g.kw0 < d->kw ? (d->kw - g.kw0 + s - 1) / s : 0;
+  g.dy0 = (py + d->pad - g.kh0) / s; g.dx0 = (px + d->pad - g.kw0) / s;
+  g.ystep = -1; g.xstep = -1; g.khstep = s; g.kwstep = s; g.kw = d->kw;
+  g.dGW = make_fastdiv(g.GW); g.dG = make_fastdiv(g.GH * g.GW); g.dntx = make_fastdiv(g.ntx > 0 ? g.ntx : 1);
+  if (g.nty == 0 || g.ntx == 0) { g.nty = 0; g.ntx = 1; }
+  return g;
+}
 
 __device__ __forceinline__ int reflect_idx(int i, int n) {
   if (i < 0) i = -i;

@@ -573,6 +573,17 @@ def _pack_bf16(src_tab: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _conv_fwd_bf16_pre(x, k, kh, kw, stride, pad, tag="", pad_mode=0, out_dtype=BF16):
+    """The preamble every forward wrapper of the bf16 convolution family shares: (d, y, prof) = the descriptor of x [N, H, W, C] -> k
+    channels, the empty [N, OH, OW, k] output and the ``_prof`` context with the family's label (``tag`` = its suffix) and FLOP count.
+    The weight pack stays with the wrapper: some pack per call (``_pack_bf16``, one more launch), some keep the pack on the
+    PackedWeight (``_wnk_of``) -- that difference is a launch count, so it is not folded in here."""
+    n, h, w, c = x.shape
+    d, oh, ow = conv_desc(n, h, w, c, k, kh, kw, stride, pad, pad_mode)
+    y = torch.empty((n, oh, ow, k), device=x.device, dtype=out_dtype)
+    return d, y, _prof(f"conv_fwd_bf16|{n}x{h}x{w} {c}->{k} k{kh}s{stride}{tag}", 2.0 * n * oh * ow * k * c * kh * kw)
+
+
 class _Conv2dBF16(torch.autograd.Function):
     """y = conv(x, W) on bf16 NHWC activations, fp32 accumulation; wf / wt are the fp32 packs (wf carries the weight gradient)."""
 
@@ -580,15 +591,11 @@ class _Conv2dBF16(torch.autograd.Function):
     def forward(ctx, x, wf, wt, kh, kw, stride, pad):
         _chk(x, dtype=BF16)
         _chk(wf, wt)
-        lib = _L()
-        n, h, w, c = x.shape
-        k = wf.shape[2]
-        d, oh, ow = conv_desc(n, h, w, c, k, kh, kw, stride, pad)
-        y = torch.empty((n, oh, ow, k), device=x.device, dtype=BF16)
+        d, y, prof = _conv_fwd_bf16_pre(x, wf.shape[2], kh, kw, stride, pad)
         wnk = _pack_bf16(wf)
-        ws, wsn = _split_ws(y, c * kh * kw)
-        with _prof(f"conv_fwd_bf16|{n}x{h}x{w} {c}->{k} k{kh}s{stride}", 2.0 * n * oh * ow * k * c * kh * kw):
-            lib.conv2d_fwd_bf16(C.byref(d), _p(x), _p(wnk), None, _p(y), _p(ws), wsn, _st())
+        ws, wsn = _split_ws(y, x.shape[3] * kh * kw)
+        with prof:
+            _L().conv2d_fwd_bf16(C.byref(d), _p(x), _p(wnk), None, _p(y), _p(ws), wsn, _st())
         ctx.save_for_backward(x, wf, wt)
         ctx.cfg = (kh, kw, stride, pad)
         return y
@@ -689,14 +696,10 @@ class _StyledConvBF16(torch.autograd.Function):
     def forward(ctx, x, wf, wt, d, noise, nw, bias, kh, kw, pad, slope, gain):
         _chk(x, dtype=BF16)
         _chk(wf, wt, d, noise, nw, bias)
-        lib = _L()
-        n, h, w, c = x.shape
-        k = wf.shape[2]
-        dsc, oh, ow = conv_desc(n, h, w, c, k, kh, kw, 1, pad)
-        y = torch.empty((n, oh, ow, k), device=x.device, dtype=BF16)
+        dsc, y, prof = _conv_fwd_bf16_pre(x, wf.shape[2], kh, kw, 1, pad, " +out")
         wnk = _pack_bf16(wf)
-        with _prof(f"conv_fwd_bf16|{n}x{h}x{w} {c}->{k} k{kh}s1 +out", 2.0 * n * oh * ow * k * c * kh * kw):
-            lib.conv2d_fwd_act_bf16(C.byref(dsc), _p(x), _p(wnk), _p(d), _p(noise), _p(nw), _p(bias), slope, gain, _p(y), _st())
+        with prof:
+            _L().conv2d_fwd_act_bf16(C.byref(dsc), _p(x), _p(wnk), _p(d), _p(noise), _p(nw), _p(bias), slope, gain, _p(y), _st())
         ctx.save_for_backward(x, wf, wt, d, noise, nw, bias, y)
         ctx.cfg = (kh, kw, pad, slope, gain)
         return y
@@ -1327,8 +1330,7 @@ def conv_bn_relu_eval_bf16(x, pw: PackedWeight, conv_bias, bn, pad=1):
         raise FmiError("conv_bn_relu_eval_bf16 is the inference form of the bf16 UNet body (eval-mode BatchNorm): gradients must be off "
                        "(torch.no_grad()); train-mode BatchNorm is the path that differentiates")
     _chk(x, dtype=BF16)
-    n, h, w, c = x.shape
-    k = pw.wf.shape[2]
+    n, k = x.shape[0], pw.wf.shape[2]
     ts = (bn.weight, bn.bias, bn.running_var, bn.running_mean) + ((conv_bias,) if conv_bias is not None else ())
     # the folded constants of a FROZEN network are kept while none of the tensors changes (storage + version counter), as
     # helpers.batch_norm keeps its own; trainable parameters are written by the fused optimiser through raw pointers: folded every call.
@@ -1344,10 +1346,9 @@ def conv_bn_relu_eval_bf16(x, pw: PackedWeight, conv_bias, bn, pad=1):
         if key is not None:
             object.__setattr__(bn, "_fmi_fold", (key, colscale, bias))
     _chk(colscale, bias)
-    dsc, oh, ow = conv_desc(n, h, w, c, k, pw.kh, pw.kw, 1, pad)
-    y = torch.empty((n, oh, ow, k), device=x.device, dtype=BF16)
+    dsc, y, prof = _conv_fwd_bf16_pre(x, k, pw.kh, pw.kw, 1, pad, " +bn")
     wnk = _pack_bf16(pw.wf)
-    with _prof(f"conv_fwd_bf16|{n}x{h}x{w} {c}->{k} k{pw.kh}s1 +bn", 2.0 * n * oh * ow * k * c * pw.kh * pw.kw):
+    with prof:
         _L().conv2d_fwd_act_bf16(C.byref(dsc), _p(x), _p(wnk), _p(colscale), None, None, _p(bias), 0.0, 1.0, _p(y), _st())
     return y
 
@@ -1373,14 +1374,12 @@ def conv2d_bias_bf16(x, pw: PackedWeight, bias, pad):
     """conv(x) + bias on a bf16 NHWC map in one launch (the output stage of fmi_conv2d_fwd_act_bf16 with slope 1, gain 1)"""
     _chk(x, dtype=BF16)
     _chk(bias)
-    n, h, w, c = x.shape
-    k = pw.wf.shape[2]
+    c, k = x.shape[3], pw.wf.shape[2]
     if c % 64 or k % 4:
         raise FmiError(f"the bf16 convolution with a bias stage needs C % 64 == 0 and K % 4 == 0, got {c} -> {k}")
-    dsc, oh, ow = conv_desc(n, h, w, c, k, pw.kh, pw.kw, 1, pad)
-    y = torch.empty((n, oh, ow, k), device=x.device, dtype=BF16)
+    dsc, y, prof = _conv_fwd_bf16_pre(x, k, pw.kh, pw.kw, 1, pad, " +bias")
     wnk = _pack_bf16(pw.wf)
-    with _prof(f"conv_fwd_bf16|{n}x{h}x{w} {c}->{k} k{pw.kh}s1 +bias", 2.0 * n * oh * ow * k * c * pw.kh * pw.kw):
+    with prof:
         _L().conv2d_fwd_act_bf16(C.byref(dsc), _p(x), _p(wnk), None, None, None, _p(bias), 1.0, 1.0, _p(y), _st())
     return y
 
@@ -1436,12 +1435,11 @@ def lrelu_conv2d_thin_bf16(x, pw: PackedWeight, bias, slope, pad_mode, act):
     _chk(bias)
     n, h, w, c = x.shape
     k = pw.wf.shape[2]
-    d, oh, ow = conv_desc(n, h, w, c, k, 3, 3, 1, 1, pad_mode)
+    d, y, prof = _conv_fwd_bf16_pre(x, k, 3, 3, 1, 1, " thin", pad_mode, torch.float32)
     if (pw.kh, pw.kw) != (3, 3) or not _L().conv2d_thin_lrelu_supported(C.byref(d)):
         raise FmiError(f"the bf16 Output block takes a 3 x 3 convolution of a 32-channel map to at most 4 channels, got {c} -> {k} "
                        f"k{pw.kh}x{pw.kw} on {h} x {w}")
-    y = torch.empty((n, oh, ow, k), device=x.device, dtype=torch.float32)
-    with _prof(f"conv_fwd_bf16|{n}x{h}x{w} {c}->{k} k3s1 thin", 2.0 * n * oh * ow * k * c * 9):
+    with prof:
         _L().conv2d_thin_lrelu_fwd_bf16(C.byref(d), _p(x), float(slope), _p(pw.wf), _p(bias), _p(y), act, _st())
     return y
 
@@ -1457,16 +1455,15 @@ def conv2d_chan_bf16(x, wnk, kh, kw, stride, pad, scale=None, bias=None, slope=N
     ``se_gate`` -- or (y, None) where the map has fewer than 128 pixels and the library leaves the squeeze to the pooling kernel."""
     _chk(x, wnk, dtype=BF16)
     _chk(scale, bias, slope)
-    n, h, w, c = x.shape
-    k = wnk.shape[0]
+    n, c, k = x.shape[0], x.shape[3], wnk.shape[0]
     if c % 64 or k % 64:
         raise FmiError(f"the bf16 IR-SE convolution needs C % 64 == 0 and K % 64 == 0, got {c} -> {k}")
-    d, oh, ow = conv_desc(n, h, w, c, k, kh, kw, stride, pad)
-    y = torch.empty((n, oh, ow, k), device=x.device, dtype=BF16)
+    d, y, prof = _conv_fwd_bf16_pre(x, k, kh, kw, stride, pad, " +chan")
+    oh, ow = y.shape[1], y.shape[2]
     part = None
     if colsum and oh * ow >= 128:
         part = _parts_ws(x.device, -(-(n * oh * ow) // CHAN_COLSUM_ROWS) * 2 * k)
-    with _prof(f"conv_fwd_bf16|{n}x{h}x{w} {c}->{k} k{kh}s{stride} +chan", 2.0 * n * oh * ow * k * c * kh * kw):
+    with prof:
         _L().conv2d_fwd_chan_bf16(C.byref(d), _p(x), _p(wnk), _p(scale), _p(bias), _p(slope), _p(y), _p(part), 0 if part is None else part.numel(),
                                   _st())
     return (y, part) if colsum else y
@@ -1590,13 +1587,11 @@ def _wnk_of(pw: PackedWeight):
 def conv2d_thin_in_bf16(x, pw: PackedWeight, bias, slope):
     """lrelu(conv3x3(x) + bias, slope) from an fp32 NHWC image with at most 4 channels to a bf16 map of 32 or 64 channels, one launch"""
     _chk(x, bias)
-    n, h, w, c = x.shape
-    k = pw.wf.shape[2]
+    c, k = x.shape[3], pw.wf.shape[2]
     if (pw.kh, pw.kw) != (3, 3) or c > 4 or k not in (32, 64):
         raise FmiError(f"the bf16 stem convolution takes a 3 x 3 layer from at most 4 to 32 or 64 channels, got {c} -> {k} k{pw.kh}x{pw.kw}")
-    d, oh, ow = conv_desc(n, h, w, c, k, 3, 3, 1, 1)
-    y = torch.empty((n, h, w, k), device=x.device, dtype=BF16)
-    with _prof(f"conv_fwd_bf16|{n}x{h}x{w} {c}->{k} k3s1 thin-in", 2.0 * n * h * w * k * c * 9):
+    d, y, prof = _conv_fwd_bf16_pre(x, k, 3, 3, 1, 1, " thin-in")  # 3 x 3, padding 1, stride 1: the output has the input's extent
+    with prof:
         _L().conv2d_thin_in_fwd_bf16(C.byref(d), _p(x), _p(pw.wf), _p(bias), float(slope), _p(y), _st())
     return y
 
@@ -1606,13 +1601,11 @@ def conv2d_enc_bf16(x, pw: PackedWeight, bias, pad, slope=1.0):
     fmi_conv2d_c32_fwd_bf16, the layers with C and K multiples of 64 on fmi_conv2d_fwd_chan_bf16; anything else is refused"""
     _chk(x, dtype=BF16)
     _chk(bias)
-    n, h, w, c = x.shape
-    k = pw.wf.shape[2]
-    d, oh, ow = conv_desc(n, h, w, c, k, pw.kh, pw.kw, 1, pad)
+    c, k = x.shape[3], pw.wf.shape[2]
     wnk = _wnk_of(pw)
     if c == 32 and k in (32, 64):
-        y = torch.empty((n, oh, ow, k), device=x.device, dtype=BF16)
-        with _prof(f"conv_fwd_bf16|{n}x{h}x{w} {c}->{k} k{pw.kh}s1 c32", 2.0 * n * oh * ow * k * c * pw.kh * pw.kw):
+        d, y, prof = _conv_fwd_bf16_pre(x, k, pw.kh, pw.kw, 1, pad, " c32")
+        with prof:
             _L().conv2d_c32_fwd_bf16(C.byref(d), _p(x), _p(wnk), _p(bias), float(slope), _p(y), _st())
         return y
     if c % 64 or k % 64:
@@ -1624,14 +1617,12 @@ def conv2d_enc_bf16(x, pw: PackedWeight, bias, pad, slope=1.0):
 def conv2d_plain_bf16(x, pw: PackedWeight, pad):
     """conv(x) without a bias on a bf16 NHWC map (fmi_conv2d_fwd_bf16), no autograd node"""
     _chk(x, dtype=BF16)
-    n, h, w, c = x.shape
-    k = pw.wf.shape[2]
-    d, oh, ow = conv_desc(n, h, w, c, k, pw.kh, pw.kw, 1, pad)
+    c, k = x.shape[3], pw.wf.shape[2]
+    d, y, prof = _conv_fwd_bf16_pre(x, k, pw.kh, pw.kw, 1, pad)
     if not _L().conv2d_bf16_supported(C.byref(d)):
         raise FmiError(f"the bf16 convolution needs C % 32 == 0 and K % 32 == 0, got {c} -> {k}; these run in fp32 only")
-    y = torch.empty((n, oh, ow, k), device=x.device, dtype=BF16)
     wnk = _wnk_of(pw)
-    with _prof(f"conv_fwd_bf16|{n}x{h}x{w} {c}->{k} k{pw.kh}s1", 2.0 * n * oh * ow * k * c * pw.kh * pw.kw):
+    with prof:
         _L().conv2d_fwd_bf16(C.byref(d), _p(x), _p(wnk), None, _p(y), None, 0, _st())
     return y
 
