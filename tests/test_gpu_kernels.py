@@ -455,7 +455,8 @@ def test_losses_against_golden(dev, FF, golden):
 
 
 def test_contextual_loss_larger(dev, FF):
-    """28x28 feature map as at full size (784 points), random features"""
+    """12x12 feature map (144 points: every 256-stride loop takes one trip), random features; the loops' second and
+    third trips (P up to 520) run kernel by kernel in test_gpu_loss_weight_kernels.py"""
     g = torch.Generator().manual_seed(11)
     from oracle import picnet_cpu as O  # checker
 
