@@ -86,10 +86,14 @@ SIGNATURES = {
     "fmi_conv2d_grouped_fwd_bf16": [PD, i32, i64, vp, vp, vp, f32, vp, vp, vp],
     "fmi_fpn_merge_bf16": [vp] * 4 + [i32] * 6 + [vp],
     "fmi_conv2d_thin_in_fwd_bf16": [PD, vp, vp, vp, f32, vp, vp],
+    "fmi_irse_stem_fwd_bf16": [PD] + [vp] * 11,
+    "fmi_fpn_merge_in_bf16": [vp] * 3 + [i32] * 6 + [vp],
+    "fmi_mask_blend_bf16": [vp] * 4 + [i64, i32, vp],
     "fmi_conv2d_c32_fwd_bf16": [PD, vp, vp, vp, f32, vp, vp],
     "fmi_resblock_tail_bf16": [vp] * 5 + [i32] * 5 + [f32, vp],
     "fmi_picnet_stem_tail_bf16": [vp] * 6 + [i32] * 5 + [f32, vp],
     "fmi_guided_attention_fwd_bf16": [vp] * 5 + [i32] * 5 + [vp],
+    "fmi_guided_attention_sliced_fwd_bf16": [vp] * 5 + [i32] * 5 + [vp],
     "fmi_blur_act_bf16": [vp, vp, vp] + [i32] * 8 + [vp, vp, vp, vp, f32, f32, i32, vp],
     "fmi_torgb_fwd_bf16": [vp, vp, vp, vp, vp, vp, i32, i64, i32, vp],
     "fmi_torgb_bwd_bf16": [vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, i32, i64, i32, vp],

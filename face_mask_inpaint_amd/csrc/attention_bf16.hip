@@ -26,7 +26,12 @@ constexpr int attn_fwd_bf16_lds = 2 * 64 * ((2 * D + 16) + (2 * NCT * 32 + 64));
 // GUIDED (ExampleGuidedAttention, example_guided_att.py:21-41): the V tile is [ref | src], each CT / 2 channels wide -- a 16-byte chunk of
 // a row comes from v (= ref) for the first CT / 2 channels and from v2 (= src) for the rest -- so ONE softmax serves both value maps,
 // and the epilogue blends the first half with ref by the soft mask m [N,T]: o[:CT/2] = (1 - m) (A ref) + m ref, o[CT/2:] = A src.
-template <int D, int NCT, int NW, bool GUIDED = false>
+// CF > 0 (GUIDED only; the pSp shapes, psp_encoders.py:128-132): the value maps are CF channels wide and grid index z is a SLICE of
+// CT / 2 = 128 of them -- the V tile is [ref slice | src slice], read at row pitch CF from channel 128 z, and written to
+// o[..., 128 z : 128 z + 128] and o[..., CF + 128 z : CF + 128 z + 128] of the [N,T,2 CF] output.  Every slice recomputes the scores from
+// the shared q (2 T^2 D against 4 T^2 128 of value work), so the accumulators stay at NCT tiles whatever CF is.  CF == 0 is the
+// unsliced kernel, whose code the slicing does not touch.
+template <int D, int NCT, int NW, bool GUIDED = false, int CF = 0>
 __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_bf16_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ v,
                                                                    uint16_t* __restrict__ o, float* __restrict__ lse,
                                                                    const float* __restrict__ gamma, const uint16_t* __restrict__ res, int T,
@@ -48,9 +53,12 @@ __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_bf16_kernel(const uint16_
   const int n = blockIdx.y;
   const int q0 = blockIdx.x * (NW * 32) + wid * 32;
   const uint16_t* qb = q + (int64_t)n * T * D;
-  constexpr int CV = GUIDED ? CT / 2 : CT;                  // channels of one value map
-  const uint16_t* vb = v + (int64_t)n * T * CV;
-  const uint16_t* vb2 = GUIDED ? v2 + (int64_t)n * T * CV : nullptr;
+  constexpr int CV = GUIDED ? CT / 2 : CT;                  // channels of one value map (of its slice with CF)
+  constexpr int CP = CF ? CF : CV;                          // row pitch of a value map (elements)
+  static_assert(CF == 0 || (GUIDED && CF % CV == 0), "slices are whole halves of the guided V tile");
+  const int coff = CF ? (int)blockIdx.z * CV : 0;           // first channel of this workgroup's slice
+  const uint16_t* vb = v + (int64_t)n * T * CP + coff;
+  const uint16_t* vb2 = GUIDED ? v2 + (int64_t)n * T * CP + coff : nullptr;
 
   // this lane's query fragment: B[k = d][col = query], d = 16 kk + 8 lh + j
   bf16x8_t qp[D / 16];
@@ -78,7 +86,7 @@ __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_bf16_kernel(const uint16_
       const int f = tid + NTH * i;
       const int key = f / (CT / 8), ch = f % (CT / 8);
       if constexpr (GUIDED)
-        rv[i] = *reinterpret_cast<const u32x4_t*>((ch < CV / 8 ? vb + 8 * ch : vb2 + 8 * (ch - CV / 8)) + (int64_t)(k0 + key) * CV);
+        rv[i] = *reinterpret_cast<const u32x4_t*>((ch < CV / 8 ? vb + 8 * ch : vb2 + 8 * (ch - CV / 8)) + (int64_t)(k0 + key) * CP);
       else
         rv[i] = *reinterpret_cast<const u32x4_t*>(vb + (int64_t)(k0 + key) * CT + 8 * ch);
     }
@@ -185,13 +193,13 @@ __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_bf16_kernel(const uint16_
   for (int c = 0; c < NCT; ++c) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const int64_t off = row * CT + c * 32 + 8 * g + 4 * lh;
+      const int64_t off = CF ? row * (2 * CF) + (c < NCT / 2 ? 0 : CF - CV) + coff + c * 32 + 8 * g + 4 * lh : row * CT + c * 32 + 8 * g + 4 * lh;
       float f[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) f[e] = acc[c][4 * g + e] * inv;
       if constexpr (GUIDED) {
         if (c < NCT / 2) {  // (1 - m) (A ref) + m ref in fp32 before the one rounding; m = 1 returns ref bit for bit
-          const uint2 r = *reinterpret_cast<const uint2*>(v + row * CV + c * 32 + 8 * g + 4 * lh);
+          const uint2 r = *reinterpret_cast<const uint2*>(v + row * CP + coff + c * 32 + 8 * g + 4 * lh);
           const float om = 1.f - mk;
           f[0] = fmaf(om, f[0], mk * bf_lo(r.x));
           f[1] = fmaf(om, f[1], mk * bf_hi(r.x));
@@ -250,5 +258,25 @@ extern "C" int fmi_guided_attention_fwd_bf16(const uint16_t* q, const uint16_t* 
                                                         (const uint16_t*)nullptr, T, src, mask)
   const int rc = nw == 8 ? ATTG16_LAUNCH(8) : ATTG16_LAUNCH(4);
 #undef ATTG16_LAUNCH
+  return rc != FMI_OK ? rc : fmi_launch_status();
+}
+
+// The same at the pSp encoder's shapes (psp_encoders.py:128-132): (D, C) = (64, 256) is attention2, (128, 512) attention1.  One workgroup
+// per (query tile, sample, slice of 128 channels): C / 128 slices in grid z, each recomputing the scores from the shared q.  Arguments,
+// checks and the wave dispatch are fmi_guided_attention_fwd_bf16's, whose own accepted shape stays (32, 128).
+extern "C" int fmi_guided_attention_sliced_fwd_bf16(const uint16_t* q, const uint16_t* src, const uint16_t* ref, const float* mask, uint16_t* out,
+                                                    int N, int T, int D, int C, int waves, void* stream) {
+  if (!q || !src || !ref || !mask || !out || N <= 0 || T <= 0 || D <= 0 || C <= 0) return FMI_ERR_BAD_ARG;
+  if (T % 128 != 0 || !((D == 64 && C == 256) || (D == 128 && C == 512)) || N > 65535) return FMI_ERR_UNSUPPORTED;
+  if (waves != 0 && waves != 4 && !(waves == 8 && T % 256 == 0)) return FMI_ERR_UNSUPPORTED;
+  if ((((uintptr_t)q | (uintptr_t)src | (uintptr_t)ref | (uintptr_t)out) & 15) != 0 || ((uintptr_t)mask & 3) != 0) return FMI_ERR_BAD_ARG;
+  const int nw = waves ? waves : fmi_guided_attention_fwd_bf16_waves(N, T);
+  const dim3 grid(T / (nw * 32), N, C / 128), block(nw * 64);
+  hipStream_t st = (hipStream_t)stream;
+#define ATTGS_LAUNCH(DD, CC, WW)                                                                                                                  \
+  fmi_launch_lds<attn_fwd_bf16_kernel<DD, 8, WW, true, CC>>(grid, block, attn_fwd_bf16_lds<DD, 8>, st, q, ref, out, (float*)nullptr, (const float*)nullptr, \
+                                                            (const uint16_t*)nullptr, T, src, mask)
+  const int rc = C == 256 ? (nw == 8 ? ATTGS_LAUNCH(64, 256, 8) : ATTGS_LAUNCH(64, 256, 4)) : (nw == 8 ? ATTGS_LAUNCH(128, 512, 8) : ATTGS_LAUNCH(128, 512, 4));
+#undef ATTGS_LAUNCH
   return rc != FMI_OK ? rc : fmi_launch_status();
 }

@@ -82,6 +82,149 @@ extern "C" int fmi_conv2d_thin_in_fwd_bf16(const fmi_conv_desc* d, const float* 
   return fmi_launch_status();
 }
 
+// ---- the pSp encoder's stem in one launch (psp_encoders.py:59-61 and block 0's first BatchNorm, helpers.py:86 / :108) ----------------
+// a = prelu(conv3x3(x) * scale + shift, slope), y = bf16(a), z = bf16(a * scale0 + shift0).  enc_thin_in_kernel's layout -- the weights in
+// LDS padded to 4 input channels, the five per-channel vectors beside them ((36 + 5) K floats, dynamic: K is a run-time value), one
+// thread = 8 output channels, one fma chain over the 27 (36) taps, 16-byte stores -- but a thread carries P pixels through the chain: at
+// one pixel per thread the kernel is bound by its LDS reads (two ds_read_b128 per 8 fmas, 864 bytes read per 32 bytes written), with P
+// pixels a weight fragment is read once for all of them.  A workgroup takes chunks of 256 P items (item = pixel * K/8 + channel group);
+// thread t has items t + 256 j, so with K/8 a divisor of 256 the channel group is the same for every j (the host gives P = 1
+// otherwise), the pixels of one j are consecutive across a wave (1 KB stores at K = 64) and P 2048 / K apart within a thread.  A tap
+// outside the map contributes fma(0, w, acc): the sum of the taps inside, in the order the one-pixel form adds them.  Both stores of a
+// pixel leave from the same fp32 a; a32 (debug, may be NULL) receives it.  What is left after that is VALU work, so the chain runs on
+// packed fp32 fmas (two channels per instruction, the same two roundings), x is addressed by 32-bit byte offsets from the uniform base
+// (one add per load; the host refuses an image of 4 GiB or more) and the roundings are v_cvt_pk_bf16_f32 (round to nearest even).
+typedef float stem_f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void stem_load4(const float* p, stem_f2 (&f)[4]) {
+  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+  f[0] = stem_f2{a.x, a.y}, f[1] = stem_f2{a.z, a.w}, f[2] = stem_f2{b.x, b.y}, f[3] = stem_f2{b.z, b.w};
+}
+template <int P>
+__global__ void __launch_bounds__(256) irse_stem_fused_kernel(const float* __restrict__ x, const float* __restrict__ wf, const float* __restrict__ scale,
+                                                              const float* __restrict__ shift, const float* __restrict__ slope,
+                                                              const float* __restrict__ scale0, const float* __restrict__ shift0, uint4* __restrict__ y,
+                                                              uint4* __restrict__ z, float* __restrict__ a32, int H, int W, int C, int K, int64_t total,
+                                                              int64_t chunks) {
+  extern __shared__ __attribute__((aligned(16))) float stem_lds[];  // [9][4][K] weights, then scale, shift, slope, scale0, shift0 [K] each
+  float* wl = stem_lds;
+  float* pl = stem_lds + 36 * K;
+  for (int i = threadIdx.x; i < 36 * K; i += 256) {
+    const int k = i % K, c = (i / K) & 3, t = i / (4 * K);
+    wl[i] = c < C ? wf[((int64_t)t * C + c) * K + k] : 0.f;
+  }
+  for (int i = threadIdx.x; i < K; i += 256) {
+    pl[i] = scale[i], pl[K + i] = shift[i], pl[2 * K + i] = slope[i], pl[3 * K + i] = scale0[i], pl[4 * K + i] = shift0[i];
+  }
+  __syncthreads();
+  const int K8 = K / 8;
+  for (int64_t ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
+    const int64_t i0 = ch * (256 * P) + threadIdx.x;  // this thread's items: i0 + 256 j
+    const int c8 = (int)(i0 % K8);
+    uint32_t xoff[P];  // byte offset of the pixel in x
+    int xx[P], yy[P];
+    bool live[P];
+    stem_f2 acc[P][4];
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+      const int64_t i = i0 + 256 * j;
+      live[j] = i < total;
+      const int64_t pix = i / K8;
+      xx[j] = (int)(pix % W), yy[j] = (int)((pix / W) % H);
+      xoff[j] = (uint32_t)(pix * C) * 4u;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[j][e] = stem_f2{0.f, 0.f};
+    }
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const int dy = t / 3 - 1, dx = t % 3 - 1;
+      const uint32_t toff = (uint32_t)((dy * W + dx) * C) * 4u;  // uniform; wraps for the taps before the pixel, as the sum below does
+      // zero padding: a tap outside the map (and a dead item) reads x[0] and counts as 0 -- every load is unconditional, so the loads of
+      // a tap leave together instead of one exec-masked block, with a wait of its own, per load
+      bool ok[P];
+      uint32_t off[P];
+#pragma unroll
+      for (int j = 0; j < P; ++j) {
+        ok[j] = live[j] & ((unsigned)(yy[j] + dy) < (unsigned)H) & ((unsigned)(xx[j] + dx) < (unsigned)W);
+        off[j] = ok[j] ? xoff[j] + toff : 0u;
+      }
+      float xv[4][P];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if (c >= C) break;
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+          const float v = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(x) + (uint32_t)(off[j] + 4u * c));
+          xv[c][j] = ok[j] ? v : 0.f;
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if (c >= C) break;
+        stem_f2 w[4];
+        stem_load4(wl + (t * 4 + c) * K + c8 * 8, w);
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+          const stem_f2 x2 = stem_f2{xv[c][j], xv[c][j]};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[j][e] = __builtin_elementwise_fma(x2, w[e], acc[j][e]);
+        }
+      }
+    }
+    stem_f2 sc[4], sh[4], sl[4], sc0[4], sh0[4];
+    stem_load4(pl + c8 * 8, sc);
+    stem_load4(pl + K + c8 * 8, sh);
+    stem_load4(pl + 2 * K + c8 * 8, sl);
+    stem_load4(pl + 3 * K + c8 * 8, sc0);
+    stem_load4(pl + 4 * K + c8 * 8, sh0);
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+      if (!live[j]) continue;
+      const int64_t i = i0 + 256 * j;
+      float a[8], b[8];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const stem_f2 v = __builtin_elementwise_fma(acc[j][e], sc[e], sh[e]), n = sl[e] * v;
+        a[2 * e] = v.x > 0.f ? v.x : n.x, a[2 * e + 1] = v.y > 0.f ? v.y : n.y;
+        const stem_f2 zz = stem_f2{a[2 * e], a[2 * e + 1]} * sc0[e] + sh0[e];  // fmi_irse_stem_bf16's expression on the same fp32 a
+        b[2 * e] = zz.x, b[2 * e + 1] = zz.y;
+      }
+      y[i] = bf_pack8_hw(a);
+      if (a32) {
+        float4* o = reinterpret_cast<float4*>(a32 + i * 8);
+        o[0] = make_float4(a[0], a[1], a[2], a[3]);
+        o[1] = make_float4(a[4], a[5], a[6], a[7]);
+      }
+      z[i] = bf_pack8_hw(b);
+    }
+  }
+}
+#define FMI_STEM_PIXELS 4 /* pixels a thread of the fused stem carries where K / 8 divides 256 (16 x 256^2 x 3 -> 64: 1, 2, 4, 8 measured) */
+extern "C" int fmi_irse_stem_fwd_bf16(const fmi_conv_desc* d, const float* x, const float* wf, const float* scale, const float* shift,
+                                      const float* slope, const float* scale0, const float* shift0, uint16_t* y, uint16_t* z, float* a32,
+                                      void* stream) {
+  int rc = enc_check_desc(d);
+  if (rc) return rc;
+  if (!x || !wf || !scale || !shift || !slope || !scale0 || !shift0 || !y || !z) return FMI_ERR_BAD_ARG;
+  if (d->C > 4 || d->K % 8 != 0 || d->K > 256 || d->kh != 3 || d->pad != 1) return FMI_ERR_UNSUPPORTED;
+  if ((int64_t)d->N * d->H * d->W * d->C * 4 > 0xffffffffLL) return FMI_ERR_UNSUPPORTED;  // x is addressed by 32-bit byte offsets
+  if ((((uintptr_t)x | (uintptr_t)wf | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)slope | (uintptr_t)scale0 | (uintptr_t)shift0) & 3) != 0 ||
+      !fmi_al16(y) || !fmi_al16(z) || !fmi_al16(a32))
+    return FMI_ERR_UNSUPPORTED;
+  const int64_t total = (int64_t)d->N * d->H * d->W * (d->K / 8);
+  const int pp = 256 % (d->K / 8) == 0 ? FMI_STEM_PIXELS : 1;
+  const int64_t chunks = ceil_div64(total, 256 * pp);
+  const dim3 grid((unsigned)(chunks < 2048 ? chunks : 2048)), block(256);
+  const size_t lds = (size_t)(41 * d->K) * sizeof(float);
+  hipStream_t st = (hipStream_t)stream;
+#define STEM_LAUNCH(PP) \
+  hipLaunchKernelGGL(irse_stem_fused_kernel<PP>, grid, block, lds, st, x, wf, scale, shift, slope, scale0, shift0, (uint4*)y, (uint4*)z, a32, d->H, d->W, \
+                     d->C, d->K, total, chunks)
+  if (pp == FMI_STEM_PIXELS) STEM_LAUNCH(FMI_STEM_PIXELS);
+  else STEM_LAUNCH(1);
+#undef STEM_LAUNCH
+  return fmi_launch_status();
+}
+
 // ---- the 32-channel layers: y = lrelu(conv(x) + b, slope), x bf16 [N,H,W,32], wnk bf16 [K][taps][32], y bf16 [N,H,W,K] -------------
 // O^T[k][pixel] = sum_tap W_tap[k][c] X_tap^T[c][pixel] on v_mfma_f32_32x32x16_bf16: a wave owns tiles of 32 consecutive pixels (rows of
 // the flattened N H W index, so any W), the A fragments of ALL taps and output channels stay in its registers for the launch

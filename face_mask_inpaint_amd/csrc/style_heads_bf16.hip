@@ -6,6 +6,8 @@
 //     FMI_STYLE_SKINNY_ROWS rows -- at batch 8 the layers that produce 4^2, 2^2 and 1^2 maps and the linear: 128, 32, 8 and 8 rows --
 //     cost what reading each head's weights costs, and take the weight-streaming kernel below.
 //   * fmi_fpn_merge_bf16: _upsample_add and the fp32 -> bf16 hand-over of a level map in one pass.
+//   * fmi_fpn_merge_in_bf16 and fmi_mask_blend_bf16: _upsample_add from bf16 maps and the mask blend of the pyramid levels
+//     (psp_encoders.py:135-138) for the bf16 neck (psp_encoders.neck_bf16), which hands the heads bf16 level maps.
 // Parameters and accumulation are fp32, every bf16 value is rounded once, nothing is accumulated through atomics.
 #include "bf16x8.h"
 
@@ -170,13 +172,17 @@ extern "C" int fmi_conv2d_grouped_fwd_bf16(const fmi_conv_desc* d, int G, int64_
 // one thread = 8 channels of one output pixel.  align_corners=True: source coordinate y (CH - 1) / (H - 1), split into its integer part
 // and the two weights by integer arithmetic -- rem / (H - 1) and (H - 1 - rem) / (H - 1), one rounding each -- so the weights carry no
 // error that grows with the coordinate.
-__global__ void __launch_bounds__(256) fpn_merge_kernel(const float* __restrict__ lat, const float* __restrict__ coarse, float* __restrict__ p32,
+// TIN is the element type of lateral and coarse: float (fmi_fpn_merge_bf16) or bf16 bits (fmi_fpn_merge_in_bf16, widened exactly).
+__device__ __forceinline__ void fpn_load8(const float* p, float (&f)[8]) { bf_load8f(p, f); }
+__device__ __forceinline__ void fpn_load8(const uint16_t* p, float (&f)[8]) { bf_unpack8(*reinterpret_cast<const uint4*>(p), f); }
+template <typename TIN>
+__global__ void __launch_bounds__(256) fpn_merge_kernel(const TIN* __restrict__ lat, const TIN* __restrict__ coarse, float* __restrict__ p32,
                                                         uint4* __restrict__ p16, int H, int W, int CH, int CW, int C8, int64_t total) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int c8 = (int)(i % C8);
     const int64_t pix = i / C8;
     float f[8];
-    bf_load8f(lat + i * 8, f);
+    fpn_load8(lat + i * 8, f);
     if (coarse) {
       const int ox = (int)(pix % W);
       const int64_t t = pix / W;
@@ -187,12 +193,12 @@ __global__ void __launch_bounds__(256) fpn_merge_kernel(const float* __restrict_
       const int y0 = ny / dy, x0 = nx / dx, ry = ny - y0 * dy, rx = nx - x0 * dx;
       const int y1 = y0 + 1 < CH ? y0 + 1 : CH - 1, x1 = x0 + 1 < CW ? x0 + 1 : CW - 1;
       const float fy = (float)ry / (float)dy, gy = (float)(dy - ry) / (float)dy, fx = (float)rx / (float)dx, gx = (float)(dx - rx) / (float)dx;
-      const float* base = coarse + (n * CH * CW) * (int64_t)C8 * 8 + c8 * 8;
+      const TIN* base = coarse + (n * CH * CW) * (int64_t)C8 * 8 + c8 * 8;
       float a00[8], a01[8], a10[8], a11[8];
-      bf_load8f(base + ((int64_t)y0 * CW + x0) * C8 * 8, a00);
-      bf_load8f(base + ((int64_t)y0 * CW + x1) * C8 * 8, a01);
-      bf_load8f(base + ((int64_t)y1 * CW + x0) * C8 * 8, a10);
-      bf_load8f(base + ((int64_t)y1 * CW + x1) * C8 * 8, a11);
+      fpn_load8(base + ((int64_t)y0 * CW + x0) * C8 * 8, a00);
+      fpn_load8(base + ((int64_t)y0 * CW + x1) * C8 * 8, a01);
+      fpn_load8(base + ((int64_t)y1 * CW + x0) * C8 * 8, a10);
+      fpn_load8(base + ((int64_t)y1 * CW + x1) * C8 * 8, a11);
 #pragma unroll
       for (int e = 0; e < 8; ++e) f[e] += gy * (gx * a00[e] + fx * a01[e]) + fy * (gx * a10[e] + fx * a11[e]);
     }
@@ -211,7 +217,44 @@ extern "C" int fmi_fpn_merge_bf16(const float* lateral, const float* coarse, flo
   if (C % 8 != 0 || !fmi_al16(lateral) || !fmi_al16(coarse) || !fmi_al16(p32) || !fmi_al16(p16)) return FMI_ERR_UNSUPPORTED;
   if ((int64_t)H * CH > 0x7fffffffLL || (int64_t)W * CW > 0x7fffffffLL) return FMI_ERR_UNSUPPORTED;
   const int64_t total = (int64_t)N * H * W * (C / 8);
-  hipLaunchKernelGGL(fpn_merge_kernel, dim3(fmi_bw_grid(total, 256 * 2)), dim3(256), 0, (hipStream_t)stream, lateral, coarse, p32, (uint4*)p16, H, W,
+  hipLaunchKernelGGL(fpn_merge_kernel<float>, dim3(fmi_bw_grid(total, 256 * 2)), dim3(256), 0, (hipStream_t)stream, lateral, coarse, p32, (uint4*)p16, H, W,
                      CH, CW, C / 8, total);
+  return fmi_launch_status();
+}
+
+// the same merge from bf16 lateral and coarse maps (the lateral convolution's and the level above's bf16 outputs): same integer bilinear
+// weights, fp32 arithmetic, one rounding; there is no fp32 output and no plain-conversion form (a bf16 map needs no hand-over)
+extern "C" int fmi_fpn_merge_in_bf16(const uint16_t* lateral, const uint16_t* coarse, uint16_t* p16, int N, int H, int W, int CH, int CW, int C,
+                                     void* stream) {
+  if (!lateral || !coarse || !p16 || N <= 0 || H <= 0 || W <= 0 || C <= 0 || CH <= 0 || CW <= 0) return FMI_ERR_BAD_ARG;
+  if (C % 8 != 0 || !fmi_al16(lateral) || !fmi_al16(coarse) || !fmi_al16(p16)) return FMI_ERR_UNSUPPORTED;
+  if ((int64_t)H * CH > 0x7fffffffLL || (int64_t)W * CW > 0x7fffffffLL) return FMI_ERR_UNSUPPORTED;
+  const int64_t total = (int64_t)N * H * W * (C / 8);
+  hipLaunchKernelGGL(fpn_merge_kernel<uint16_t>, dim3(fmi_bw_grid(total, 256 * 2)), dim3(256), 0, (hipStream_t)stream, lateral, coarse, (float*)nullptr,
+                     (uint4*)p16, H, W, CH, CW, C / 8, total);
+  return fmi_launch_status();
+}
+
+// ---- mask blend (psp_encoders.py:135-138) -----------------------------------------------------------------------------------------------
+// y = bf16(m r + (1 - m) c) from bf16 r, c [rows][C] and fp32 m [rows], one thread = 8 channels of one pixel.  fma(m, r, (1 - m) c) in
+// fp32: m == 1 leaves r and m == 0 leaves c, and a bf16 value survives its own rounding, so both return their operand bit for bit.
+__global__ void __launch_bounds__(256) mask_blend_kernel(const uint4* __restrict__ r, const uint4* __restrict__ c, const float* __restrict__ m,
+                                                         uint4* __restrict__ y, int C8, int64_t total) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const float mk = m[i / C8], om = 1.f - mk;
+    float a[8], b[8];
+    bf_unpack8(r[i], a);
+    bf_unpack8(c[i], b);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a[e] = mk == 1.f ? a[e] : (mk == 0.f ? b[e] : fmaf(mk, a[e], om * b[e]));  // the selects keep a -0's sign
+    y[i] = bf_pack8(a);
+  }
+}
+extern "C" int fmi_mask_blend_bf16(const uint16_t* r, const uint16_t* c, const float* m, uint16_t* y, int64_t rows, int C, void* stream) {
+  if (!r || !c || !m || !y || rows <= 0 || C <= 0) return FMI_ERR_BAD_ARG;
+  if (C % 8 != 0 || !fmi_al16(r) || !fmi_al16(c) || !fmi_al16(y) || ((uintptr_t)m & 3) != 0 || rows > 0x7fffffffffffLL / C) return FMI_ERR_UNSUPPORTED;
+  const int64_t total = rows * (C / 8);
+  hipLaunchKernelGGL(mask_blend_kernel, dim3(fmi_bw_grid(total, 256 * 2)), dim3(256), 0, (hipStream_t)stream, (const uint4*)r, (const uint4*)c, m, (uint4*)y,
+                     C / 8, total);
   return fmi_launch_status();
 }

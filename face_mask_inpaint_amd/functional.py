@@ -1660,23 +1660,68 @@ def picnet_stem_tail_bf16(h, img, wb, bias, slope, raw=True, act=True):
     return y_raw, y_act
 
 
-GUIDED_ATTENTION_BF16_SHAPES = ((32, 128),)  # (d_qk, C) of fmi_guided_attention_fwd_bf16
+# (d_qk, C) of fmi_guided_attention_fwd_bf16 (the first) and of fmi_guided_attention_sliced_fwd_bf16 (the pSp encoder's two)
+GUIDED_ATTENTION_BF16_SHAPES = ((32, 128), (64, 256), (128, 512))
 
 
-def guided_attention_bf16(q, src, ref, m):
+def guided_attention_bf16(q, src, ref, m, waves=0):
     """cat[(1 - m) (A ref) + m ref, A src] with A = softmax(q q^T) evaluated once, one launch: q [N,T,D], src / ref [N,T,C] bf16, m fp32
-    [N,T] -> bf16 [N,T,2C]"""
+    [N,T] -> bf16 [N,T,2C].  ``waves``: 0 = the library's choice, 4 or 8 (T % 256 == 0) forces the workgroup size (tests)."""
     _chk(q, src, ref, dtype=BF16)
     _chk(m)
     n, t, d = q.shape
     c = src.shape[2]
     if t % 128 or (d, c) not in GUIDED_ATTENTION_BF16_SHAPES or ref.shape != src.shape or m.numel() != n * t:
-        raise FmiError(f"the bf16 guided attention needs a token count that is a multiple of 128 and (d_qk, C) = (32, 128), got T = {t}, "
-                       f"(d_qk, C) = ({d}, {c}); these run in fp32 only")
+        raise FmiError(f"the bf16 guided attention needs a token count that is a multiple of 128 and (d_qk, C) in "
+                       f"{set(GUIDED_ATTENTION_BF16_SHAPES)}, got T = {t}, (d_qk, C) = ({d}, {c}); these run in fp32 only")
     out = torch.empty((n, t, 2 * c), device=q.device, dtype=BF16)
-    with _prof(f"attn_guided_fwd_bf16|T{t} d{d} C{c} b{n}", 2.0 * n * t * t * (d + 2 * c)):
-        _L().guided_attention_fwd_bf16(_p(q), _p(src), _p(ref), _p(m), _p(out), n, t, d, c, 0, _st())
+    with _prof(f"attn_guided_fwd_bf16|T{t} d{d} C{c} b{n}", 2.0 * n * t * t * (d * (c // 128) + 2 * c)):
+        fwd = _L().guided_attention_fwd_bf16 if c == 128 else _L().guided_attention_sliced_fwd_bf16
+        fwd(_p(q), _p(src), _p(ref), _p(m), _p(out), n, t, d, c, int(waves), _st())
     return out
+
+
+# ---- bf16 stem and neck of the pSp encoder for inference (GradualStyleEncoder(encoder_neck_eval_dtype='bf16'), psp_encoders.neck_bf16):
+# no autograd nodes -- the caller has refused grad mode.  The image and the mask are fp32, every map between them and the heads bf16. ----
+def irse_stem_fused_bf16(x, pw: PackedWeight, scale, shift, slope, scale0, shift0, debug=False):
+    """the pSp stem in one launch (fmi_irse_stem_fwd_bf16): a = prelu(conv3x3(x) * scale + shift, slope) from the fp32 NHWC image with at
+    most 4 channels; returns (bf16 a, bf16 a * scale0 + shift0) -- block 0's input and its first BatchNorm -- and with ``debug`` the
+    fp32 a as a third value"""
+    _chk(x, scale, shift, slope, scale0, shift0)
+    c, k = x.shape[3], pw.wf.shape[2]
+    if (pw.kh, pw.kw) != (3, 3) or c > 4 or k % 8 or k > 256 or any(t.numel() != k for t in (scale, shift, slope, scale0, shift0)):
+        raise FmiError(f"the fused pSp stem takes a 3 x 3 layer from at most 4 to K % 8 == 0 (<= 256) channels with [K] vectors, got {c} -> {k} "
+                       f"k{pw.kh}x{pw.kw}")
+    d, y, prof = _conv_fwd_bf16_pre(x, k, 3, 3, 1, 1, " stem")
+    z = torch.empty_like(y)
+    a = torch.empty(y.shape, device=x.device, dtype=torch.float32) if debug else None
+    with prof:
+        _L().irse_stem_fwd_bf16(C.byref(d), _p(x), _p(pw.wf), _p(scale), _p(shift), _p(slope), _p(scale0), _p(shift0), _p(y), _p(z), _p(a), _st())
+    return (y, z, a) if debug else (y, z)
+
+
+def mask_blend_bf16(m, r, c):
+    """bf16(m r + (1 - m) c) in one launch (fmi_mask_blend_bf16): r, c bf16 [N,H,W,C], m fp32 [N,H,W]; m == 1 returns r, m == 0 returns c"""
+    _chk(r, c, dtype=BF16)
+    _chk(m)
+    ch = r.shape[-1]
+    if c.shape != r.shape or ch % 8 or m.numel() * ch != r.numel():
+        raise FmiError(f"mask_blend_bf16: r {tuple(r.shape)}, c {tuple(c.shape)}, m {tuple(m.shape)} (C % 8 == 0)")
+    y = torch.empty_like(r)
+    _L().mask_blend_bf16(_p(r), _p(c), _p(m), _p(y), m.numel(), ch, _st())
+    return y
+
+
+def fpn_merge_in_bf16(lateral, coarse):
+    """bf16(bilinear(coarse, align_corners=True, to lateral's size) + lateral) from bf16 NHWC maps in one pass (fmi_fpn_merge_in_bf16)"""
+    _chk(lateral, coarse, dtype=BF16)
+    n, h, w, c = lateral.shape
+    if coarse.dim() != 4 or coarse.shape[0] != n or coarse.shape[3] != c or c % 8:
+        raise FmiError(f"fpn_merge_in_bf16: lateral {tuple(lateral.shape)}, coarse {tuple(coarse.shape)} (C % 8 == 0)")
+    p16 = torch.empty_like(lateral)
+    with _prof(f"fpn_merge_in_bf16|{n}x{h}x{w}x{c}", 9.0 * lateral.numel()):
+        _L().fpn_merge_in_bf16(_p(lateral), _p(coarse), _p(p16), n, h, w, coarse.shape[1], coarse.shape[2], c, _st())
+    return p16
 
 
 class _Resize(torch.autograd.Function):

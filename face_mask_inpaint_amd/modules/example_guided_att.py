@@ -20,18 +20,20 @@ class ExampleGuidedAttention(nn.Module):
         if out_channels is not None:
             self.out_conv = nn.Conv2d(in_channels * 2, out_channels, 1)
 
-    def bf16_unfit(self):
-        """why the bf16 form cannot run this module (None: it can)"""
+    def bf16_unfit(self, shapes=None):
+        """why the bf16 form cannot run this module (None: it can); ``shapes``: a caller's narrower set of (img_f // 4, img_f)"""
         c = self.conv.in_channels
-        if (c // 4, c) not in FF.GUIDED_ATTENTION_BF16_SHAPES:
-            return f"(img_f // 4, img_f) in {set(FF.GUIDED_ATTENTION_BF16_SHAPES)} at the guided attention (got ({c // 4}, {c}))"
-        if self.out_channels is not None:
-            return "a guided attention without out_conv"
+        shapes = FF.GUIDED_ATTENTION_BF16_SHAPES if shapes is None else shapes
+        if (c // 4, c) not in shapes:
+            return f"(img_f // 4, img_f) in {set(shapes)} at the guided attention (got ({c // 4}, {c}))"
+        if self.out_channels is not None and self.out_channels % 64:
+            return f"an out_conv whose width is a multiple of 64 (got {self.out_channels})"
         return None
 
     def _nhwc_bf16(self, mask_nhw, src, ref):
         """inference on bf16 feature maps, two launches: the query convolution, then both attentions from one softmax with the mask blend
-        in the epilogue (fmi_guided_attention_fwd_bf16); the result is bf16 [N,H,W,2C]"""
+        in the epilogue (fmi_guided_attention_fwd_bf16, at the pSp widths fmi_guided_attention_sliced_fwd_bf16); the result is bf16 [N,H,W,2C] -- or, with out_conv, a third launch (the 1x1
+        convolution with its bias on fmi_conv2d_fwd_chan_bf16) and bf16 [N,H,W,out_channels]"""
         n, h, w, c = src.shape
         unfit = self.bf16_unfit()
         if unfit or ref.dtype != torch.bfloat16 or (h * w) % 128:
@@ -39,7 +41,10 @@ class ExampleGuidedAttention(nn.Module):
                               f" (got {h} x {w} = {h * w} tokens); these run in fp32 only")
         q = FF.conv2d_plain_bf16(src, packed(self.conv), 0)
         out = FF.guided_attention_bf16(q.view(n, h * w, -1), src.view(n, h * w, c), ref.view(n, h * w, c), mask_nhw.contiguous().view(n, h * w))
-        return out.view(n, h, w, 2 * c)
+        out = out.view(n, h, w, 2 * c)
+        if self.out_channels is not None:
+            out = FF.conv2d_chan_bf16(out, FF._wnk_of(packed(self.out_conv)), 1, 1, 1, 0, bias=self.out_conv.bias.detach())
+        return out
 
     def nhwc(self, mask_nhw, src, ref):
         """mask [N,H,W] (soft), src / ref [N,H,W,C] -> [N,H,W,2C] (or out_channels)."""

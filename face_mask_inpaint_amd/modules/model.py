@@ -55,7 +55,7 @@ class ReferenceFill(nn.Module):
         if use_att:
             self.attention = ExampleGuidedAttention(encoder_params["img_f"])
             if feature_dtype == torch.bfloat16:
-                unfit = self.attention.bf16_unfit()
+                unfit = self.attention.bf16_unfit(shapes=((32, 128),))  # the one width the bf16 ReferenceFill has been validated at
                 if unfit:
                     raise FF.FmiError(f"ReferenceFill(feature_dtype=torch.bfloat16) needs {unfit}; these run in fp32 only")
                 object.__setattr__(self.attention.conv, "_fmi_no_w3", True)  # runs on bf16 activations: no fp32 piece images of its pack

@@ -87,6 +87,32 @@ def style_level_bf16(heads, p16, latents, first=0, holder=None):
     return FF.conv2d_grouped_bf16(x, lin_w, lin_b, 1, 1, 0, shared=False, out=latents, first=first)
 
 
+def neck_bf16(attention1, attention2, latlayer1, latlayer2, c1, c2, c3, r1=None, r2=None, r3=None, mask=None):
+    """The neck of the pSp encoder (psp_encoders.py:126-147: mask resizes, guided attention or mask blend at the three levels, lateral
+    1x1 convolutions, _upsample_add) on bf16 NHWC maps, inference only: c1 / c2 / c3 are the source taps ([N,64,64,128], [N,32,32,256],
+    [N,16,16,512] at full widths), r1 / r2 / r3 the reference taps and ``mask`` the fp32 [N,H,W] soft mask -- all four None for a forward
+    without a reference.  ``attention1`` / ``attention2`` (ExampleGuidedAttention with out_conv) work on c3 / c2; None: the plain blend
+    there, as with use_attention off.  Returns the three bf16 level maps the heads read (coarse, middle, fine).  No fp32 activation map
+    is written: 3 launches per attention, 1 per blend, 2 per lateral level.  The caller holds weight_scope over the modules and has
+    refused grad mode."""
+    if r3 is not None:
+        m = mask.contiguous().unsqueeze(-1)  # [N,H,W,1]
+        n = m.shape[0]
+        mask_3 = FF.resize_bilinear(m, r3.shape[1], r3.shape[2]).view(n, r3.shape[1], r3.shape[2])
+        mask_2 = FF.resize_bilinear(m, r2.shape[1], r2.shape[2]).view(n, r2.shape[1], r2.shape[2])
+        mask_1 = FF.resize_bilinear(m, r1.shape[1], r1.shape[2]).view(n, r1.shape[1], r1.shape[2])
+        c3 = attention1.nhwc(mask_3, c3, r3) if attention1 is not None else FF.mask_blend_bf16(mask_3, r3, c3)
+        c2 = attention2.nhwc(mask_2, c2, r2) if attention2 is not None else FF.mask_blend_bf16(mask_2, r2, c2)
+        c1 = FF.mask_blend_bf16(mask_1, r1, c1)
+
+    def lateral(conv, x):
+        return FF.conv2d_chan_bf16(x, helpers._wnk(conv), 1, 1, 1, 0, bias=None if conv.bias is None else conv.bias.detach())
+
+    p2 = FF.fpn_merge_in_bf16(lateral(latlayer1, c2), c3)
+    p1 = FF.fpn_merge_in_bf16(lateral(latlayer2, c1), p2)
+    return c3, p2, p1
+
+
 class GradualStyleEncoder(Module):
     def __init__(self, num_layers, mode="ir", opts=None, *, _widths=(64, 64, 128, 256, 512), _spatial=(16, 32, 64)):
         """``_widths`` (stem + the four stage depths) and ``_spatial`` (map sizes feeding the coarse / middle / fine heads)
@@ -127,6 +153,17 @@ class GradualStyleEncoder(Module):
         if sdt not in ("fp32", "bf16"):
             raise FF.FmiError(f"style_heads_eval_dtype must be 'fp32' or 'bf16', got {sdt!r}")
         self.eval_heads_dtype = torch.bfloat16 if sdt == "bf16" else torch.float32
+        # opts.encoder_neck_eval_dtype ("fp32" default / "bf16"): the stem and the neck of an EVAL-mode forward -- bf16 runs the stem as one
+        # launch that writes the body's two bf16 inputs, takes the body's bf16 outputs as the taps and keeps the attention blocks, the
+        # blends, the lateral convolutions and the merges on bf16 maps (neck_bf16; no backward).  It consumes bf16 taps and produces bf16
+        # level maps, so it needs both options above to be bf16: there is no mixed form
+        ndt = getattr(opts, "encoder_neck_eval_dtype", "fp32")
+        if ndt not in ("fp32", "bf16"):
+            raise FF.FmiError(f"encoder_neck_eval_dtype must be 'fp32' or 'bf16', got {ndt!r}")
+        if ndt == "bf16" and (edt != "bf16" or sdt != "bf16"):
+            raise FF.FmiError("encoder_neck_eval_dtype='bf16' needs encoder_eval_dtype='bf16' and style_heads_eval_dtype='bf16' (got "
+                              f"{edt!r} and {sdt!r}): the neck reads the body's bf16 taps and writes the heads' bf16 level maps")
+        self.eval_neck_dtype = torch.bfloat16 if ndt == "bf16" else torch.float32
         self._widths = tuple(_widths)
         self.use_attention = opts.use_attention
         if opts.use_attention:
@@ -134,8 +171,10 @@ class GradualStyleEncoder(Module):
             self.attention2 = ExampleGuidedAttention(w3, out_channels=w3)
 
     def _pyramid(self, x):
-        x = run_conv(self.input_layer[0], x)
-        x = FF.prelu(batch_norm(self.input_layer[1], x), self.input_layer[2].weight)
+        neck16 = self._neck_bf16()
+        if not neck16:
+            x = run_conv(self.input_layer[0], x)
+            x = FF.prelu(batch_norm(self.input_layer[1], x), self.input_layer[2].weight)
         b16 = self.body_dtype == torch.bfloat16 and self.training
         infer16 = self._infer_bf16()
         if getattr(self, "_fmi_body_b16", None) != (b16 or infer16):  # the body's convolutions need no fp32 piece images while they run on bf16 activations
@@ -143,6 +182,17 @@ class GradualStyleEncoder(Module):
                 if isinstance(m, nn.Conv2d):
                     object.__setattr__(m, "_fmi_no_w3", b16 or infer16)
             object.__setattr__(self, "_fmi_body_b16", b16 or infer16)
+        if neck16:  # the stem in one launch; the tails of blocks 6, 20 and 23 write no fp32 copy: their bf16 y is the tap
+            taps = {}
+            stem = self.input_layer
+            x, z = FF.irse_stem_fused_bf16(x, packed(stem[0]), *helpers.fold_bn_eval(stem[1]), stem[2].weight.detach(),
+                                           *helpers.fold_bn_eval(self.body[0].res_layer[0]))
+            for i, l in enumerate(self.body):
+                nxt = self.body[i + 1].res_layer[0] if i + 1 < len(self.body) else None
+                x, z, _ = l.infer_bf16(x, z, nxt, tap=False)
+                if i in (6, 20, 23):
+                    taps[i] = x
+            return taps[6], taps[20], taps[23]
         if infer16:
             taps = {}
             x, z = FF.irse_stem_bf16(x, *helpers.fold_bn_eval(self.body[0].res_layer[0]))
@@ -175,6 +225,38 @@ class GradualStyleEncoder(Module):
 
     def _heads_bf16(self):
         return self.eval_heads_dtype == torch.bfloat16 and not self.training
+
+    def _neck_bf16(self):
+        return self.eval_neck_dtype == torch.bfloat16 and not self.training
+
+    def _latents_from_maps(self, maps):
+        """the heads on the three bf16 level maps of neck_bf16 (coarse, middle, fine): log2(spatial) + 1 launches per level"""
+        latents = torch.empty((maps[0].shape[0], self.style_count, maps[0].shape[3]), device=maps[0].device, dtype=torch.float32)
+        bounds = [0, min(self.coarse_ind, self.style_count), min(self.middle_ind, self.style_count), self.style_count]
+        for lvl, p16 in enumerate(maps):
+            lo, hi = bounds[lvl], bounds[lvl + 1]
+            if hi > lo:
+                style_level_bf16([self.styles[j] for j in range(lo, hi)], p16, latents, lo, holder=self)
+        return latents
+
+    def _neck_check(self, x, ref):
+        """the refusals of the bf16 stem and neck, before any device call; there is no fp32 detour"""
+        if torch.is_grad_enabled():
+            raise FF.FmiError("GradualStyleEncoder with encoder_neck_eval_dtype='bf16' is inference only (no backward): call it under "
+                              "torch.no_grad() or detach the input")
+        if any(w % 64 for w in self._widths):
+            raise FF.FmiError(f"the bf16 stem and neck need every width to be a multiple of 64, got {self._widths}")
+        if ref is not None and self.use_attention:
+            h, w = x.shape[2], x.shape[3]
+            for lvl in range(4):  # the body's four stride-2 stages; the attentions sit behind the third (32^2) and the fourth (16^2)
+                h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+                if lvl >= 2 and (h * w) % 128:
+                    raise FF.FmiError(f"the bf16 guided attention needs a token count that is a multiple of 128, got {h} x {w} = {h * w} "
+                                      f"tokens at attention{4 - lvl} for a {x.shape[2]} x {x.shape[3]} image")
+            for att in (self.attention1, self.attention2):
+                unfit = att.bf16_unfit()
+                if unfit:
+                    raise FF.FmiError(f"the bf16 neck needs {unfit}")
 
     def _latents_bf16(self, c1, c2, c3):
         """FPN + heads of the bf16 inference form: three map hand-overs and log2(spatial) + 1 launches per level, written straight into
@@ -217,6 +299,16 @@ class GradualStyleEncoder(Module):
                     if isinstance(m, nn.Conv2d):
                         object.__setattr__(m, "_fmi_no_w3", heads16)
             object.__setattr__(self, "_fmi_heads_b16", heads16)
+        neck16 = self._neck_bf16()
+        if neck16:
+            self._neck_check(x, ref)
+        if getattr(self, "_fmi_neck_b16", None) != neck16:  # the stem's, the attentions' and the lateral convolutions need no fp32 piece images either
+            convs = [self.input_layer[0], self.latlayer1, self.latlayer2]
+            if self.use_attention:
+                convs += [self.attention1.conv, self.attention1.out_conv, self.attention2.conv, self.attention2.out_conv]
+            for m in convs:
+                object.__setattr__(m, "_fmi_no_w3", neck16)
+            object.__setattr__(self, "_fmi_neck_b16", neck16)
         if self._infer_bf16():  # refused before any device call; there is no fp32 detour
             if torch.is_grad_enabled():
                 raise FF.FmiError("GradualStyleEncoder with encoder_eval_dtype='bf16' is inference only (no backward): call it under "
@@ -236,6 +328,10 @@ class GradualStyleEncoder(Module):
                     t1, t2, t3 = self._pyramid(torch.cat([FF.to_nhwc(x), FF.to_nhwc(ref)], dim=0))
                 finally:
                     helpers.BN_GROUPS[0] = 1
+                if neck16:
+                    (c1, r1), (c2, r2), (c3, r3) = ((t[:nb], t[nb:]) for t in (t1, t2, t3))
+                    att1, att2 = (self.attention1, self.attention2) if self.use_attention else (None, None)
+                    return self._latents_from_maps(neck_bf16(att1, att2, self.latlayer1, self.latlayer2, c1, c2, c3, r1, r2, r3, mask))
                 (c1, r1), (c2, r2), (c3, r3) = FF.split_batch(t1, nb), FF.split_batch(t2, nb), FF.split_batch(t3, nb)
                 m = mask.contiguous().unsqueeze(-1)  # [N,H,W,1]
                 n = m.shape[0]
@@ -251,4 +347,6 @@ class GradualStyleEncoder(Module):
                 c1 = self._blend(mask_1, r1, c1)
             else:
                 c1, c2, c3 = self._pyramid(FF.to_nhwc(x))
+                if neck16:
+                    return self._latents_from_maps(neck_bf16(None, None, self.latlayer1, self.latlayer2, c1, c2, c3))
             return self._latents(c1, c2, c3)

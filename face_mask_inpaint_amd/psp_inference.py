@@ -59,6 +59,9 @@ def get_args(argv=None):
                    help="activation type of the encoder's IR-SE body (bf16: the fused inference form of its 24 blocks)")
     p.add_argument("--style_heads_dtype", type=str, default="fp32", choices=("fp32", "bf16"),
                    help="activation type of the encoder's map2style heads (bf16: the heads of a pyramid level run together, one launch per layer)")
+    p.add_argument("--neck_dtype", type=str, default="fp32", choices=("fp32", "bf16"),
+                   help="activation type of the encoder's stem and neck (bf16: fused stem, guided attention, blends, laterals and merges on bf16 maps; "
+                        "needs --encoder_dtype bf16 and --style_heads_dtype bf16)")
     p.add_argument("--out_dir", type=str, default=None, help="where gen_<id>.jpg / metrics.csv go (default: test_results/<run name>)")
     p.add_argument("--num_batches", type=int, default=2, help="synthetic mode: batches to run")
     return p.parse_args(argv)
@@ -136,8 +139,9 @@ def build(args, device):
     opts.encoder_eval_dtype = getattr(args, "encoder_dtype", "fp32")
     opts.encoder_dtype = "fp32"
     opts.style_heads_eval_dtype = getattr(args, "style_heads_dtype", "fp32")  # likewise: the heads of an EVAL-mode forward
+    opts.encoder_neck_eval_dtype = getattr(args, "neck_dtype", "fp32")  # likewise: the stem and the neck of an EVAL-mode forward
     generator = pSp(opts).to(device).eval()
-    if "bf16" in (opts.encoder_eval_dtype, opts.style_heads_eval_dtype):  # a frozen encoder keeps its folded BatchNorm constants and bf16 weight packs between calls
+    if "bf16" in (opts.encoder_eval_dtype, opts.style_heads_eval_dtype, opts.encoder_neck_eval_dtype):  # a frozen encoder keeps its folded BatchNorm constants and bf16 weight packs between calls
         base_function._freeze(generator.encoder)
     if generator.latent_avg is None:
         with torch.no_grad():

@@ -877,6 +877,14 @@ int fmi_irse_stem_bf16(const float* x, const float* scale, const float* shift, u
  * model[1] lives here because conv2 is the only consumer.  y 16-byte aligned. */
 int fmi_conv2d_thin_in_fwd_bf16(const fmi_conv_desc* d, const float* x, const float* wf, const float* bias, float slope, uint16_t* y,
                                 void* stream);
+/* the pSp encoder's stem (psp_encoders.py:59-61: Conv2d(3, 64, 3x3, pad 1, no bias), BatchNorm2d, PReLU) and block 0's first BatchNorm
+ * (helpers.py:86 / :108) in one launch, eval mode:  v = conv3x3(x) in fp32 FMAs,  a = prelu(v * scale[k] + shift[k], slope[k]),
+ * y = bf16(a),  z = bf16(a * scale0[k] + shift0[k]) -- both rounded once from the fp32 a, the rounding points of the fp32 convolution
+ * followed by fmi_irse_stem_bf16.  x fp32 [N,H,W,C <= 4], wf fp32 [9][C][K] (the fp32 forward pack), the five vectors fp32 [K],
+ * y / z bf16 [N,H,W,K]; a32 (debug, may be NULL) receives the fp32 a.  K % 8 == 0 and K <= 256, 3x3 pad 1 stride 1, x below 4 GiB,
+ * y / z / a32 16-byte aligned, else FMI_ERR_UNSUPPORTED; a NULL operand or an inconsistent descriptor: FMI_ERR_BAD_ARG. */
+int fmi_irse_stem_fwd_bf16(const fmi_conv_desc* d, const float* x, const float* wf, const float* scale, const float* shift, const float* slope,
+                           const float* scale0, const float* shift0, uint16_t* y, uint16_t* z, float* a32, void* stream);
 /* the 32-channel layers (base_function.py:254-256 at ngf 32, :279): y = lrelu(conv(x) + bias, slope); slope = 1 is the plain convolution.
  * x bf16 [N,H,W,32], wnk bf16 [K][kh*kw][32] (fmi_pack_weight_bf16), bias fp32 [K] or NULL, y bf16 [N,H,W,K].  C == 32, K in {32, 64},
  * 3x3 pad 1 or 1x1 pad 0, stride 1, dense pixel pitches; 16-byte aligned pointers.  bf16 MFMA, fp32 accumulation; the whole weight set
@@ -902,6 +910,13 @@ int fmi_picnet_stem_tail_bf16(const uint16_t* h, const float* img, const float* 
 int fmi_guided_attention_fwd_bf16_waves(int N, int T);
 int fmi_guided_attention_fwd_bf16(const uint16_t* q, const uint16_t* src, const uint16_t* ref, const float* mask, uint16_t* out, int N, int T,
                                   int D, int C, int waves, void* stream);
+/* the same at the pSp encoder's shapes (example_guided_att.py:21-41 as psp_encoders.py:128-132 builds it): (D, C) in {(64, 256),
+ * (128, 512)} = attention2 / attention1.  The kernel is the one above with grid index z a slice of 128 channels: its V tile is
+ * [ref slice | src slice] read at row pitch C, it writes out[..., 128 z : +128] and out[..., C + 128 z : +128], and every slice recomputes
+ * the scores from the shared q, so the accumulators of a wave do not grow with C.  Same arguments, checks, blend (m == 1 returns ref
+ * bit for bit), lazy reference maximum and wave dispatch; any other (D, C), (32, 128) included: FMI_ERR_UNSUPPORTED. */
+int fmi_guided_attention_sliced_fwd_bf16(const uint16_t* q, const uint16_t* src, const uint16_t* ref, const float* mask, uint16_t* out, int N,
+                                         int T, int D, int C, int waves, void* stream);
 
 /* ------------------------------------------------------------------------
  * Inference form of the map2style heads of the pSp encoder on bf16 NHWC activations: the G heads of one pyramid level run together, one
@@ -933,6 +948,15 @@ int fmi_conv2d_grouped_fwd_bf16(const fmi_conv_desc* d, int G, int64_t x_group_o
  * or a non-positive extent: FMI_ERR_BAD_ARG. */
 int fmi_fpn_merge_bf16(const float* lateral, const float* coarse, float* p32, uint16_t* p16, int N, int H, int W, int CH, int CW, int C,
                        void* stream);
+/* _upsample_add (psp_encoders.py:97-98) from bf16 maps: p16 = bf16(bilinear(coarse, align_corners=True, to H x W) + lateral) with the same
+ * integer bilinear weights and fp32 arithmetic as fmi_fpn_merge_bf16, one rounding.  lateral, p16 bf16 [N,H,W,C], coarse bf16
+ * [N,CH,CW,C]; C % 8 == 0, 16-byte aligned pointers (else FMI_ERR_UNSUPPORTED).  A NULL pointer or a non-positive extent: FMI_ERR_BAD_ARG. */
+int fmi_fpn_merge_in_bf16(const uint16_t* lateral, const uint16_t* coarse, uint16_t* p16, int N, int H, int W, int CH, int CW, int C,
+                          void* stream);
+/* the mask blend of the pyramid levels (psp_encoders.py:135-138) in one launch: y = bf16(m r + (1 - m) c), evaluated in fp32, from bf16
+ * r, c [rows][C] and fp32 m [rows].  m == 1 returns r and m == 0 returns c bit for bit.  C % 8 == 0, r / c / y 16-byte aligned (else
+ * FMI_ERR_UNSUPPORTED); a NULL pointer or a non-positive extent: FMI_ERR_BAD_ARG. */
+int fmi_mask_blend_bf16(const uint16_t* r, const uint16_t* c, const float* m, uint16_t* y, int64_t rows, int C, void* stream);
 
 #ifdef __cplusplus
 }
