@@ -106,6 +106,8 @@ SIGNATURES = {
     "fmi_attention_fwd_f32": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "fmi_attention_fwd_bf16": [vp] * 6 + [i32] * 5 + [vp],
     "fmi_attention_bwd_f32": [vp] * 12 + [i32] * 5 + [vp],
+    "fmi_attention_bwd_prep_bf16": [vp] * 4 + [i32] * 4 + [vp],
+    "fmi_attention_bwd_bf16": [vp] * 7 + [i32] * 4 + [vp],
     "fmi_attention_fwd_image_bytes": [i32, i32, i32, i32, i32, C.POINTER(i64)],
     "fmi_attention_fwd_pieces_f32": [vp] * 4 + [i64] + [vp] * 3 + [i32] * 5 + [vp],
     "fmi_attention_bwd_image_bytes": [i32, i32, i32, i32, i32, C.POINTER(i64)],

@@ -2115,6 +2115,64 @@ def self_attention(q: torch.Tensor, values: Sequence[torch.Tensor]) -> Tuple[tor
     return _SelfAttention.apply(q, *values)
 
 
+ATTN_BF16_SHAPES = ((64, 256), (32, 128))  # (d_qk, C) of fmi_attention_fwd_bf16 and its backward
+
+
+def attention_bf16_unfit(t, d, c):
+    """why the bf16 attention (forward and backward) does not take T tokens at widths (d_qk, C); None: it does"""
+    if t % 128 or (d, c) not in ATTN_BF16_SHAPES:
+        return (f"a token count that is a multiple of 128 and (d_qk, C) in {{(64, 256), (32, 128)}}, got T = {t}, "
+                f"(d_qk, C) = ({d}, {c})")
+    return None
+
+
+class _SelfAttentionBf16Train(torch.autograd.Function):
+    """softmax(q q^T) v on the bf16 kernels with a backward: fmi_attention_fwd_bf16 (lse kept, no epilogue), then
+    fmi_attention_bwd_prep_bf16 + fmi_attention_bwd_bf16.  Saved for the backward: q16, v16, o16 (bf16) and lse -- not the fp32 operands.
+    No host synchronisation anywhere: the whole node can be captured into a graph."""
+
+    @staticmethod
+    def forward(ctx, q, v):
+        n, t, d = q.shape
+        c = v.shape[2]
+        q16, v16 = q.to(BF16), v.to(BF16)  # the one rounding of each operand
+        o16 = torch.empty_like(v16)
+        lse = torch.empty((n, t), device=q.device, dtype=torch.float32)
+        with _prof(f"attn_fused_fwd_bf16|T{t} d{d} C{c} b{n}", 2.0 * n * t * t * (d + c)):
+            _L().attention_fwd_bf16(_p(q16), _p(v16), _p(o16), _p(lse), None, None, n, t, d, c, 0, _st())
+        ctx.save_for_backward(q16, v16, o16, lse)
+        return o16.float()
+
+    @staticmethod
+    def backward(ctx, go):
+        q16, v16, o16, lse = ctx.saved_tensors
+        n, t, d = q16.shape
+        c = v16.shape[2]
+        go = go.contiguous()
+        _chk(go)
+        go16 = torch.empty_like(o16)
+        delta = torch.empty_like(lse)
+        gq = torch.empty((n, t, d), device=go.device, dtype=torch.float32)  # the key launch writes every element
+        gv = torch.empty((n, t, c), device=go.device, dtype=torch.float32)
+        with _prof(f"attn_bwd_prep_bf16|T{t} C{c} b{n}", 2.0 * n * t * c):
+            _L().attention_bwd_prep_bf16(_p(go), _p(o16), _p(go16), _p(delta), n, t, d, c, _st())
+        with _prof(f"attn_fused_bwd_bf16|T{t} d{d} C{c} b{n}", 2.0 * n * t * t * (4 * d + 3 * c)):
+            _L().attention_bwd_bf16(_p(q16), _p(v16), _p(go16), _p(lse), _p(delta), _p(gq), _p(gv), n, t, d, c, _st())
+        return gq, gv
+
+
+def self_attention_bf16_train(q: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """q [N,T,d], v [N,T,C] fp32 -> softmax(q q^T) v in fp32, computed by the bf16 attention kernels, with gradients for both.  q and v
+    are rounded to bf16 once; scores, softmax and accumulators are fp32 (include/fmi_hip.h: fmi_attention_bwd_bf16)."""
+    if q.dim() != 3 or v.dim() != 3 or q.shape[:2] != v.shape[:2]:
+        raise FmiError(f"self_attention_bf16_train takes q [N,T,d] and v [N,T,C], got {tuple(q.shape)} and {tuple(v.shape)}")
+    why = attention_bf16_unfit(q.shape[1], q.shape[2], v.shape[2])
+    if why or q.shape[0] > 65535:
+        raise FmiError(f"the bf16 attention needs {why or f'at most 65535 samples, got {q.shape[0]}'}")
+    _chk(q, v)
+    return _SelfAttentionBf16Train.apply(q, v)
+
+
 # ---------------------------------------------------------------------------------------------------
 # losses
 # ---------------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 """Host-side mirror of modules/model.py: ReferenceFill (model.py:15-112) and scale_img (model.py:10-12)."""
 from __future__ import annotations
 
+import os
+
 import torch
 from torch import nn
 
@@ -15,14 +17,33 @@ def scale_img(img, size):
     return FF.to_nchw(FF.resize_bilinear(FF.to_nhwc(img), int(size[0]), int(size[1])))
 
 
+ATTENTION_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
+
+
+def attention_dtype_from_env():
+    """FMI_ATTENTION_DTYPE={fp32,bf16} (default fp32): the decoder attention's dtype where ReferenceFill is built without the argument --
+    how a trainer whose flags are the reference's, or a fixed benchmark, selects the bf16 attention"""
+    name = os.environ.get("FMI_ATTENTION_DTYPE", "fp32")
+    if name not in ATTENTION_DTYPES:
+        raise FF.FmiError(f"FMI_ATTENTION_DTYPE must be one of {sorted(ATTENTION_DTYPES)}, got {name!r}")
+    return ATTENTION_DTYPES[name]
+
+
 class ReferenceFill(nn.Module):
     def __init__(self, mask_detector, encoder_params, decoder_params, use_att=True, out_size=(256, 256), decoder_dtype=torch.float32,
-                 feature_dtype=torch.float32):
+                 feature_dtype=torch.float32, attention_dtype=None):
         """decoder_dtype=torch.bfloat16 (this build's extra, inference only): ResGenerator's decoder blocks, attention and Output block
         on the bf16 kernels.  feature_dtype=torch.bfloat16 (likewise, independent of decoder_dtype): both ResEncoders and the guided
         attention on the bf16 kernels -- the image enters in fp32, the distribution heads leave in fp32, the attention's output is cast to
-        fp32 once for ``encoded + f``.  The latent path and all parameters stay fp32 either way."""
+        fp32 once for ``encoded + f``.  The latent path and all parameters stay fp32 either way.
+        attention_dtype=torch.bfloat16 (an extra too, and TRAINABLE): the fp32 decoder with attn1's softmax(q q^T) x on the bf16 attention
+        kernels, forward and backward (ResGenerator(attn_dtype=)); None (the default) reads FMI_ATTENTION_DTYPE, which defaults to fp32."""
         super().__init__()
+        if attention_dtype is None:
+            attention_dtype = attention_dtype_from_env()
+        if attention_dtype not in (torch.float32, torch.bfloat16):
+            raise FF.FmiError(f"attention_dtype must be torch.float32 or torch.bfloat16, got {attention_dtype}")
+        self.attention_dtype = attention_dtype
         if feature_dtype not in (torch.float32, torch.bfloat16):
             raise FF.FmiError(f"feature_dtype must be torch.float32 or torch.bfloat16, got {feature_dtype}")
         self.feature_dtype = feature_dtype
@@ -50,7 +71,7 @@ class ReferenceFill(nn.Module):
             self.ref_encoder = network.define_e(**encoder_params, encoder_type="ref", **enc_kw)
         else:
             raise NotImplementedError
-        self.decoder = network.define_g(**decoder_params, compute_dtype=decoder_dtype)
+        self.decoder = network.define_g(**decoder_params, compute_dtype=decoder_dtype, attn_dtype=attention_dtype)
         self.use_att = use_att
         if use_att:
             self.attention = ExampleGuidedAttention(encoder_params["img_f"])

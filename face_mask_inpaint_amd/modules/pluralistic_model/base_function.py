@@ -310,10 +310,17 @@ class Output(_NhwcBlock):
 class Auto_Attn(nn.Module):
     """Short+Long attention (base_function.py:401-448).  Only the ``pre is None`` form is on the hot path; the
     attention map itself is never materialised, so the second return value is None (every caller discards it:
-    network.py:265-268, 364-366)."""
+    network.py:265-268, 364-366).
 
-    def __init__(self, input_nc, norm_layer=nn.BatchNorm2d):
+    ``attn_dtype=torch.bfloat16`` (this build's extra, an opt-in for training an otherwise fp32 model): on an fp32 input the query
+    convolution and ``gamma * out + x`` stay fp32, and softmax(q q^T) x runs on the bf16 attention kernels, forward and backward
+    (FF.self_attention_bf16_train).  Parameters and state_dict keys are those of the default."""
+
+    def __init__(self, input_nc, norm_layer=nn.BatchNorm2d, attn_dtype=torch.float32):
         super().__init__()
+        if attn_dtype not in (torch.float32, torch.bfloat16):
+            raise FF.FmiError(f"attn_dtype must be torch.float32 or torch.bfloat16, got {attn_dtype}")
+        self.attn_dtype = attn_dtype
         self.input_nc = input_nc
         self.query_conv = nn.Conv2d(input_nc, input_nc // 4, kernel_size=1)
         self.gamma = nn.Parameter(torch.zeros(1))
@@ -322,6 +329,13 @@ class Auto_Attn(nn.Module):
         self.model = ResBlock(int(input_nc * 2), input_nc, input_nc, norm_layer=norm_layer, use_spect=True)
         self.model._fmi_never_runs = True  # the reference never executes it when pre is None; its u/v must not advance
 
+    def check_bf16(self, h, w, c):
+        """attn_dtype=torch.bfloat16 on an h x w map of c channels: refused before any device work where the bf16 attention does not
+        take the shape -- there is no fp32 detour"""
+        why = FF.attention_bf16_unfit(h * w, self.query_conv.out_channels, c) if self.attn_dtype == torch.bfloat16 else None
+        if why:
+            raise FF.FmiError(f"Auto_Attn(attn_dtype=torch.bfloat16) needs {why} from a {h} x {w} map; these run in fp32 only")
+
     def nhwc(self, x):
         with weight_scope(self):
             n, h, w, c = x.shape
@@ -329,11 +343,17 @@ class Auto_Attn(nn.Module):
                 q = FF.conv2d_bias_bf16(x, packed(self.query_conv), self.query_conv.bias, 0)
                 xv = x.view(n, h * w, c)
                 return FF.self_attention_bf16(q.view(n, h * w, -1), xv, self.gamma, xv).view(n, h, w, c)
+            self.check_bf16(h, w, c)
             q = run_conv(self.query_conv, x)
-            (o,) = FF.self_attention(q.view(n, h * w, -1), [x.view(n, h * w, c)])
+            if self.attn_dtype == torch.bfloat16:
+                o = FF.self_attention_bf16_train(q.view(n, h * w, -1), x.view(n, h * w, c))
+            else:
+                (o,) = FF.self_attention(q.view(n, h * w, -1), [x.view(n, h * w, c)])
             return FF.scale_add_param(o.view(n, h, w, c), self.gamma, x)
 
     def forward(self, x, pre=None, mask=None):
         if pre is not None:
             raise NotImplementedError("the long-term (pre/mask) branch of Auto_Attn is never taken by the reference's callers")
+        if x.dtype != torch.bfloat16:
+            self.check_bf16(x.shape[2], x.shape[3], x.shape[1])
         return FF.to_nchw(self.nhwc(FF.to_nhwc(x))), None

@@ -23,8 +23,9 @@ def define_e(encoder_type="src", input_nc=3, ngf=64, z_nc=512, img_f=512, L=6, l
 
 
 def define_g(output_nc=3, ngf=64, z_nc=512, img_f=512, L=1, layers=5, norm="instance", activation="ReLU", use_spect=True,
-             use_coord=False, use_attn=True, init_type="orthogonal", gpu_ids=[], compute_dtype=torch.float32):
-    net = ResGenerator(output_nc, ngf, z_nc, img_f, L, layers, norm, activation, use_spect, use_coord, use_attn, compute_dtype=compute_dtype)
+             use_coord=False, use_attn=True, init_type="orthogonal", gpu_ids=[], compute_dtype=torch.float32, attn_dtype=torch.float32):
+    net = ResGenerator(output_nc, ngf, z_nc, img_f, L, layers, norm, activation, use_spect, use_coord, use_attn, compute_dtype=compute_dtype,
+                       attn_dtype=attn_dtype)
     return init_net(net, init_type, activation, gpu_ids)
 
 
@@ -156,14 +157,19 @@ class ResEncoder(nn.Module):
 class ResGenerator(nn.Module):
     """network.py:181-307.  ``compute_dtype=torch.bfloat16`` (this build's extra, inference only): the latent ResBlocks stay fp32,
     ``encoded + f`` is cast to bf16 once, and decoder0.., attn1 and the Output block run on the bf16 kernels; the image leaves the
-    Output block in fp32.  Parameters, state_dict keys and SpectralNorm state are those of the fp32 build."""
+    Output block in fp32.  Parameters, state_dict keys and SpectralNorm state are those of the fp32 build.
+    ``attn_dtype=torch.bfloat16`` (likewise an extra, and trainable): the fp32 generator with attn1's softmax(q q^T) x alone on the bf16
+    attention kernels, forward and backward (Auto_Attn); everything else, and every default, is the fp32 build's."""
 
     def __init__(self, output_nc=3, ngf=64, z_nc=128, img_f=1024, L=1, layers=6, norm="batch", activation="ReLU",
-                 use_spect=True, use_coord=False, use_attn=False, compute_dtype=torch.float32):
+                 use_spect=True, use_coord=False, use_attn=False, compute_dtype=torch.float32, attn_dtype=torch.float32):
         super().__init__()
         if compute_dtype not in (torch.float32, torch.bfloat16):
             raise FF.FmiError(f"compute_dtype must be torch.float32 or torch.bfloat16, got {compute_dtype}")
+        if attn_dtype not in (torch.float32, torch.bfloat16):
+            raise FF.FmiError(f"attn_dtype must be torch.float32 or torch.bfloat16, got {attn_dtype}")
         self.compute_dtype = compute_dtype
+        self.attn_dtype = attn_dtype
         self.layers, self.L, self.use_attn = layers, L, use_attn
         norm_layer = get_norm_layer(norm_type=norm)
         nonlinearity = get_nonlinearity_layer(activation_type=activation)
@@ -180,7 +186,10 @@ class ResGenerator(nn.Module):
             if i > layers - 2:
                 setattr(self, "out" + str(i), Output(ch, output_nc, 3, None, nonlinearity, use_spect, use_coord))
             if i == 1 and use_attn:
-                setattr(self, "attn" + str(i), Auto_Attn(ch, None))
+                setattr(self, "attn" + str(i), Auto_Attn(ch, None, attn_dtype=attn_dtype))
+                if attn_dtype == torch.bfloat16 and (ch // 4, ch) not in FF.ATTN_BF16_SHAPES:
+                    raise FF.FmiError(f"ResGenerator(attn_dtype=torch.bfloat16) needs (d_qk, C) in {{(64, 256), (32, 128)}} at attn{i} "
+                                      f"(got ({ch // 4}, {ch})); these channel counts run in fp32 only")
             if compute_dtype == torch.bfloat16:
                 self._check_bf16_block(i, prev_ch, ch, norm, use_attn)
         if compute_dtype == torch.bfloat16:
@@ -221,6 +230,11 @@ class ResGenerator(nn.Module):
         if bf16 and self.use_attn and self.layers > 1 and (16 * encoded.shape[1] * encoded.shape[2]) % 128:
             raise FF.FmiError(f"the bf16 attention at attn1 needs a token count that is a multiple of 128: a {encoded.shape[1]} x "
                               f"{encoded.shape[2]} feature map gives {16 * encoded.shape[1] * encoded.shape[2]} tokens")
+        if not bf16 and self.attn_dtype == torch.bfloat16 and self.use_attn and self.layers > 1 and (
+                16 * encoded.shape[1] * encoded.shape[2]) % 128:
+            raise FF.FmiError(f"ResGenerator(attn_dtype=torch.bfloat16): the bf16 attention at attn1 needs a token count that is a multiple "
+                              f"of 128: a {encoded.shape[1]} x {encoded.shape[2]} feature map gives "
+                              f"{16 * encoded.shape[1] * encoded.shape[2]} tokens; these run in fp32 only")
         with weight_scope(self):
             if z is not None:
                 f = self.generator.nhwc(z)

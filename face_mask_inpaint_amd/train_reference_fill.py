@@ -12,7 +12,10 @@ literal choice, kept) and ``G_checkpoint_epoch{n}.pth`` / ``D_checkpoint_epoch{n
   * Adam is optim.FusedAdam; batches arrive as device tensors from dataloader.get_reference_dataloader / to_device_batch, whose
     ``true_masks`` is the reference's ``(mask > 0).float()``;
   * logging goes through ``logging`` and an optional ``callback(event: dict)``: no wandb, no tqdm, no histograms or images;
-  * loss values and validation metrics stay device scalars until the end of an evaluation round or of the epoch.
+  * loss values and validation metrics stay device scalars until the end of an evaluation round or of the epoch;
+  * the environment variable ``FMI_ATTENTION_DTYPE=bf16`` (``fp32`` is the default; ``get_args`` keeps exactly the reference's flags)
+    runs the generator's ``attn1`` on the bf16 attention kernels, forward and backward, in the otherwise fp32 model -- read by
+    ``ReferenceFill`` where it is built, same parameters and checkpoints.
 
 ``load_networks`` reproduces the reference literally -- including that for G and E it collects the MODEL'S OWN tensors for
 every key whose shape matches the checkpoint (``matches[k] = v`` at :123-126 takes ``v`` from ``generator.decoder.state_dict()``,

@@ -379,7 +379,7 @@ int fmi_attention_fwd_f32(const float* q, const float* v1, const float* v2, floa
 int fmi_attention_fwd_waves(int N, int T);
 int fmi_attention_bwd_structure(int N, int T);
 
-/* The same forward on bf16 operands (inference; no backward): q [N,T,D], v [N,T,C] and o [N,T,C] bf16, scores / running maximum / row
+/* The same forward on bf16 operands (inference, and training with the backward below): q [N,T,D], v [N,T,C] and o [N,T,C] bf16, scores / running maximum / row
  * sum / output accumulators fp32, P rounded to bf16 only as the matrix operand of P V (the row sum adds the fp32 values).
  * Optional epilogue o = gamma[0] * O + residual, computed in fp32 before the one rounding of o: gamma a 1-element fp32 DEVICE tensor,
  * residual bf16 in o's layout (Auto_Attn's gamma * out + x, base_function.py:439); both NULL or both given.  lse [N,T] fp32 as above
@@ -390,6 +390,22 @@ int fmi_attention_bwd_structure(int N, int T);
 int fmi_attention_fwd_bf16_waves(int N, int T);
 int fmi_attention_fwd_bf16(const uint16_t* q, const uint16_t* v, uint16_t* o, float* lse, const float* gamma, const uint16_t* residual,
                            int N, int T, int D, int C, int waves, void* stream);
+
+/* Backward of fmi_attention_fwd_bf16 without its epilogue (csrc/attention_bwd_bf16.hip), K = Q and no scaling as there:
+ *     P = exp(S - lse),  dP = go V^T,  dS = P o (dP - delta),  gv = P^T go,  gq = dS Q + dS^T Q.
+ *   fmi_attention_bwd_prep_bf16  one pass over go (fp32 [N,T,C], the gradient of O) and o (bf16, as the forward stored it): writes
+ *                                go16 = bf16(go) (round to nearest even) and delta[n,t] = sum_c go o (fp32 products and sum, from the
+ *                                unrounded go).  No atomics: one thread group owns a row.
+ *   fmi_attention_bwd_bf16       q16 [N,T,D], v16 / go16 [N,T,C] bf16, lse / delta [N,T] fp32 -> gq [N,T,D], gv [N,T,C] fp32.  Two launches:
+ *                                key-stationary (gv and the key-side half dS^T Q of gq, plain stores), then query-stationary (the
+ *                                query-side half dS Q, added by the row's one owner).  No float atomics, no hand-off between
+ *                                workgroups: two runs give the same bits whatever fmi_set_deterministic says.  gq and gv need no zeroing.
+ * Rounding: q16, v16, go16, and P and dS as matrix operands, are rounded to bf16 once each; scores, exp, dP - delta and all accumulators
+ * are fp32.  Supported: T % 128 == 0, (D, C) in {(64, 256), (32, 128)}, N <= 65535; else FMI_ERR_UNSUPPORTED before any launch.  A NULL
+ * pointer or one off 16-byte alignment: FMI_ERR_BAD_ARG. */
+int fmi_attention_bwd_prep_bf16(const float* go, const uint16_t* o, uint16_t* go16, float* delta, int N, int T, int D, int C, void* stream);
+int fmi_attention_bwd_bf16(const uint16_t* q, const uint16_t* v, const uint16_t* go16, const float* lse, const float* delta, float* gq,
+                           float* gv, int N, int T, int D, int C, void* stream);
 
 /* The same forward with the bf16 pieces of K (= q) and V cut ONCE per pass into a key-tile image (layout: csrc/attention.hip, AttKImg)
  * that every workgroup streams into LDS by LDS-DMA; bit-identical results (the same pieces in the same MFMA order).
