@@ -38,13 +38,15 @@ static ConvGeom f32_geom(ConvGeom g, const fmi_conv_desc* d, const float* img) {
 }
 
 #ifndef FMI_HOST_EMU
-// y[pixel][k] = bias[k] + residual[pixel][k] (either may be null): first pass of a split-reduction convolution
-__global__ void __launch_bounds__(256) conv_split_init_kernel(float* __restrict__ y, const float* __restrict__ bias,
+// y[pixel][k] = bias[k] + bias2[k] + residual[pixel][k] (each may be null): first pass of a split-reduction convolution; bias2 = the second
+// convolution's bias of a pair (conv_pair.h)
+__global__ void __launch_bounds__(256) conv_split_init_kernel(float* __restrict__ y, const float* __restrict__ bias, const float* __restrict__ bias2,
                                                              const float* __restrict__ res, int K, int cstride, int64_t total) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int k = (int)(i % K);
     const int64_t o = (i / K) * cstride + k;
     float v = bias ? bias[k] : 0.f;
+    if (bias2) v += bias2[k];
     if (res) v += res[o];
     y[o] = v;
   }
@@ -94,7 +96,7 @@ static int conv_phase(const fmi_conv_desc* d, const ConvGeom& g, const float* x,
   if (shared_init || ks > 1) {
     if (!shared_init) {
       const int64_t total = (int64_t)g.N * ep.OHt * ep.OWt * Nout;
-      hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, st, ep.y, ep.bias, ep.res, Nout, ep.cstride,
+      hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, st, ep.y, ep.bias, (const float*)nullptr, ep.res, Nout, ep.cstride,
                          total);
     }
     ep.bias = nullptr;
@@ -213,7 +215,7 @@ static int dgrad_impl(const fmi_conv_desc* d, const float* dy, const float* wt, 
       }
     if (strided_split) {
       const int64_t total = (int64_t)d->N * d->H * d->W * d->C;
-      hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, dx, bias, residual, d->C,
+      hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, dx, bias, (const float*)nullptr, residual, d->C,
                          d->x_cstride, total);
     }
   }
@@ -321,6 +323,131 @@ extern "C" int fmi_conv2d_wgrad_f32(const fmi_conv_desc* d, const float* x, cons
   if (fmi_det()) ksplit = 1;  // reproducible mode: one workgroup per tile walks the whole pixel reduction
   if (ksplit * batch_w > 65535) ksplit = 65535 / batch_w;
   return launch_gemm(la, lb, ep, Mg, Ng, Kg, batch_w, (int)ksplit, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The stride-1 ResBlock pair (conv_pair.h): y = act(conv3x3(x1, W1) + conv1x1(x2, W2) + b1 + b2) as one reduction over 9 * C + C2 elements,
+// and dW1, dW2 and the gradient of both biases from one walk over dy.  d describes the 3x3 convolution (d->w3 = the piece image of its
+// forward pack or null); x2 is dense [N][H][W][C2].
+// ---------------------------------------------------------------------------------------------
+static int pair_check(const fmi_conv_desc* d, int C2) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  if (C2 <= 0) return FMI_ERR_BAD_ARG;
+  if (d->kh != 3 || d->kw != 3 || d->stride != 1 || d->pad != 1 || d->pad_mode != 0 || d->dil > 1) return FMI_ERR_UNSUPPORTED;
+  if ((d->C & 15) || (C2 & 15) || (d->K & 3) || d->x_cstride != d->C || d->y_cstride != d->K) return FMI_ERR_UNSUPPORTED;
+  if (9ll * d->C + C2 > 0x3fffffffLL || (int64_t)d->N * d->H * d->W >= (1ll << 30)) return FMI_ERR_UNSUPPORTED;
+  return FMI_OK;
+}
+// reduction splits of the pair's forward, as the launch takes them (1: unsplit)
+static int pair_ksplit(const fmi_conv_desc* d, int C2, int act, bool tap_reuse) {
+  const int M = d->N * d->H * d->W, Kd = 9 * d->C + C2;
+  int ks = act == 0 ? conv_ksplit(M, d->K, Kd) : 1;
+  if (tap_reuse) {  // launch_conv3x3: whole (ky, 16 channels) steps per split
+    const int nit = 3 * (d->C >> 4) + (C2 >> 4);
+    if (ks > nit) ks = nit;
+    const int it_chunk = (nit + ks - 1) / ks;
+    return (nit + it_chunk - 1) / it_chunk;
+  }
+  const int kchunk = (int)ceil_div64(ceil_div64(Kd, ks), 16) * 16;  // launch_gemm: 16-deep tiles per split
+  return (int)ceil_div64(Kd, kchunk);
+}
+static bool pair_tap_reuse(const fmi_conv_desc* d) {
+#ifndef FMI_HOST_EMU
+  return (d->C >= 64 || d->K <= 32);  // conv3x3_eligible's channel rule; alignment is checked at the call
+#else
+  return false;
+#endif
+}
+extern "C" int fmi_conv2d_pair_supported(const fmi_conv_desc* d, int C2) { return d && pair_check(d, C2) == FMI_OK; }
+extern "C" int fmi_conv2d_pair_ksplit(const fmi_conv_desc* d, int C2, int act) {
+  if (!d || pair_check(d, C2) != FMI_OK) return 0;
+  return pair_ksplit(d, C2, act, pair_tap_reuse(d));
+}
+// Which passes of a supported shape the ResBlock routes here: bit 0 the forward, bit 1 the weight gradient.  A pass is routed only where the
+// fused launch was faster than conv2 + bypass in EVERY alternated round of tools/bench_tools/resblock_pair_time.py
+// (profiles/resblock_pair.txt): the weight gradient at every measured shape (8 x 8^2 .. 8 x 128^2); the forward at all of them but
+// 8 x 32^2 128 -> 128, a tie (39.6 against 39.5 us, lower in 2 rounds of 5).  Where conv2 runs from piece images of x1 today
+// (functional.p3_wanted: >= 16384 pixels, C >= 64, K >= 128) only the measured shape, 8 x 64^2 64 -> 128, is routed.  Below 32 channels
+// (nothing measured: the step has no such block) the two launches stay.
+extern "C" int fmi_conv2d_pair_routed(const fmi_conv_desc* d, int C2) {
+  if (!fmi_conv2d_pair_supported(d, C2) || d->C < 32) return 0;
+  const int64_t px = (int64_t)d->N * d->H * d->W;
+  if (px >= 16384 && d->C >= 64 && d->K >= 128) return (d->C == 64 && d->K == 128 && px <= 32768) ? 3 : 0;
+  const bool fwd_tie = d->C == 128 && d->K == 128 && px > 2048 && px < 16384;
+  return fwd_tie ? 2 : 3;
+}
+
+extern "C" int fmi_conv2d_pair_fwd_f32(const fmi_conv_desc* d, const float* x1, const float* x2, int C2, const float* wf1, const float* wf2,
+                                       const void* w3b, const float* b1, const float* b2, float* y, int act, void* stream) {
+  if (!d) return FMI_ERR_BAD_ARG;
+  int rc = pair_check(d, C2);
+  if (rc) return rc;
+  if (!x1 || !x2 || !wf1 || !wf2 || !y || act < 0 || act > 2) return FMI_ERR_BAD_ARG;
+  if (!aligned16(x1) || !aligned16(x2) || !aligned16(wf1) || !aligned16(wf2) || !aligned16(y) || !aligned16(b1) || !aligned16(b2)) return FMI_ERR_BAD_ARG;
+  if (!b1) { b1 = b2; b2 = nullptr; }
+  const ConvGeom g = f32_geom(fwd_geom(d, d->N), d, x1);
+  const int K1 = g.Kdim(), Kd = K1 + C2, M = g.Mdim();
+  ConvEp2 ep;
+  static_cast<ConvEp&>(ep) = ConvEp{y, b1, nullptr, d->OH, d->OW, 1, 0, 0, d->OH, d->OW, d->y_cstride, act, g.dGW, g.dG, (int64_t)d->OH * d->OW * d->y_cstride};
+  ep.bias2 = b2;
+  ep.vec = ep_vec(ep, d->K);
+  const bool tap_reuse = pair_tap_reuse(d);
+  const int ks = pair_ksplit(d, C2, act, tap_reuse);
+#ifndef FMI_HOST_EMU
+  hipStream_t st = (hipStream_t)stream;
+  if (ks > 1) {  // y = b1 + b2 first; the partial sums meet in it through atomics
+    const int64_t total = (int64_t)M * d->K;
+    hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, st, y, b1, b2, (const float*)nullptr, d->K, d->y_cstride, total);
+    ep.bias = nullptr;
+    ep.bias2 = nullptr;
+    ep.act = 3;
+    ep.vec = 0;
+  }
+  const uint16_t* w3 = (const uint16_t*)weight_pieces(d, 1, d->C);
+  const uint16_t* w32 = aligned16(w3b) ? (const uint16_t*)w3b : nullptr;
+  if (!w3 || !w32) w3 = w32 = nullptr;  // the piece images of BOTH packs, or the fp32 packs
+  if (tap_reuse) {
+    C3Args2 ca;
+    static_cast<C3Args&>(ca) = C3Args{x1, wf1, g.N, g.IH, g.IW, g.C, g.cstride, d->K, 0, make_fastdiv(g.IW), make_fastdiv(g.IH * g.IW), w3};
+    ca.x2 = x2; ca.w2 = wf2; ca.w3b = w32; ca.C2 = C2; ca.cs2 = C2;
+    return launch_conv3x3(ca, ep, M, ks, st);
+  }
+  const ConvK2 la{ConvK{x1, g}, x2, C2, C2, K1};
+  if (w3) {
+    const int64_t w3_stride = 9ll * d->C * d->K;
+    return launch_gemm(la, ConvWX32{ConvWX3{w3, g, w3_stride, d->K}, w32, C2, K1}, ep, M, d->K, Kd, 1, ks, st);
+  }
+  return launch_gemm(la, ConvWX2{ConvWX{wf1, g, 0, d->K, 1}, wf2, C2, K1}, ep, M, d->K, Kd, 1, ks, st);
+#else
+  (void)w3b;
+  return launch_gemm(ConvK2{ConvK{x1, g}, x2, C2, C2, K1}, ConvWX2{ConvWX{wf1, g, 0, d->K, 1}, wf2, C2, K1}, ep, M, d->K, Kd, 1, ks, (hipStream_t)stream);
+#endif
+}
+
+// dw1 [9][C][K], dw2 [C2][K] and dbias [K] (may be null) are ACCUMULATED into: the caller zeroes them, as for fmi_conv2d_wgrad_f32
+extern "C" int fmi_conv2d_pair_wgrad_f32(const fmi_conv_desc* d, const float* x1, const float* x2, int C2, const float* dy, float* dw1, float* dw2,
+                                         float* dbias, void* stream) {
+  if (!d) return FMI_ERR_BAD_ARG;
+  int rc = pair_check(d, C2);
+  if (rc) return rc;
+  if (!x1 || !x2 || !dy || !dw1 || !dw2) return FMI_ERR_BAD_ARG;
+  if (!aligned16(x1) || !aligned16(x2) || !aligned16(dy)) return FMI_ERR_BAD_ARG;
+  const ConvGeom g = f32_geom(fwd_geom(d, d->N), d, x1);
+  const int R1 = g.Kdim(), ones_row = dbias ? R1 + C2 : -1;
+  const int Mg = R1 + C2 + (dbias ? 1 : 0), Ng = d->K, Kg = g.Mdim();
+  const WgradAX2 la{WgradAX{x1, g, -1}, x2, C2, C2, R1, ones_row};
+  const DenseX lb{dy, (int64_t)d->y_cstride, (int64_t)d->OH * d->OW * d->y_cstride, Ng, Kg, 1};
+  const WgradEp2 ep{WgradEp{dw1, g, d->K, 0, dbias, ones_row}, dw2, R1};
+  // the pixel split of fmi_conv2d_wgrad_f32, over the taller row range
+  const int64_t tiles = ceil_div64(Mg, 128) * ceil_div64(Ng, Ng <= 32 ? 32 : (Ng <= 64 ? 64 : 128));
+  int64_t ksplit = 2048 / tiles;
+  const int64_t kmax = Kg / 512;
+  if (ksplit > kmax) ksplit = kmax;
+  if (ksplit < 1) ksplit = 1;
+  if (fmi_det()) ksplit = 1;
+  if (ksplit > 65535) ksplit = 65535;
+  return launch_gemm(la, lb, ep, Mg, Ng, Kg, 1, (int)ksplit, (hipStream_t)stream);
 }
 
 #ifndef FMI_HOST_EMU

@@ -9,8 +9,12 @@
 //                   image are zero chunks.  Anchor i, tap kx reads LDS row i + kx = pixel x + kx - 1; where that wrapped
 //                   around a row end (x = 0 with kx = 0, x = W-1 with kx = 2) the fragment is zeroed in registers.
 //   adjoint    :    dx = conv(dy, flipped taps) with reduction over the conv's output channels: same kernel, tap index 8 - t.
+//   pair       :    X2 = true (conv_pair.h): after the last (channel chunk, ky) step of x the loop goes on over 16-channel chunks of a second
+//                   dense image x2 at the CENTRE tap only (the ResBlock's 1x1 bypass), with that convolution's own weight pack: one A image
+//                   read at ky = 1, one weight tile, the kx = 1 fragments.  The single-source instantiations take C3Args / ConvEp as before.
 #pragma once
 #include "gemm_core.h"
+#include "conv_pair.h"
 
 #ifndef FMI_HOST_EMU
 struct C3Args {
@@ -21,11 +25,19 @@ struct C3Args {
   const uint16_t* w3;  // W3 kernels: the same weights as bf16 pieces [3][9][C / 8][Nout][8] (ConvWX3 in gemm_core.h)
 };
 
+struct C3Args2 : C3Args {  // the pair: second activation source and its 1x1 weight pack (fp32 [C2][Nout], pieces [3][C2 / 8][Nout][8])
+  const float* x2;
+  const float* w2;
+  const uint16_t* w3b;
+  int C2, cs2;
+};
+
 // W3: the weight tiles arrive as bf16 piece images ([3 kx][3 pieces][2 channel groups][BN] 16-byte chunks per stage) and are read as
 // ready B fragments; only the activation fragments are split in registers.
 // FL: blocked accumulation (a second accumulator set, flushed every 10 steps = 480 reduction elements), see conv_p3.h
-template <class T, bool W3, bool FL = false>
-__global__ void __launch_bounds__(256) conv3x3_dma_kernel(C3Args a, ConvEp ep, int M, int tiles_n, int ksplit, int it_chunk) {
+template <class T, bool W3, bool FL = false, bool X2 = false>
+__global__ void __launch_bounds__(256) conv3x3_dma_kernel(std::conditional_t<X2, C3Args2, C3Args> a, std::conditional_t<X2, ConvEp2, ConvEp> ep, int M,
+                                                          int tiles_n, int ksplit, int it_chunk) {
   const float* const zchunk = fmi_zero_chunk_ptr();  // the zero chunk's address: read from the GOT ONCE (see fmi_zero_chunk_ptr)
   constexpr int BM = T::BM, BN = T::BN, BK = 16;
   constexpr int RA = ((BM + 2 + 15) / 16) * 16;  // rows of the A image (multiple of the 16 rows one wave instruction writes)
@@ -41,7 +53,9 @@ __global__ void __launch_bounds__(256) conv3x3_dma_kernel(C3Args a, ConvEp ep, i
   const int tile_m = lid / tiles_n, tile_n = lid - tile_m * tiles_n;
   const int zs = blockIdx.y;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
-  const int cchunks = a.C >> 4, nit_all = 3 * cchunks;
+  const int cchunks = a.C >> 4, nit1 = 3 * cchunks;
+  int nit_all = nit1;
+  if constexpr (X2) nit_all += a.C2 >> 4;
   const int it_begin = zs * it_chunk;
   int it_end = it_begin + it_chunk;
   if (it_end > nit_all) it_end = nit_all;
@@ -49,7 +63,7 @@ __global__ void __launch_bounds__(256) conv3x3_dma_kernel(C3Args a, ConvEp ep, i
   const int HW = a.H * a.W;
 
   // A copy slots of this thread: wave instruction j*4 + wid covers LDS rows 16*(j*4+wid) .. +15, 4 lanes (k-quarters) per row
-  int64_t abase[NLA];
+  int64_t abase[NLA], abase2[X2 ? NLA : 1];
   int ay[NLA];
 #pragma unroll
   for (int j = 0; j < NLA; ++j) {
@@ -63,6 +77,7 @@ __global__ void __launch_bounds__(256) conv3x3_dma_kernel(C3Args a, ConvEp ep, i
       const uint32_t rem = (uint32_t)an - n * (uint32_t)HW;
       ay[j] = (int)fdiv(rem, a.dW);
       abase[j] = (int64_t)an * a.cs + kq;
+      if constexpr (X2) abase2[j] = (int64_t)an * a.cs2 + kq;
     }
   }
   // B copy slots: chunk p of [3][16][BN/4]
@@ -118,6 +133,28 @@ __global__ void __launch_bounds__(256) conv3x3_dma_kernel(C3Args a, ConvEp ep, i
     const int cc_ = it / 3, ky = it - 3 * cc_, c0 = cc_ * 16;  // wave-uniform
     const uint32_t sa = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(st * STAGE) * 4u + (uint32_t)wid * 1024u);  // + this wave's slot
     const uint32_t sb = sa + RA * BK * 4;
+    if constexpr (X2) {
+      if (it >= nit1) {  // wave-uniform: 16 channels of x2 at the centre tap
+        const int c2 = (it - nit1) * 16;
+#pragma unroll
+        for (int j = 0; j < NLA; ++j) {
+          if (j >= na_w) break;
+          glds16(ay[j] >= 0 ? a.x2 + abase2[j] + c2 : zchunk, sa + (uint32_t)(j * 4096));
+        }
+#pragma unroll
+        for (int j = 0; j < NLB; ++j) {
+          if (j >= nb_w) break;
+          if ((bkx[j] & 3) != 1) continue;  // only the kx = 1 tile is read back
+          const float* g;
+          if (W3)
+            g = boff[j] >= 0 ? (const float*)(a.w3b + (int64_t)(bkx[j] >> 2) * a.C2 * a.Nout + (int64_t)(c2 >> 3) * a.Nout * 8 + boff[j]) : zchunk;
+          else
+            g = boff[j] >= 0 ? a.w2 + (int64_t)c2 * a.Nout + boff[j] : zchunk;
+          glds16(g, sb + (uint32_t)(j * 4096));
+        }
+        return;
+      }
+    }
     const int64_t aoff = (int64_t)(ky - 1) * a.W * a.cs + c0;
 #pragma unroll
     for (int j = 0; j < NLA; ++j) {
@@ -139,11 +176,14 @@ __global__ void __launch_bounds__(256) conv3x3_dma_kernel(C3Args a, ConvEp ep, i
       glds16(g, sb + (uint32_t)(j * 4096));
     }
   };
-  auto compute = [&](int st) {
+  auto compute = [&](int st, bool centre) {  // centre (wave-uniform, pair only): an x2 step, only the kx = 1 tile and fragments
     const float* sa = lds + st * STAGE;
     const float* sb = sa + RA * BK;
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx) {
+      if constexpr (X2) {
+        if (centre && kx != 1) continue;
+      }
       float fa[T::TM][8], fb[T::TN][8];
 #pragma unroll
       for (int i = 0; i < T::TM; ++i) {
@@ -196,7 +236,7 @@ __global__ void __launch_bounds__(256) conv3x3_dma_kernel(C3Args a, ConvEp ep, i
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (it + 1 < it_end) issue(it + 1, st ^ 1);
-    compute(st);
+    compute(st, X2 && it >= nit1);
     st ^= 1;
     if constexpr (FL) {
       if (++since == 10 || it + 1 == it_end) {
@@ -219,7 +259,7 @@ __global__ void __launch_bounds__(256) conv3x3_dma_kernel(C3Args a, ConvEp ep, i
 #pragma unroll
       for (int j = 0; j < T::TN; ++j) acc[i][j] = acc2[i][j];
   }
-  store_tile<ConvEp, T>(ep, acc, M, a.Nout, m0 + wm, n0 + wn, lh, l31);
+  store_tile<std::conditional_t<X2, ConvEp2, ConvEp>, T>(ep, acc, M, a.Nout, m0 + wm, n0 + wn, lh, l31);
 }
 
 // geometry the tap-reuse kernel takes (the caller falls back to the generic path otherwise).  C >= 64 or a narrow output: with 32
@@ -231,8 +271,15 @@ static bool conv3x3_eligible(const float* x, const float* w, int C, int cs, int 
 
 using Tile128x64w = TileCfg<4, 1, 1, 2>;  // 128 x 64 with every wave spanning both column tiles: one activation split per 12 MFMAs
 
-static int launch_conv3x3(const C3Args& a, const ConvEp& ep, int M, int ksplit, hipStream_t st) {
-  const int nit = 3 * (a.C >> 4);
+// reduction steps of a launch: 3 per 16-channel chunk of x, one per 16-channel chunk of the pair's x2
+static int c3_steps(const C3Args& a) { return 3 * (a.C >> 4); }
+static int c3_steps(const C3Args2& a) { return 3 * (a.C >> 4) + (a.C2 >> 4); }
+
+template <class ARGS, class EP>
+static int launch_conv3x3(const ARGS& a, const EP& ep, int M, int ksplit, hipStream_t st) {
+  constexpr bool X2 = std::is_same<ARGS, C3Args2>::value;
+  static_assert(std::is_same<EP, std::conditional_t<X2, ConvEp2, ConvEp>>::value, "the pair launches with ConvEp2");
+  const int nit = c3_steps(a);
   if (ksplit > nit) ksplit = nit;
   const int it_chunk = (nit + ksplit - 1) / ksplit;
   ksplit = (nit + it_chunk - 1) / it_chunk;
@@ -240,10 +287,10 @@ static int launch_conv3x3(const C3Args& a, const ConvEp& ep, int M, int ksplit, 
   do {                                                                                                                        \
     const int64_t tm = ceil_div64(M, TILE::BM), tn = ceil_div64(a.Nout, TILE::BN);                                            \
     if (fl)                                                                                                                   \
-      hipLaunchKernelGGL((conv3x3_dma_kernel<TILE, W3, true>), dim3((unsigned)(tm * tn), (unsigned)ksplit), dim3(256), 0, st, a, ep, M, (int)tn, \
+      hipLaunchKernelGGL((conv3x3_dma_kernel<TILE, W3, true, X2>), dim3((unsigned)(tm * tn), (unsigned)ksplit), dim3(256), 0, st, a, ep, M, (int)tn, \
                          ksplit, it_chunk);                                                                                   \
     else                                                                                                                      \
-      hipLaunchKernelGGL((conv3x3_dma_kernel<TILE, W3>), dim3((unsigned)(tm * tn), (unsigned)ksplit), dim3(256), 0, st, a, ep, M, (int)tn, ksplit, \
+      hipLaunchKernelGGL((conv3x3_dma_kernel<TILE, W3, false, X2>), dim3((unsigned)(tm * tn), (unsigned)ksplit), dim3(256), 0, st, a, ep, M, (int)tn, ksplit, \
                          it_chunk);                                                                                           \
   } while (0)
 #define C3_LAUNCH(TILE) C3_LAUNCH_(TILE, false)

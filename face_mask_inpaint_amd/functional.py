@@ -552,6 +552,120 @@ def conv2d(x, pw: PackedWeight, bias=None, residual=None, stride=1, pad=0, pad_m
     return _Conv2d.apply(x, pw.wf, bias, residual, pw.wt, pw.kh, pw.kw, stride, pad, pad_mode, act, in_act, skip_act_bwd, int(dilation), bool(passthrough), pw.w3)
 
 
+class _Conv2dPair(torch.autograd.Function):
+    """y = act(conv3x3(f(x1), W1) + conv1x1(x2, W2) + b1 + b2), stride 1, pad 1: the main path's last convolution and the 1x1 bypass of a
+    ResBlock as one reduction (fmi_conv2d_pair_fwd_f32); dW1, dW2 and the gradient of both biases come from one walk over dy
+    (fmi_conv2d_pair_wgrad_f32); the two input gradients are the two adjoint launches of the single convolutions."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, wf1, wf2, b1, b2, wt1, wt2, act, in_act, w3_1, w3_2, route=3):
+        """in_act: None or ("apply", slope): the 3x3 convolution reads lrelu(x1, slope), as in _Conv2d.  route: fmi_conv2d_pair_routed's bits
+        -- 1: the fused forward, 2: the fused weight gradient; a pass without its bit runs as the two single launches"""
+        _chk(x1, x2, wf1, wf2, b1, b2)
+        lib = _L()
+        n, h, w, c1 = x1.shape
+        c2, k = x2.shape[3], wf1.shape[2]
+        if in_act is not None:
+            x1 = eltwise(EW_LRELU, x1, None, in_act[1])
+        both3 = w3_1[0] is not None and w3_2[0] is not None
+        d, _, _ = conv_desc(n, h, w, c1, k, 3, 3, 1, 1, w3=w3_1[0] if both3 else None)
+        y = torch.empty((n, h, w, k), device=x1.device, dtype=torch.float32)
+        if route & 1:
+            with _prof(f"conv_fwd|{n}x{h}x{w} {c1}->{k} k3s1 +1x1 {c2}", 2.0 * n * h * w * k * (9 * c1 + c2)):
+                lib.conv2d_pair_fwd_f32(C.byref(d), _p(x1), _p(x2), c2, _p(wf1), _p(wf2), C.c_void_p(w3_2[0].data_ptr()) if both3 else None,
+                                        _p(b1), _p(b2), _p(y), act, _st())
+        else:
+            s = torch.empty_like(y)
+            d2, _, _ = conv_desc(n, h, w, c2, k, 1, 1, 1, 0, w3=w3_2[0])
+            with _prof(f"conv_fwd|{n}x{h}x{w} {c2}->{k} k1s1", 2.0 * n * h * w * k * c2):
+                lib.conv2d_fwd_f32(C.byref(d2), _p(x2), _p(wf2), _p(b2), None, _p(s), 0, 1, 0, _st())
+            d, _, _ = conv_desc(n, h, w, c1, k, 3, 3, 1, 1, w3=w3_1[0])
+            with _prof(f"conv_fwd|{n}x{h}x{w} {c1}->{k} k3s1", 2.0 * n * h * w * k * c1 * 9):
+                lib.conv2d_fwd_f32(C.byref(d), _p(x1), _p(wf1), _p(b1), _p(s), _p(y), act, 1, 0, _st())
+        ctx.save_for_backward(x1, x2, wf1, wf2, y if act else None)
+        ctx.wt, ctx.wt3, ctx.act = (wt1, wt2), (w3_1[1], w3_2[1]), act
+        ctx.has_b = (b1 is not None, b2 is not None)
+        ctx.in_slope = None if in_act is None else float(in_act[1])
+        ctx.route = route
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        lib = _L()
+        x1, x2, wf1, wf2, y = ctx.saved_tensors
+        gy = gy.contiguous()
+        if ctx.act:
+            gy = _act_bwd(gy, y, ctx.act)
+        n, h, w, c1 = x1.shape
+        c2, k = x2.shape[3], wf1.shape[2]
+        gx1 = gx2 = gwf1 = gwf2 = gb = None
+        if ctx.needs_input_grad[0]:
+            gy3 = p3_of(gy) if (ctx.wt3[0] is not None and p3_wanted(n * h * w, k, c1, 9)) else None
+            d, _, _ = conv_desc(n, h, w, c1, k, 3, 3, 1, 1, w3=ctx.wt3[0], x3=gy3)
+            gx1 = torch.empty_like(x1)
+            with _prof(f"conv_dgrad|{n}x{h}x{w} {c1}->{k} k3s1", 2.0 * gy.numel() * c1 * 9):
+                if ctx.in_slope is not None:  # act'(x1) in the adjoint's epilogue
+                    lib.conv2d_dgrad_masked_f32(C.byref(d), _p(gy), _p(ctx.wt[0]), _p(x1), ctx.in_slope, _p(gx1), _st())
+                else:
+                    lib.conv2d_dgrad_f32(C.byref(d), _p(gy), _p(ctx.wt[0]), None, None, _p(gx1), 1, 0, _st())
+        if ctx.needs_input_grad[1]:
+            d, _, _ = conv_desc(n, h, w, c2, k, 1, 1, 1, 0, w3=ctx.wt3[1])
+            gx2 = torch.empty_like(x2)
+            with _prof(f"conv_dgrad|{n}x{h}x{w} {c2}->{k} k1s1", 2.0 * gy.numel() * c2):
+                lib.conv2d_dgrad_f32(C.byref(d), _p(gy), _p(ctx.wt[1]), None, None, _p(gx2), 1, 0, _st())
+        want_gb = (ctx.has_b[0] and ctx.needs_input_grad[4]) or (ctx.has_b[1] and ctx.needs_input_grad[5])
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            d, _, _ = conv_desc(n, h, w, c1, k, 3, 3, 1, 1)
+            gwf1, gwf2 = _zeros_like(wf1), _zeros_like(wf2)
+            if want_gb:
+                gb = _zeros(k, x1.device, torch.float32)
+            if ctx.route & 2:
+                with _prof(f"conv_wgrad|{n}x{h}x{w} {c1}->{k} k3s1 +1x1 {c2}", 2.0 * gy.numel() * (9 * c1 + c2)):
+                    lib.conv2d_pair_wgrad_f32(C.byref(d), _p(x1), _p(x2), c2, _p(gy), _p(gwf1), _p(gwf2), _p(gb), _st())
+            else:
+                with _prof(f"conv_wgrad|{n}x{h}x{w} {c1}->{k} k3s1", 2.0 * gy.numel() * c1 * 9):
+                    lib.conv2d_wgrad_f32(C.byref(d), _p(x1), _p(gy), _p(gwf1), _p(gb), 1, 0, _st())
+                d2, _, _ = conv_desc(n, h, w, c2, k, 1, 1, 1, 0)
+                with _prof(f"conv_wgrad|{n}x{h}x{w} {c2}->{k} k1s1", 2.0 * gy.numel() * c2):
+                    lib.conv2d_wgrad_f32(C.byref(d2), _p(x2), _p(gy), _p(gwf2), None, 1, 0, _st())
+        elif want_gb:
+            gb = _zeros(k, x1.device, torch.float32)
+            lib.bias_grad_f32(_p(gy), gy.numel() // k, k, k, _p(gb), _st())
+        gb1 = gb if (ctx.has_b[0] and ctx.needs_input_grad[4]) else None
+        gb2 = gb if (ctx.has_b[1] and ctx.needs_input_grad[5]) else None  # the same sum over dy is the gradient of both biases
+        return gx1, gx2, gwf1, gwf2, gb1, gb2, None, None, None, None, None, None, None
+
+
+PAIR_ENABLED = True  # False: ResBlock keeps conv2 and the bypass as two launches everywhere (the comparison route of the tests)
+
+
+def conv2d_pair_ok(x1, pw1: PackedWeight, x2, pw2: PackedWeight) -> int:
+    """which passes of conv3x3(x1, pw1) + conv1x1(x2, pw2) conv2d_pair runs fused: 0 (none: the two-launch form), else the bits of
+    fmi_conv2d_pair_routed (1: forward, 2: weight gradient).  Needs fp32 dense 16-byte aligned tensors on the device and a shape at which
+    the library measured the fused launch faster (profiles/resblock_pair.txt)"""
+    if not PAIR_ENABLED or not (x1.is_cuda and x2.is_cuda) or x1.dtype != torch.float32 or x2.dtype != torch.float32:
+        return 0
+    if not torch.is_grad_enabled():  # inference keeps its launch sequence: the routing table was measured on the training step's shapes
+        return 0
+    if (pw1.kh, pw1.kw, pw2.kh, pw2.kw) != (3, 3, 1, 1) or x1.dim() != 4 or x1.shape[:3] != x2.shape[:3] or pw1.wf.shape[2] != pw2.wf.shape[2]:
+        return 0
+    if not (x1.is_contiguous() and x2.is_contiguous()) or x1.data_ptr() % 16 or x2.data_ptr() % 16:
+        return 0
+    n, h, w, c1 = x1.shape
+    d, _, _ = conv_desc(n, h, w, c1, pw1.wf.shape[2], 3, 3, 1, 1)
+    return int(_L().conv2d_pair_routed(C.byref(d), x2.shape[3]))
+
+
+def conv2d_pair(x1, pw1: PackedWeight, b1, x2, pw2: PackedWeight, b2, act=ACT_NONE, in_act=None):
+    """act(conv3x3(f(x1)) + conv1x1(x2) + b1 + b2): the passes conv2d_pair_ok names run as one launch each, the others (all of them where it
+    says 0) as the 1x1 convolution and the 3x3 one with its result as the residual.  in_act: None or ("apply", slope), see _Conv2d"""
+    route = conv2d_pair_ok(x1, pw1, x2, pw2)
+    if route:
+        return _Conv2dPair.apply(x1, x2, pw1.wf, pw2.wf, b1, b2, pw1.wt, pw2.wt, act, in_act, pw1.w3, pw2.w3, route)
+    s = conv2d(x2, pw2, b2)
+    return conv2d(x1, pw1, b1, s, 1, 1, 0, act, in_act)
+
+
 # ---- bf16 activations (StyleGAN2 decoder of configs C3 / C5): fp32 master weights, bf16 copies packed per call ----
 BF16 = torch.bfloat16
 

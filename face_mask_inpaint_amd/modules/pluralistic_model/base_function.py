@@ -178,6 +178,18 @@ class ResBlock(_NhwcBlock):
         h = FF.conv2d_enc_bf16(h, packed(c2), c2.bias, 1)
         return FF.resblock_tail_bf16(h, s, self.sample, self._slope, raw, act, f32)
 
+    def _conv2_plus_bypass(self, h, xp, in_act):
+        """model(x) + shortcut(x): conv2 and the 1x1 bypass as one reduction where the fused launches take the shape (FF.conv2d_pair), else
+        the bypass launch and conv2 with its result as the residual of the epilogue"""
+        c2, cb = _conv(self.conv2), _conv(self.bypass)
+        for c in (c2, cb):
+            if c.stride != (1, 1) or c.dilation != (1, 1) or c.groups != 1:
+                raise NotImplementedError("Conv2d geometry outside the hot path")
+        if c2.padding == (1, 1) and cb.padding == (0, 0):
+            return FF.conv2d_pair(h, packed(c2), c2.bias, xp, packed(cb), cb.bias, in_act=in_act)
+        s = run_conv(cb, xp)
+        return run_conv(c2, h, residual=s, in_act=in_act)
+
     def nhwc(self, x):
         with weight_scope(self):
             # x has two consumers (the main path and the 1x1 bypass): the bypass reads the pass-through copy the main path's first op
@@ -186,14 +198,12 @@ class ResBlock(_NhwcBlock):
                 # LeakyReLU -> conv pairs: the activation is applied on the way in and differentiated in the adjoint's epilogue
                 act_in = ("apply", self._slope)
                 h, xp = run_conv(_conv(self.conv1), x, in_act=act_in, passthrough=True)
-                s = run_conv(_conv(self.bypass), xp)
-                out = run_conv(_conv(self.conv2), h, residual=s, in_act=act_in)  # model(x) + shortcut(x), fused in the epilogue
+                out = self._conv2_plus_bypass(h, xp, act_in)
             else:
                 h, xp = _norm_act(self.model[0], x, self._slope, passthrough=True)
-                s = run_conv(_conv(self.bypass), xp)
                 h = run_conv(_conv(self.conv1), h)
                 h = _norm_act(self.model[3], h, self._slope)
-                out = run_conv(_conv(self.conv2), h, residual=s)  # model(x) + shortcut(x), fused in the epilogue
+                out = self._conv2_plus_bypass(h, xp, None)
             if self.sample:  # pool(a) + pool(b) == pool(a + b)
                 out = FF.avg_pool(out, 2)
             return out

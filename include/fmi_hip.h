@@ -156,6 +156,25 @@ int fmi_conv_transpose2d_pair_bwd_f32(const fmi_conv_desc* d, const float* x1, c
                                       int64_t ws_bytes, void* stream);
 int fmi_conv2d_dgrad_f32(const fmi_conv_desc* d, const float* dy, const float* wt, const float* bias,
                          const float* residual, float* dx, int batch_w, int64_t w_bstride, void* stream);
+/* The stride-1 ResBlock's  y = act(conv3x3(x1, W1) + conv1x1(x2, W2) + b1 + b2)  in one launch (csrc/conv_pair.h): after the 9 * C (tap,
+ * channel) reduction steps over x1 the reduction goes on over the C2 channels of x2 at the centre tap.  d describes the 3x3 convolution
+ * (kernel 3, stride 1, pad 1, zero padding, dense NHWC, d->C % 16 == 0, d->K % 4 == 0; d->w3 = the piece image of its forward pack or
+ * NULL); x2 is dense [N][H][W][C2], C2 % 16 == 0; wf1 [9][C][K], wf2 [C2][K] the forward packs and w3b wf2's piece image (NULL: the fp32
+ * packs are read); b1 / b2 may be NULL.  A split reduction (fmi_conv2d_pair_ksplit(d, C2, act) > 1; never with an activation nor in
+ * reproducible mode) starts from y = b1 + b2 and adds partial sums atomically.  Any other geometry: FMI_ERR_UNSUPPORTED (_supported says
+ * 0); a NULL required pointer or one off 16-byte alignment: FMI_ERR_BAD_ARG; both before any launch.  _routed: which passes of a supported
+ * shape were measured faster than the single launches in every round (profiles/resblock_pair.txt): bit 0 the forward, bit 1 the weight
+ * gradient; 0: keep the two-launch form.
+ * fmi_conv2d_pair_wgrad_f32: dw1 [9][C][K], dw2 [C2][K] and dbias [K] (the gradient of b1 AND of b2; may be NULL) from one walk over dy,
+ * ACCUMULATED into zeroed destinations with the pixel split, atomics and reproducible-mode rule of fmi_conv2d_wgrad_f32.  The two input
+ * gradients are two fmi_conv2d_dgrad_*_f32 calls. */
+int fmi_conv2d_pair_supported(const fmi_conv_desc* d, int C2);
+int fmi_conv2d_pair_routed(const fmi_conv_desc* d, int C2);
+int fmi_conv2d_pair_ksplit(const fmi_conv_desc* d, int C2, int act);
+int fmi_conv2d_pair_fwd_f32(const fmi_conv_desc* d, const float* x1, const float* x2, int C2, const float* wf1, const float* wf2,
+                            const void* w3b, const float* b1, const float* b2, float* y, int act, void* stream);
+int fmi_conv2d_pair_wgrad_f32(const fmi_conv_desc* d, const float* x1, const float* x2, int C2, const float* dy, float* dw1, float* dw2,
+                              float* dbias, void* stream);
 /* Adjoint of  act(x) -> conv : dx = conv_adjoint(dy, wt) * act'(x), act' = (mask > 0 ? 1 : mask_slope); mask = x or act(x), dx's layout.
  * The LeakyReLU -> conv pairs of ResBlock / ResBlockEncoderOptimized (base_function.py:207-305) and the ReLU -> conv pairs inside
  * VGG16 (loss.py:45-65): the multiplication happens in the GEMM epilogue, the separate activation-backward pass disappears.
