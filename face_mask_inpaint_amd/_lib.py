@@ -92,6 +92,10 @@ SIGNATURES = {
     "fmi_fpn_merge_in_bf16": [vp] * 3 + [i32] * 6 + [vp],
     "fmi_mask_blend_bf16": [vp] * 4 + [i64, i32, vp],
     "fmi_conv2d_c32_fwd_bf16": [PD, vp, vp, vp, f32, vp, vp],
+    "fmi_conv2d_dgrad_relu_bf16": [PD, vp, vp, vp, vp, vp],
+    "fmi_vgg_tap_fwd_bf16": [vp, vp, vp, i32, i32, i32, i32, vp],
+    "fmi_vgg_tap_bwd_bf16": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "fmi_conv2d_thin_input_dgrad_bf16": [PD, vp, vp, vp, vp],
     "fmi_resblock_tail_bf16": [vp] * 5 + [i32] * 5 + [f32, vp],
     "fmi_picnet_stem_tail_bf16": [vp] * 6 + [i32] * 5 + [f32, vp],
     "fmi_guided_attention_fwd_bf16": [vp] * 5 + [i32] * 5 + [vp],
@@ -213,7 +217,7 @@ SIGNATURES = {
 STATUS = {0: "ok", 1: "bad argument", 2: "unsupported shape/mode", 3: "kernel launch failed"}
 
 
-PREDICATES = {"fmi_debug_bf16_tile": [i32], "fmi_set_deterministic": [i32], "fmi_get_deterministic": [], "fmi_conv2d_thin_supported": [PD], "fmi_conv2d_bf16_supported": [PD], "fmi_conv2d_thin_lrelu_supported": [PD], "fmi_conv2d_thin_lrelu_bwd_ws_bytes": [PD], "fmi_conv2d_thin_in_supported": [PD], "fmi_conv2d_thin_in_routed": [PD], "fmi_conv2d_thin_in_wgrad_ws_bytes": [PD], "fmi_conv2d_pair_supported": [PD, i32], "fmi_conv2d_pair_routed": [PD, i32], "fmi_conv2d_pair_ksplit": [PD, i32, i32], "fmi_conv_transpose2d_pair_bwd_supported": [PD, i32, i32], "fmi_conv_transpose2d_pair_bwd_ws_bytes": [PD, i32, i32], "fmi_attention_fwd_uses_pieces": [i32] * 5, "fmi_attention_bwd_uses_pieces": [i32] * 5, "fmi_attention_fwd_waves": [i32] * 2, "fmi_attention_fwd_bf16_waves": [i32] * 2, "fmi_guided_attention_fwd_bf16_waves": [i32] * 2, "fmi_attention_bwd_structure": [i32] * 2}
+PREDICATES = {"fmi_debug_bf16_tile": [i32], "fmi_debug_bf16_last_tile": [], "fmi_set_deterministic": [i32], "fmi_get_deterministic": [], "fmi_conv2d_thin_supported": [PD], "fmi_conv2d_bf16_supported": [PD], "fmi_conv2d_thin_lrelu_supported": [PD], "fmi_conv2d_thin_lrelu_bwd_ws_bytes": [PD], "fmi_conv2d_thin_in_supported": [PD], "fmi_conv2d_thin_in_routed": [PD], "fmi_conv2d_thin_in_wgrad_ws_bytes": [PD], "fmi_conv2d_pair_supported": [PD, i32], "fmi_conv2d_pair_routed": [PD, i32], "fmi_conv2d_pair_ksplit": [PD, i32, i32], "fmi_conv_transpose2d_pair_bwd_supported": [PD, i32, i32], "fmi_conv_transpose2d_pair_bwd_ws_bytes": [PD, i32, i32], "fmi_attention_fwd_uses_pieces": [i32] * 5, "fmi_attention_bwd_uses_pieces": [i32] * 5, "fmi_attention_fwd_waves": [i32] * 2, "fmi_attention_fwd_bf16_waves": [i32] * 2, "fmi_guided_attention_fwd_bf16_waves": [i32] * 2, "fmi_attention_bwd_structure": [i32] * 2}
 
 
 class FmiError(RuntimeError):

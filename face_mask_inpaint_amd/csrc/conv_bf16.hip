@@ -163,6 +163,19 @@ struct EpChanB {
   float* colsum;       // [ceil(M / 64)][2][Nout] or null
 };
 
+// EpMaskB: the adjoint whose result is the gradient of a ReLU's OUTPUT (the VGG16 trunk of VGGLoss in bf16, modules/loss.py:33-52 of the
+// reference: the convolutions of a block that read another convolution's activated map).  a = that activated map, with the geometry and
+// channel stride of the tensor this launch writes: y = a > 0 ? acc : 0, one rounding to bf16, 8-byte loads of a beside the 8-byte stores.
+// Also the output stage of the eight-phase kernel (conv_bf16_8ph.h).  One phase, no split reduction.
+struct EpMaskB {
+  const bf16_t* a;
+};
+template <class V>  // float[4] or a four-float vector: both kernels apply ONE rule (a NaN and a negative zero mask)
+__device__ __forceinline__ void ep_mask4(uint2 m, V& v) {
+  v[0] = bf_lo(m.x) > 0.f ? v[0] : 0.f, v[1] = bf_hi(m.x) > 0.f ? v[1] : 0.f;
+  v[2] = bf_lo(m.y) > 0.f ? v[2] : 0.f, v[3] = bf_hi(m.y) > 0.f ? v[3] : 0.f;
+}
+
 template <class T, int BK, int NST = 2, class CH = EpNoneB>
 __global__ void __launch_bounds__(T::NT) conv_bf16_kernel(ConvSetB set, CH ch) {
   const float* const zchunk = fmi_zero_chunk_ptr();  // the zero chunk's address: read from the GOT ONCE (see fmi_zero_chunk_ptr)
@@ -430,6 +443,30 @@ __global__ void __launch_bounds__(T::NT) conv_bf16_kernel(ConvSetB set, CH ch) {
     }
     return;
   }
+  if constexpr (std::is_same<CH, EpMaskB>::value) {  // N % 4 == 0, 8-byte aligned rows of y and of the mask's map (the host checks)
+#pragma unroll
+    for (int i = 0; i < T::TM; ++i) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int row = m0 + wm + i * 32 + 8 * g + 4 * lh + c;
+        int n_s = 0;
+        const int64_t off = row < M ? ep.row_off(row, n_s) : 0;
+#pragma unroll
+        for (int j = 0; j < T::TN; ++j) {
+          float a[4] = {acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
+          quad_transpose(a, c);
+          const int col = n0 + wn + j * 32 + colq;
+          if (row >= M || col >= N) continue;
+          ep_mask4(*reinterpret_cast<const uint2*>(ch.a + off + col), a);
+          uint2 v;
+          v.x = bf_pack2(a[0], a[1]);
+          v.y = bf_pack2(a[2], a[3]);
+          *reinterpret_cast<uint2*>(ep.y + off + col) = v;
+        }
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < T::TM; ++i) {
 #pragma unroll
@@ -490,13 +527,16 @@ extern "C" int fmi_debug_bf16_tile(int mode) {
   if (mode >= 0) g_bf16_tile_mode = mode;
   return prev;
 }
+// the tile launch_conv_bf16 took last (tests assert which kernel a shape reached): 1000 BM + BN, plus 1000000 for the eight-phase kernel
+static int g_bf16_last_tile = 0;
+extern "C" int fmi_debug_bf16_last_tile(void) { return g_bf16_last_tile; }
 
 // phases: nph filled entries of set.ph (la, lb, ep, M, K); N = output channels.  ws (may be null): zeroed fp32 twin of the output
 // tensor with out_elems elements -- small feature maps with a deep reduction (the 4^2 .. 16^2 layers: 2 - 32 output tiles) then
 // split the reduction over workgroups and the sums are converted to bf16 by a second launch.
 template <int BK>
 static int launch_conv_bf16(ConvSetB& set, int nph, int N, bf16_t* y, float* ws, int64_t ws_floats, int64_t out_elems, hipStream_t st,
-                            const EpActB* act = nullptr) {
+                            const EpActB* act = nullptr, const EpMaskB* mask = nullptr) {
   int Mmax = 0, Kmax = 0;
   for (int p = 0; p < nph; ++p) {
     if (set.ph[p].M > Mmax) Mmax = set.ph[p].M;
@@ -522,7 +562,14 @@ static int launch_conv_bf16(ConvSetB& set, int nph, int N, bf16_t* y, float* ws,
     }                                                                                                                             \
     set.tiles_n = (int)tn;                                                                                                        \
     set.ksplit = (int)ks;                                                                                                         \
+    g_bf16_last_tile = TILE::BM * 1000 + TILE::BN;                                                                                \
     set.ws = ks > 1 ? ws : nullptr;                                                                                               \
+    if (mask) { /* the masked adjoint: 64-deep reduction tiles and at least 64 output columns (ws is null: ks == 1) */           \
+      if constexpr (BK == 64 && TILE::BN >= 64)                                                                                   \
+        hipLaunchKernelGGL((conv_bf16_kernel<TILE, BK, 2, EpMaskB>), dim3((unsigned)tmax, nph, 1), dim3(TILE::NT), 0, st, set, *mask); \
+      else return FMI_ERR_UNSUPPORTED;                                                                                            \
+      break;                                                                                                                      \
+    }                                                                                                                             \
     hipLaunchKernelGGL((conv_bf16_kernel<TILE, BK>), dim3((unsigned)tmax, nph, (unsigned)ks), dim3(TILE::NT), 0, st, set, EpNoneB{}); \
     if (ks > 1)                                                                                                                   \
       hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(fmi_bw_grid(out_elems / 4, 256)), dim3(256), 0, st, ws, y, out_elems / 4);      \
@@ -552,9 +599,15 @@ static int launch_conv_bf16(ConvSetB& set, int nph, int N, bf16_t* y, float* ws,
       set.tiles_n = (int)tn;
       set.ksplit = 1;
       set.ws = nullptr;
+      g_bf16_last_tile = 1000000 + (wide ? 256256 : 512128);
       EpActB a{};
       if (act) a = *act;
-      if (wide) hipLaunchKernelGGL((conv_bf16_8ph_kernel<T8P256x256>), dim3((unsigned)tmax, nph, 1), dim3(512), 0, st, set, a);
+      if (mask) {
+        if constexpr (BK == 64) {
+          if (wide) hipLaunchKernelGGL((conv_bf16_8ph_kernel<T8P256x256, EpMaskB>), dim3((unsigned)tmax, nph, 1), dim3(512), 0, st, set, *mask);
+          else hipLaunchKernelGGL((conv_bf16_8ph_kernel<T8P512x128, EpMaskB>), dim3((unsigned)tmax, nph, 1), dim3(512), 0, st, set, *mask);
+        }
+      } else if (wide) hipLaunchKernelGGL((conv_bf16_8ph_kernel<T8P256x256>), dim3((unsigned)tmax, nph, 1), dim3(512), 0, st, set, a);
       else hipLaunchKernelGGL((conv_bf16_8ph_kernel<T8P512x128>), dim3((unsigned)tmax, nph, 1), dim3(512), 0, st, set, a);
       return fmi_launch_status();
     }
@@ -699,16 +752,10 @@ int fmi_conv_bf16_grouped_tiles(const fmi_conv_desc* d, int G, int64_t x_off, in
 #undef FMI_LAUNCH_G
   return fmi_launch_status();
 }
-/* dx = adjoint of the convolution described by d applied to dy; wck = weights packed [C][kh*kw][K] */
-extern "C" int fmi_conv2d_dgrad_bf16(const fmi_conv_desc* d, const uint16_t* dy, const uint16_t* wck, const float* colscale, uint16_t* dx,
-                                     float* ws, int64_t ws_floats, void* stream) {
-  int rc = check_desc_b(d);
-  if (rc) return rc;
-  if (!dy || !wck || !dx) return FMI_ERR_BAD_ARG;
-  if (d->K % 32 != 0 || d->y_cstride % 8 != 0 || !fmi_al16(dy) || !fmi_al16(wck)) return FMI_ERR_UNSUPPORTED;
+// The phases of an adjoint launch: one ConvPhaseB per non-empty sub-pixel phase of the stride (geometry, both loaders, the addressing of
+// the output stage, M, K); returns their number.
+static int adj_set_b(const fmi_conv_desc* d, const uint16_t* dy, const uint16_t* wck, const float* colscale, uint16_t* dx, ConvSetB& set) {
   const int s = d->stride;
-  if (s > 2) return FMI_ERR_UNSUPPORTED;  // at most four sub-pixel phases per launch
-  ConvSetB set{};
   int nph = 0;
   for (int py = 0; py < s; ++py) {
     for (int px = 0; px < s; ++px) {
@@ -726,11 +773,39 @@ extern "C" int fmi_conv2d_dgrad_bf16(const fmi_conv_desc* d, const uint16_t* dy,
       P.K = g.Kdim();
     }
   }
+  return nph;
+}
+/* dx = adjoint of the convolution described by d applied to dy; wck = weights packed [C][kh*kw][K] */
+extern "C" int fmi_conv2d_dgrad_bf16(const fmi_conv_desc* d, const uint16_t* dy, const uint16_t* wck, const float* colscale, uint16_t* dx,
+                                     float* ws, int64_t ws_floats, void* stream) {
+  int rc = check_desc_b(d);
+  if (rc) return rc;
+  if (!dy || !wck || !dx) return FMI_ERR_BAD_ARG;
+  if (d->K % 32 != 0 || d->y_cstride % 8 != 0 || !fmi_al16(dy) || !fmi_al16(wck)) return FMI_ERR_UNSUPPORTED;
+  if (d->stride > 2) return FMI_ERR_UNSUPPORTED;  // at most four sub-pixel phases per launch
+  ConvSetB set{};
+  const int nph = adj_set_b(d, dy, wck, colscale, dx, set);
   if (nph == 0) return FMI_OK;
   const int64_t out_elems = (int64_t)d->N * d->H * d->W * d->x_cstride;
   if (ws && (((uintptr_t)ws & 15) || ((uintptr_t)dx & 7))) ws = nullptr;
   return d->K % 64 == 0 ? launch_conv_bf16<64>(set, nph, d->C, dx, ws, ws_floats, out_elems, (hipStream_t)stream)
                         : launch_conv_bf16<32>(set, nph, d->C, dx, ws, ws_floats, out_elems, (hipStream_t)stream);
+}
+/* dx = a_in > 0 ? adjoint(dy) : 0 -- fmi_conv2d_dgrad_bf16 with the mask of the ReLU that produced the convolution's input in the output
+ * stage (EpMaskB): the convolutions of a VGG16 block that read another convolution's activated map (modules/loss.py:33-52 of the
+ * reference).  a_in has the geometry of dx.  3x3, stride 1, pad 1, C and K multiples of 64; the tile is the one the plain adjoint takes
+ * for the shape, without the split reduction: no atomics, the same bits every run. */
+extern "C" int fmi_conv2d_dgrad_relu_bf16(const fmi_conv_desc* d, const uint16_t* dy, const uint16_t* wck, const uint16_t* a_in, uint16_t* dx,
+                                          void* stream) {
+  int rc = check_desc_b(d);
+  if (rc) return rc;
+  if (!dy || !wck || !a_in || !dx) return FMI_ERR_BAD_ARG;
+  if (d->kh != 3 || d->kw != 3 || d->pad != 1 || d->stride != 1 || d->C % 64 != 0 || d->K % 64 != 0) return FMI_ERR_UNSUPPORTED;
+  if (d->x_cstride % 4 != 0 || d->y_cstride % 8 != 0 || !fmi_al16(dy) || !fmi_al16(wck) || !fmi_al16(a_in) || !fmi_al16(dx)) return FMI_ERR_UNSUPPORTED;
+  ConvSetB set{};
+  const int nph = adj_set_b(d, dy, wck, nullptr, dx, set);  // one phase, its 8-byte stores on (checked above)
+  const EpMaskB mask{a_in};
+  return launch_conv_bf16<64>(set, nph, d->C, dx, nullptr, 0, (int64_t)d->N * d->H * d->W * d->x_cstride, (hipStream_t)stream, nullptr, &mask);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -53,8 +53,10 @@ struct EpActB {
 typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 
-template <class T>
-__global__ void __launch_bounds__(512) conv_bf16_8ph_kernel(ConvSetB set, EpActB act) {
+// CH: the output stage -- EpActB (plain when its `on` is 0) or EpMaskB (conv_bf16.hip: y = a > 0 ? acc : 0, the masked adjoint)
+template <class T, class CH = EpActB>
+__global__ void __launch_bounds__(512) conv_bf16_8ph_kernel(ConvSetB set, CH act) {
+  constexpr bool MASK = std::is_same<CH, EpMaskB>::value;
   constexpr int BM = T::BM, BN = T::BN, NA = T::NA, NB = T::NB, AH = T::AH, BH = T::BH, STAGE = T::STAGE;
   const int lid = xcd_remap(blockIdx.x, gridDim.x);
   if (lid >= set.ph[blockIdx.y].tiles) return;  // whole workgroup
@@ -304,7 +306,8 @@ __global__ void __launch_bounds__(512) conv_bf16_8ph_kernel(ConvSetB set, EpActB
   const ConvEpB ep = set.ph[blockIdx.y].ep;
   const int M = set.ph[blockIdx.y].M, N = set.N;
   const int cl = 4 * (lane >> 4);
-  const float nwv = (act.on && act.noise) ? act.nw[0] : 0.f;
+  float nwv = 0.f;
+  if constexpr (!MASK) nwv = (act.on && act.noise) ? act.nw[0] : 0.f;
   // a plain stride-1 convolution writes anchor row r to pixel r: no decode of (sample, y, x) per row -- eight of them per lane were a
   // quarter of this stage's instructions; the sample index is only needed for the per-sample column scale
   const bool linear = ep.OS == 1 && ep.GH == ep.OHt && ep.GW == ep.OWt;
@@ -319,7 +322,8 @@ __global__ void __launch_bounds__(512) conv_bf16_8ph_kernel(ConvSetB set, EpActB
       const int col = n0 + wc * 64 + j * 32 + c * 16 + cl;
       bsv[j][c] = make_float4(0.f, 0.f, 0.f, 0.f);
       csv[j][c] = make_float4(1.f, 1.f, 1.f, 1.f);
-      if (act.on && act.bias && col < N) bsv[j][c] = *reinterpret_cast<const float4*>(act.bias + col);
+      if constexpr (!MASK)
+        if (act.on && act.bias && col < N) bsv[j][c] = *reinterpret_cast<const float4*>(act.bias + col);
     }
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -347,7 +351,8 @@ __global__ void __launch_bounds__(512) conv_bf16_8ph_kernel(ConvSetB set, EpActB
           }
       }
       float nz = 0.f;
-      if (act.on && act.noise) nz = nwv * act.noise[pix];
+      if constexpr (!MASK)
+        if (act.on && act.noise) nz = nwv * act.noise[pix];
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
 #pragma unroll
@@ -356,7 +361,9 @@ __global__ void __launch_bounds__(512) conv_bf16_8ph_kernel(ConvSetB set, EpActB
           if (col >= N) continue;
           f32x4v a = acc[i][j][r][c];
           if (ep.colscale) a[0] *= csv[j][c].x, a[1] *= csv[j][c].y, a[2] *= csv[j][c].z, a[3] *= csv[j][c].w;
-          if (act.on) {
+          if constexpr (MASK) {  // 8-byte load of the activated map beside the 8-byte store
+            ep_mask4(*reinterpret_cast<const uint2*>(act.a + off + col), a);
+          } else if (act.on) {
             const float bb[4] = {bsv[j][c].x, bsv[j][c].y, bsv[j][c].z, bsv[j][c].w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {

@@ -246,15 +246,23 @@ __global__ void __launch_bounds__(256) thin_in_wgrad_kernel(TiWgradArgs a) {
 constexpr int DG_BH = 8;                 // rows of a band
 constexpr int DG_ROW = 4096 + 2 * 64;    // floats of a ring slot: (4 * 256 / K4 + 2) pixels x K channels = 4096 + 2 K
 
+// four consecutive dy channels as fp32: a 16-byte load of the fp32 map, or an 8-byte load of the bf16 map widened (exact)
+__device__ __forceinline__ float4 ti_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ float4 ti_ld4(const uint16_t* p) {
+  const uint2 v = *reinterpret_cast<const uint2*>(p);
+  return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
+}
+
+template <typename DT = float>  // element type of dy: float, or uint16_t = bf16 bits (fmi_conv2d_thin_input_dgrad_bf16); the ring, the FMAs and dx are fp32
 struct TiDgradArgs {
-  const float* dy;  // [N,H,W,K]
+  const DT* dy;     // [N,H,W,K]
   const float* wt;  // wt[TAPS][K][C]
   float* dx;        // [N,H,W,C]
   int H, W, K, kbits, segs, bands;
 };
 
-template <int C>
-__global__ void __launch_bounds__(256) thin_in_dgrad_kernel(TiDgradArgs a) {
+template <int C, typename DT = float>
+__global__ void __launch_bounds__(256) thin_in_dgrad_kernel(TiDgradArgs<DT> a) {
   __shared__ __attribute__((aligned(16))) float ring[3][DG_ROW];
   const int tid = threadIdx.x;
   const int K4 = 1 << a.kbits, k4 = tid & (K4 - 1), rn = tid >> a.kbits, segw = TI_RUN * (256 >> a.kbits);
@@ -268,12 +276,12 @@ __global__ void __launch_bounds__(256) thin_in_dgrad_kernel(TiDgradArgs a) {
   // the chunks `tid + 256 l` of image row r (pixels x0 - 1 ..): zeros outside the image
   auto stage = [&](int r, float4 (&st)[NL]) {
     const bool rok = (unsigned)r < (unsigned)a.H;
-    const float* rowp = a.dy + (int64_t)(n * a.H + (rok ? r : 0)) * a.W * a.K;
+    const DT* rowp = a.dy + (int64_t)(n * a.H + (rok ? r : 0)) * a.W * a.K;
 #pragma unroll
     for (int l = 0; l < NL; ++l) {
       const int idx = tid + 256 * l, gx = x0 - 1 + (idx >> a.kbits);
       const bool ok = rok && idx < nv && (unsigned)gx < (unsigned)a.W;
-      const float4 v = *reinterpret_cast<const float4*>(rowp + (int64_t)(ok ? gx : 0) * a.K + 4 * (idx & (K4 - 1)));
+      const float4 v = ti_ld4(rowp + (int64_t)(ok ? gx : 0) * a.K + 4 * (idx & (K4 - 1)));
       st[l] = make_float4(ti_keep(v.x, ok), ti_keep(v.y, ok), ti_keep(v.z, ok), ti_keep(v.w, ok));
     }
   };
@@ -363,8 +371,8 @@ __global__ void __launch_bounds__(256) thin_in_dgrad_kernel(TiDgradArgs a) {
 }
 
 // 1x1: no halo, every lane reads its own 16 bytes of dy; pixels are taken flat (N H W), a run = 4 consecutive ones
-template <int C>
-__global__ void __launch_bounds__(256) thin_in_dgrad_k1_kernel(TiDgradArgs a, int64_t npix) {
+template <int C, typename DT = float>
+__global__ void __launch_bounds__(256) thin_in_dgrad_k1_kernel(TiDgradArgs<DT> a, int64_t npix) {
   const int tid = threadIdx.x;
   const int K4 = 1 << a.kbits, k4 = tid & (K4 - 1), rn = tid >> a.kbits, rpb = 256 >> a.kbits;
   ti_f2 wr[C][2];
@@ -380,7 +388,7 @@ __global__ void __launch_bounds__(256) thin_in_dgrad_k1_kernel(TiDgradArgs a, in
     for (int j = 0; j < TI_RUN; ++j) {
       const int64_t p = run * TI_RUN + j;
       const bool live = p < npix;
-      const float4 g = *reinterpret_cast<const float4*>(a.dy + (live ? p : npix - 1) * a.K + 4 * k4);
+      const float4 g = ti_ld4(a.dy + (live ? p : npix - 1) * a.K + 4 * k4);
       const ti_f2 g0 = ti_f2{ti_keep(g.x, live), ti_keep(g.y, live)}, g1 = ti_f2{ti_keep(g.z, live), ti_keep(g.w, live)};
 #pragma unroll
       for (int c = 0; c < C; ++c) {
@@ -503,6 +511,33 @@ extern "C" int fmi_conv2d_thin_in_wgrad_f32(const fmi_conv_desc* d, const float*
   return fmi_launch_status();
 }
 
+// The streaming input gradient of a shape the caller has checked (ti_ok, K/4 a power of two, alignment): 1x1 flat over the pixels, 3x3 by
+// bands and segments.
+template <typename DT>
+static int ti_dgrad_launch(const fmi_conv_desc* d, const DT* dy, const float* wt, float* dx, hipStream_t st) {
+  const int kbits = ti_pow2_bits(d->K / 4), segw = TI_RUN * (256 >> kbits);
+  TiDgradArgs<DT> a{dy, wt, dx, d->H, d->W, d->K, kbits, (d->W + segw - 1) / segw, (d->H + DG_BH - 1) / DG_BH};
+  if (ti_taps(d) == 1) {
+    const int64_t npix = (int64_t)d->N * d->H * d->W;
+    const int grid = fmi_bw_grid(((npix + TI_RUN - 1) / TI_RUN) << kbits, 256);
+    switch (d->C) {
+      case 1: hipLaunchKernelGGL((thin_in_dgrad_k1_kernel<1, DT>), dim3(grid), dim3(256), 0, st, a, npix); break;
+      case 2: hipLaunchKernelGGL((thin_in_dgrad_k1_kernel<2, DT>), dim3(grid), dim3(256), 0, st, a, npix); break;
+      case 3: hipLaunchKernelGGL((thin_in_dgrad_k1_kernel<3, DT>), dim3(grid), dim3(256), 0, st, a, npix); break;
+      default: hipLaunchKernelGGL((thin_in_dgrad_k1_kernel<4, DT>), dim3(grid), dim3(256), 0, st, a, npix); break;
+    }
+    return fmi_launch_status();
+  }
+  const int64_t tasks = (int64_t)d->N * a.bands * a.segs;  // < 2^31: fewer than pixels
+  switch (d->C) {
+    case 1: hipLaunchKernelGGL((thin_in_dgrad_kernel<1, DT>), dim3((unsigned)tasks), dim3(256), 0, st, a); break;
+    case 2: hipLaunchKernelGGL((thin_in_dgrad_kernel<2, DT>), dim3((unsigned)tasks), dim3(256), 0, st, a); break;
+    case 3: hipLaunchKernelGGL((thin_in_dgrad_kernel<3, DT>), dim3((unsigned)tasks), dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL((thin_in_dgrad_kernel<4, DT>), dim3((unsigned)tasks), dim3(256), 0, st, a); break;
+  }
+  return fmi_launch_status();
+}
+
 // The streaming form of fmi_conv2d_thin_input_dgrad_f32 (thinconv.hip calls it first): FMI_ERR_UNSUPPORTED for what it leaves to the
 // kernels there -- 3x3 maps below TI_MIN_PIXELS among them; the 1x1 form has no other kernel behind that entry and is taken at any
 // size.  dy rows 16-byte aligned, dx 4-byte aligned, K/4 a power of two.
@@ -510,28 +545,20 @@ int fmi_thin_in_dgrad_try(const fmi_conv_desc* d, const float* dy, const float* 
   const int k4 = d->K / 4;
   if (!ti_ok(d) || (k4 & (k4 - 1)) || !fmi_al16(dy) || (((uintptr_t)wt | (uintptr_t)dx) & 3)) return FMI_ERR_UNSUPPORTED;
   if (ti_taps(d) == 9 && !ti_routed(d)) return FMI_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  const int kbits = ti_pow2_bits(k4), segw = TI_RUN * (256 >> kbits);
-  TiDgradArgs a{dy, wt, dx, d->H, d->W, d->K, kbits, (d->W + segw - 1) / segw, (d->H + DG_BH - 1) / DG_BH};
-  if (ti_taps(d) == 1) {
-    const int64_t npix = (int64_t)d->N * d->H * d->W;
-    const int grid = fmi_bw_grid(((npix + TI_RUN - 1) / TI_RUN) << kbits, 256);
-    switch (d->C) {
-      case 1: hipLaunchKernelGGL(thin_in_dgrad_k1_kernel<1>, dim3(grid), dim3(256), 0, st, a, npix); break;
-      case 2: hipLaunchKernelGGL(thin_in_dgrad_k1_kernel<2>, dim3(grid), dim3(256), 0, st, a, npix); break;
-      case 3: hipLaunchKernelGGL(thin_in_dgrad_k1_kernel<3>, dim3(grid), dim3(256), 0, st, a, npix); break;
-      default: hipLaunchKernelGGL(thin_in_dgrad_k1_kernel<4>, dim3(grid), dim3(256), 0, st, a, npix); break;
-    }
-    return fmi_launch_status();
-  }
-  const int64_t tasks = (int64_t)d->N * a.bands * a.segs;  // < 2^31: fewer than pixels
-  switch (d->C) {
-    case 1: hipLaunchKernelGGL(thin_in_dgrad_kernel<1>, dim3((unsigned)tasks), dim3(256), 0, st, a); break;
-    case 2: hipLaunchKernelGGL(thin_in_dgrad_kernel<2>, dim3((unsigned)tasks), dim3(256), 0, st, a); break;
-    case 3: hipLaunchKernelGGL(thin_in_dgrad_kernel<3>, dim3((unsigned)tasks), dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL(thin_in_dgrad_kernel<4>, dim3((unsigned)tasks), dim3(256), 0, st, a); break;
-  }
-  return fmi_launch_status();
+  return ti_dgrad_launch<float>(d, dy, wt, dx, (hipStream_t)stream);
+}
+
+/* The same adjoint reading a bf16 gradient (VGG16's first layer behind the bf16 trunk of VGGLoss, modules/loss.py:33-52 of the reference):
+ * dy16 [N,H,W,K] bf16 is widened as it is staged, the FMAs and dx [N,H,W,C<=4] are fp32.  The whole class of the streaming kernels
+ * (fmi_conv2d_thin_in_supported with K/4 a power of two), at ANY map size: there is no other bf16-reading kernel behind it. */
+extern "C" int fmi_conv2d_thin_input_dgrad_bf16(const fmi_conv_desc* d, const uint16_t* dy16, const float* wt, float* dx, void* stream) {
+  if (!d || !dy16 || !wt || !dx) return FMI_ERR_BAD_ARG;
+  if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->kh <= 0 || d->kw <= 0 || d->stride <= 0 || d->pad < 0 ||
+      d->OH != (d->H + 2 * d->pad - d->kh) / d->stride + 1 || d->OW != (d->W + 2 * d->pad - d->kw) / d->stride + 1)
+    return FMI_ERR_BAD_ARG;
+  const int k4 = d->K / 4;
+  if (!ti_ok(d) || (k4 & (k4 - 1)) || !fmi_al16(dy16) || (((uintptr_t)wt | (uintptr_t)dx) & 3)) return FMI_ERR_UNSUPPORTED;
+  return ti_dgrad_launch<uint16_t>(d, dy16, wt, dx, (hipStream_t)stream);
 }
 
 #endif  // FMI_HOST_EMU

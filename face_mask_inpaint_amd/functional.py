@@ -1838,6 +1838,144 @@ def fpn_merge_in_bf16(lateral, coarse):
     return p16
 
 
+# ---- bf16 VGG16 trunk of VGGLoss (VGGLoss(feature_dtype=torch.bfloat16)): TRAINABLE THROUGH -- the frozen convolutions between the fp32
+# image and the four fp32 taps the loss kernels read, forward and input-gradient chain on bf16 maps.  The parameters stay fp32; the bf16
+# packs are cut once per prepared weight (vgg_trunk_packs). ----
+def _vgg_fwd_entry(c, k):
+    """which one-launch conv + bias + ReLU entry a trunk layer C -> K takes: "act" = fmi_conv2d_fwd_act_bf16 (the eight-phase kernel),
+    "chan" = fmi_conv2d_fwd_chan_bf16 (the 128-row tiles).  Measured per layer shape at 24 x 224 x 224 (profiles/vgg_bf16.txt): the
+    64-column layer leaves half of the eight-phase kernel's 128-column tile masked off and is faster on the 128 x 64 tile.  This is the
+    FORWARD's choice only: the adjoints go through fmi_conv2d_dgrad_bf16's own dispatch, which never takes the eight-phase kernel for 64
+    output columns (conv1_2's adjoint runs on the 128 x 64 tile of conv_bf16_kernel)."""
+    return "chan" if k <= 64 else "act"
+
+
+def vgg_trunk_check_widths(shapes):
+    """shapes: (C, K, kh, kw) per convolution.  Refuses, naming the layer, what the bf16 kernels of the trunk do not take (host only)"""
+    for i, (c, k, kh, kw) in enumerate(shapes):
+        if (kh, kw) != (3, 3) or k % 64 or (c % 64 if i else c > 4):
+            raise FmiError(f"the bf16 VGG trunk needs 3 x 3 convolutions whose widths are multiples of 64 (width_div = 1): convolution {i} "
+                           f"is {c} -> {k} k{kh}x{kw}")
+
+
+def vgg_trunk_packs(pws: Sequence[PackedWeight], biases) -> list:
+    """per convolution of the trunk (wf, wt, wnk, wck, bias, zero slope): the fp32 packs of the first layer's thin-input kernels, the bf16
+    forward [K][9][C] and adjoint [C][9][K] packs of the others, cut here once"""
+    vgg_trunk_check_widths([(pw.C, pw.rows, pw.kh, pw.kw) for pw in pws])
+    out = []
+    for i, (pw, b) in enumerate(zip(pws, biases)):
+        _chk(b)
+        first = i == 0
+        out.append((pw.wf, pw.wt, None if first else _pack_bf16(pw.wf), None if first else _pack_bf16(pw.wt), b,
+                    None if first else _slope_vec(b.device, pw.rows, 0.0)))
+    return out
+
+
+def vgg_trunk_check_extent(h, w):
+    """refuses a VGG input the bf16 trunk does not take (three 2 x 2 pools of whole windows); host only"""
+    if h % 8 or w % 8:
+        raise FmiError(f"the bf16 VGG trunk needs H and W of its input to be multiples of 8, got {h} x {w}")
+
+
+def _vgg_trunk_fwd(x, packs, blocks):
+    """(the four fp32 taps, the bf16 activated map of every convolution)"""
+    lib = _L()
+    acts, taps, li, hmap = [], [], 0, x
+    for bi, nconv in enumerate(blocks):
+        for _ in range(nconv):
+            wf, _wt, wnk, _wck, bias, zslope = packs[li]
+            n, h, w, c = hmap.shape
+            k = wf.shape[2]
+            if li == 0:
+                d, a, prof = _conv_fwd_bf16_pre(hmap, k, 3, 3, 1, 1, " thin-in +relu")
+                with prof:
+                    lib.conv2d_thin_in_fwd_bf16(C.byref(d), _p(hmap), _p(wf), _p(bias), 0.0, _p(a), _st())
+            elif _vgg_fwd_entry(c, k) == "chan":
+                a = conv2d_chan_bf16(hmap, wnk, 3, 3, 1, 1, bias=bias, slope=zslope)
+            else:
+                d, a, prof = _conv_fwd_bf16_pre(hmap, k, 3, 3, 1, 1, " +relu")
+                with prof:
+                    lib.conv2d_fwd_act_bf16(C.byref(d), _p(hmap), _p(wnk), None, None, None, _p(bias), 0.0, 1.0, _p(a), _st())
+            acts.append(a)
+            hmap = a
+            li += 1
+        n, h, w, c = hmap.shape
+        tap = torch.empty((n, h, w, c), device=x.device, dtype=torch.float32)
+        pooled = torch.empty((n, h // 2, w // 2, c), device=x.device, dtype=BF16) if bi + 1 < len(blocks) else None
+        with _prof(f"vgg_tap_fwd_bf16|{n}x{h}x{w}x{c}" + ("" if pooled is None else " +pool"), 0.0):
+            lib.vgg_tap_fwd_bf16(_p(hmap), _p(tap), _p(pooled), n, h, w, c, _st())
+        taps.append(tap)
+        hmap = pooled
+    return taps, acts
+
+
+class _VggTrunkBF16(torch.autograd.Function):
+    """x fp32 [N, H, W, 3] (resized, normalised) -> the four fp32 taps.  Keeps the ten bf16 activated maps; the backward is four tap passes,
+    six masked adjoints, three plain adjoints and the thin-input adjoint, which returns the fp32 image gradient.  A tap nobody used
+    arrives without a gradient: the blocks behind the last tap that has one are skipped whole (no gradient reaches them); a block in
+    front of it still runs -- the gradient of the pooled map passes through it -- with zeros for its own tap."""
+
+    @staticmethod
+    def forward(ctx, x, packs, blocks):
+        taps, acts = _vgg_trunk_fwd(x, packs, blocks)
+        ctx.save_for_backward(*acts)
+        ctx.packs, ctx.blocks = packs, blocks
+        ctx.set_materialize_grads(False)  # an unused tap arrives as None, not as a freshly zero-filled tensor
+        return tuple(taps)
+
+    @staticmethod
+    def backward(ctx, *gtaps):
+        lib = _L()
+        acts, packs, blocks = ctx.saved_tensors, ctx.packs, ctx.blocks
+        first = [sum(blocks[:bi]) for bi in range(len(blocks))]  # index of each block's first convolution
+        gpool = None
+        for bi in reversed(range(len(blocks))):
+            last = first[bi] + blocks[bi] - 1
+            a = acts[last]
+            n, h, w, k = a.shape
+            if gtaps[bi] is None and gpool is None:
+                continue
+            gt = torch.zeros((n, h, w, k), device=a.device, dtype=torch.float32) if gtaps[bi] is None else gtaps[bi].contiguous()
+            _chk(gt)
+            dy = torch.empty_like(a)
+            with _prof(f"vgg_tap_bwd_bf16|{n}x{h}x{w}x{k}" + ("" if gpool is None else " +unpool"), 0.0):
+                lib.vgg_tap_bwd_bf16(_p(a), _p(gt), _p(gpool), _p(dy), n, h, w, k, _st())
+            for li in range(last, first[bi] - 1, -1):
+                _wf, wt, _wnk, wck, _bias, _z = packs[li]
+                k, c = wt.shape[1], wt.shape[2]
+                d, _, _ = conv_desc(n, h, w, c, k, 3, 3, 1, 1)
+                flops = 2.0 * dy.numel() * c * 9
+                if li == 0:  # conv1_1: the bf16 gradient in, the fp32 image gradient out
+                    gx = torch.empty((n, h, w, c), device=dy.device, dtype=torch.float32)
+                    with _prof(f"conv_dgrad_bf16|{n}x{h}x{w} {c}->{k} k3s1 thin-in", flops):
+                        lib.conv2d_thin_input_dgrad_bf16(C.byref(d), _p(dy), _p(wt), _p(gx), _st())
+                    return gx, None, None
+                dx = torch.empty((n, h, w, c), device=dy.device, dtype=BF16)
+                if li > first[bi]:  # its input is the previous convolution's ReLU output: that mask in the output stage
+                    with _prof(f"conv_dgrad_bf16|{n}x{h}x{w} {c}->{k} k3s1 +mask", flops):
+                        lib.conv2d_dgrad_relu_bf16(C.byref(d), _p(dy), _p(wck), _p(acts[li - 1]), _p(dx), _st())
+                else:  # its input is a pooled map: the plain adjoint, unsplit (no atomics)
+                    with _prof(f"conv_dgrad_bf16|{n}x{h}x{w} {c}->{k} k3s1", flops):
+                        lib.conv2d_dgrad_bf16(C.byref(d), _p(dy), _p(wck), None, _p(dx), None, 0, _st())
+                dy = dx
+            gpool = dy
+        return None, None, None  # no tap carried a gradient
+
+
+def vgg_trunk_bf16(x, packs, blocks=(2, 2, 3, 3)):
+    """the four fp32 taps [N, H/2^i, W/2^i, C_i] of the bf16 VGG16 trunk on the fp32 NHWC image x; ``packs`` from vgg_trunk_packs, ``blocks``
+    the number of convolutions per block.  Differentiable in x; under no_grad nothing is kept."""
+    if x.dim() != 4 or x.shape[3] > 4:
+        raise FmiError(f"the bf16 VGG trunk takes an NHWC image with at most 4 channels, got {tuple(x.shape)}")
+    vgg_trunk_check_extent(x.shape[1], x.shape[2])  # before any device call
+    _chk(x)
+    if len(packs) != sum(blocks):
+        raise FmiError(f"the bf16 VGG trunk has {sum(blocks)} convolutions, got {len(packs)} packs")
+    if torch.is_grad_enabled() and x.requires_grad:
+        return list(_VggTrunkBF16.apply(x, packs, tuple(blocks)))
+    return _vgg_trunk_fwd(x, packs, tuple(blocks))[0]
+
+
 class _Resize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, oh, ow, mean, std):

@@ -6,6 +6,8 @@ FF.seg_ce_dice_loss, its validation metric FF.seg_dice_score.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 from torch import nn
 
@@ -15,6 +17,18 @@ from .pluralistic_model import base_function
 from .pluralistic_model.external_function import GANLoss, run_conv
 
 VGG_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M"]  # vgg16.features[:23] has no 5th stage
+
+
+VGG_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
+
+
+def vgg_dtype_from_env():
+    """FMI_VGG_DTYPE={fp32,bf16} (default fp32): the dtype of VGGLoss's feature trunk where it is built without the argument -- how pSpLoss,
+    a trainer whose flags are the reference's, or a fixed benchmark selects the bf16 trunk"""
+    name = os.environ.get("FMI_VGG_DTYPE", "fp32")
+    if name not in VGG_DTYPES:
+        raise FF.FmiError(f"FMI_VGG_DTYPE must be one of {sorted(VGG_DTYPES)}, got {name!r}")
+    return VGG_DTYPES[name]
 
 
 def _vgg16_features(width_div: int = 1) -> nn.Sequential:
@@ -31,8 +45,17 @@ def _vgg16_features(width_div: int = 1) -> nn.Sequential:
 
 
 class VGGLoss(torch.nn.Module):
-    def __init__(self, width_div: int = 1):
+    def __init__(self, width_div: int = 1, feature_dtype=None):
+        """feature_dtype=torch.bfloat16 (this build's extra, TRAINABLE THROUGH): the trunk between the image and the four tapped feature
+        maps on the bf16 kernels, forward and input-gradient chain (FF.vgg_trunk_bf16); the parameters, the taps the loss kernels read and
+        the image gradient stay fp32.  Needs width_div = 1 and an input whose H and W are multiples of 8.  None (the default) reads
+        FMI_VGG_DTYPE, which defaults to fp32."""
         super().__init__()
+        if feature_dtype is None:
+            feature_dtype = vgg_dtype_from_env()
+        if feature_dtype not in (torch.float32, torch.bfloat16):
+            raise FF.FmiError(f"feature_dtype must be torch.float32 or torch.bfloat16, got {feature_dtype}")
+        self.feature_dtype = feature_dtype
         try:  # the reference's source of weights (loss.py:21)
             import torchvision  # type: ignore
 
@@ -44,6 +67,8 @@ class VGGLoss(torch.nn.Module):
             for p in bl.parameters():
                 p.requires_grad = False
         self.blocks = torch.nn.ModuleList(blocks)
+        if feature_dtype == torch.bfloat16:
+            FF.vgg_trunk_check_widths([(m.in_channels, m.out_channels) + tuple(m.kernel_size) for bl in blocks for m in bl if isinstance(m, nn.Conv2d)])
         self.register_buffer("mean", torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1))
         self.register_buffer("std", torch.tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1))
         self._cache = {}
@@ -55,7 +80,9 @@ class VGGLoss(torch.nn.Module):
         if self._cache.get("key") != key:
             with torch.no_grad():
                 pws = FF.prepare_weights([(c.weight, None, None) for c in convs])
-            self._cache = {"key": key, "pws": pws}
+                # the bf16 trunk's packs live and die with the fp32 packs they are cut from: no pack launch per call
+                packs16 = FF.vgg_trunk_packs(pws, [c.bias for c in convs]) if self.feature_dtype == torch.bfloat16 else None
+            self._cache = {"key": key, "pws": pws, "packs16": packs16}
         for c, pw in zip(convs, self._cache["pws"]):
             object.__setattr__(c, "_fmi_packed", pw)
 
@@ -74,22 +101,46 @@ class VGGLoss(torch.nn.Module):
                 prev_conv = True
         return x
 
+    def _taps16(self, x, y):
+        """the bf16 trunk: (taps of x with gradient, taps of y without), four fp32 NHWC maps each, or (None, None) for the fp32 trunk"""
+        if self.feature_dtype != torch.bfloat16:
+            return None, None
+        blocks = tuple(sum(isinstance(m, nn.Conv2d) for m in bl) for bl in self.blocks)
+        xt = FF.vgg_trunk_bf16(x, self._cache["packs16"], blocks)
+        with torch.no_grad():
+            yt = FF.vgg_trunk_bf16(y, self._cache["packs16"], blocks)
+        return xt, yt
+
+    @staticmethod
+    def _input_extent(h, w):
+        return (224, 224) if w > 224 else (h, w)  # loss.py:48-49 "Filter HQ"
+
+    def _check16(self, h, w):
+        """the bf16 trunk's refusal of a VGG input extent, before any device call of the forward that asks"""
+        if self.feature_dtype == torch.bfloat16:
+            FF.vgg_trunk_check_extent(h, w)
+
     def _input(self, img):
         x = FF.to_nhwc(img)
         n, h, w, c = x.shape
-        oh, ow = (224, 224) if w > 224 else (h, w)  # loss.py:48-49 "Filter HQ"
+        oh, ow = self._input_extent(h, w)
         return FF.resize_bilinear(x, oh, ow, self.mean.view(3).contiguous(), self.std.view(3).contiguous())
 
     def forward(self, input, target, lossType="perceptual"):
+        self._check16(*self._input_extent(input.shape[2], input.shape[3]))
         self._prepare()
         x = self._input(input)
         with torch.no_grad():
             y = self._input(target)
         loss = 0.0
+        xt, yt = self._taps16(x, y)
         for i in range(len(self.blocks)):
-            x = self._block(i, x)
-            with torch.no_grad():
-                y = self._block(i, y)
+            if xt is not None:
+                x, y = xt[i], yt[i]
+            else:
+                x = self._block(i, x)
+                with torch.no_grad():
+                    y = self._block(i, y)
             n, h, w, c = x.shape
             dim = c * h * w
             if lossType == "perceptual":
@@ -108,6 +159,8 @@ class VGGLoss(torch.nn.Module):
         inputs share ONE VGG pass with gradient (batch k*N) and the targets ONE pass without (the three losses of
         GANOptimizer are 6 VGG passes of batch N in the reference, loss.py:84-95): larger GEMM M fills the GPU at the
         28x28 / 56x56 layers, and the launch count drops 3x."""
+        for t in triples:
+            self._check16(*self._input_extent(t[0].shape[2], t[0].shape[3]))
         x = torch.cat([self._input(t[0]) for t in triples], 0)
         with torch.no_grad():
             y = torch.cat([self._input(t[1]) for t in triples], 0)
@@ -116,14 +169,19 @@ class VGGLoss(torch.nn.Module):
     def forward_multi_prepared(self, x, y, loss_types):
         """``forward_multi`` from its block loop onward: x, y [k*N, H, W, 3] NHWC are the resized and normalised operands of the k
         losses stacked along the batch (what ``forward_multi`` builds, or FF.gan_image_head in one pass); y carries no gradient"""
+        self._check16(x.shape[1], x.shape[2])
         self._prepare()
         k = len(loss_types)
         n = x.shape[0] // k
         losses = [0.0] * k
+        xt, yt = self._taps16(x, y)
         for i in range(len(self.blocks)):
-            x = self._block(i, x)
-            with torch.no_grad():
-                y = self._block(i, y)
+            if xt is not None:
+                x, y = xt[i], yt[i]
+            else:
+                x = self._block(i, x)
+                with torch.no_grad():
+                    y = self._block(i, y)
             _, h, w, c = x.shape
             dim = c * h * w
             xparts, yparts = x.split(n, 0), y.split(n, 0)  # contiguous batch slices; the backward of split is one cat
@@ -144,10 +202,10 @@ class GANOptimizer(nn.Module):
     """loss.py:68-144.  ``__call__`` performs the generator step then the discriminator step and returns
     (D_loss, G_loss, perc_loss, style_loss, cx_loss) exactly like the reference."""
 
-    def __init__(self, optimizer_D, optimizer_G, lambda_g=0.01, debug=False, vgg_width_div: int = 1):
+    def __init__(self, optimizer_D, optimizer_G, lambda_g=0.01, debug=False, vgg_width_div: int = 1, vgg_dtype=None):
         super().__init__()
         self.gan_loss = GANLoss("lsgan")
-        self.vgg_loss = VGGLoss(vgg_width_div)
+        self.vgg_loss = VGGLoss(vgg_width_div, feature_dtype=vgg_dtype)  # vgg_dtype None: FMI_VGG_DTYPE (VGGLoss)
         self.debug = debug
         self.optimizer_D = optimizer_D
         self.optimizer_G = optimizer_G

@@ -52,6 +52,10 @@ int fmi_get_deterministic(void);
  * 1 = never the eight-wave tiles, 2 = no eight-phase kernel, 8 = the eight-phase kernel (csrc/conv_bf16_8ph.h) wherever it is legal.
  * mode < 0 only queries.  Returns the previous mode. */
 int fmi_debug_bf16_tile(int mode);
+/* The tile the last launch of the bf16 forward / adjoint dispatch took (tests assert which kernel a shape reached): 1000 BM + BN of the
+ * tile (rows x output columns), plus 1000000 for the eight-phase kernel; 0 before the first launch.  fmi_conv2d_fwd_chan_bf16 and the
+ * grouped entry choose their tiles themselves and do not set it. */
+int fmi_debug_bf16_last_tile(void);
 
 /* ------------------------------------------------------------------------
  * Dense batched GEMM on the fp32 matrix cores (v_mfma_f32_32x32x2_f32).
@@ -992,6 +996,33 @@ int fmi_fpn_merge_in_bf16(const uint16_t* lateral, const uint16_t* coarse, uint1
  * r, c [rows][C] and fp32 m [rows].  m == 1 returns r and m == 0 returns c bit for bit.  C % 8 == 0, r / c / y 16-byte aligned (else
  * FMI_ERR_UNSUPPORTED); a NULL pointer or a non-positive extent: FMI_ERR_BAD_ARG. */
 int fmi_mask_blend_bf16(const uint16_t* r, const uint16_t* c, const float* m, uint16_t* y, int64_t rows, int C, void* stream);
+
+/* ------------------------------------------------------------------------
+ * bf16 VGG16 trunk of VGGLoss for training (VGGLoss(feature_dtype=torch.bfloat16) / FMI_VGG_DTYPE=bf16): the frozen convolutions between
+ * the image and the four feature maps the losses read, forward and input-gradient chain.  Replaces modules/loss.py:16-65 of the reference
+ * (the four blocks of vgg16.features[:23] and the loop that taps them); the loss terms themselves stay the fp32 kernels.  The forward
+ * convolutions are fmi_conv2d_thin_in_fwd_bf16 (conv1_1) and fmi_conv2d_fwd_act_bf16 (bias + ReLU in the output stage).  fp32 parameters
+ * and accumulation, one round-to-nearest-even per stored bf16 value, no split reductions and no atomics: every result is bit-reproducible
+ * in either mode of fmi_set_deterministic.  Every entry refuses bad arguments (FMI_ERR_BAD_ARG: NULL pointers, non-positive extents, a
+ * descriptor whose OH / OW do not follow from it) and unsupported shapes or misaligned pointers (FMI_ERR_UNSUPPORTED) before any HIP call.
+ * ---------------------------------------------------------------------- */
+/* the adjoint of a convolution whose input is another convolution's ReLU output (loss.py:33-52: conv1_2, 2_2, 3_2, 3_3, 4_2, 4_3):
+ * dx = bf16(a_in > 0 ? adjoint(dy) : 0) -- fmi_conv2d_dgrad_bf16 with that ReLU's mask in the output stage.  dy bf16 [N,OH,OW,K], wck bf16
+ * [C][9][K] (fmi_pack_weight_bf16), a_in and dx bf16 [N,H,W,x_cstride].  3x3 pad 1 stride 1, C % 64 == 0, K % 64 == 0, x_cstride % 4 == 0,
+ * y_cstride % 8 == 0, 16-byte aligned pointers.  The tile is the one fmi_conv2d_dgrad_bf16 takes for the shape (fmi_debug_bf16_tile
+ * applies), never the split reduction; with a_in > 0 everywhere the result is that entry's, bit for bit. */
+int fmi_conv2d_dgrad_relu_bf16(const fmi_conv_desc* d, const uint16_t* dy, const uint16_t* wck, const uint16_t* a_in, uint16_t* dx, void* stream);
+/* the point where the losses tap a block's activated map a bf16 [N,H,W,C] (loss.py:54-65), one pass over a: tap fp32 [N,H,W,C] = float(a)
+ * (exact) and, pooled not NULL, pooled bf16 [N,H/2,W/2,C] = the 2x2 max pool that opens the next block, with fmi_maxpool2_bf16's winner
+ * rule (first maximum in row-major order, a NaN wins).  C % 8 == 0, 16-byte aligned pointers, H and W even with pooled. */
+int fmi_vgg_tap_fwd_bf16(const uint16_t* a, float* tap, uint16_t* pooled, int N, int H, int W, int C, void* stream);
+/* its backward with the block's last ReLU: dy = bf16(a > 0 ? gtap + unpool(gpool) : 0), the sum in fp32 and one rounding; gtap fp32
+ * [N,H,W,C], gpool bf16 [N,H/2,W/2,C] or NULL (block 4), routed to each window's winner by the forward's rule.  Same conditions. */
+int fmi_vgg_tap_bwd_bf16(const uint16_t* a, const float* gtap, const uint16_t* gpool, uint16_t* dy, int N, int H, int W, int C, void* stream);
+/* fmi_conv2d_thin_input_dgrad_f32 reading a bf16 gradient (conv1_1's adjoint, loss.py:33-52 towards the generated image): dy16 bf16
+ * [N,H,W,K], wt fp32 [taps][K][C], dx fp32 [N,H,W,C <= 4]; fp32 FMAs.  The class fmi_conv2d_thin_in_supported accepts with K/4 a power of
+ * two, at any map size (the streaming kernel of csrc/thinin.hip); dy16 16-byte aligned. */
+int fmi_conv2d_thin_input_dgrad_bf16(const fmi_conv_desc* d, const uint16_t* dy16, const float* wt, float* dx, void* stream);
 
 #ifdef __cplusplus
 }

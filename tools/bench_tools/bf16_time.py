@@ -1,7 +1,7 @@
 """timing only: bf16 conv forward / adjoint / weight gradient on the decoder's big layers"""
-import ctypes as C, sys, time
+import ctypes as C, os, sys, time
 import torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from face_mask_inpaint_amd import _lib, functional as FF
 lib = _lib.lib()
 dev = torch.device("cuda:0")

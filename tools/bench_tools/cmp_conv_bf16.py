@@ -3,7 +3,8 @@ style_heads_bf16.hip) and the Python forward wrappers that share _conv_fwd_bf16_
 every output must be torch.equal on the raw bits.  The shapes take each branch of the host set-up (the tile table of launch_conv_bf16, the
 grouped table, the adjoint's phases) and each output stage of conv_bf16_kernel.  The weight gradient and the split reduction accumulate
 with atomics outside the reproducible mode: they run in that mode only.  A refusal (FmiError) is reported; where one is expected both
-builds must refuse alike.  Exit status 1 on any difference."""
+builds must refuse alike.  Exit status 1 on any difference.  Either build may lack entries the other has (an older library next to a newer
+one): only the entries the cases call are needed."""
 import ctypes as C
 import os
 import sys
@@ -14,7 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 from face_mask_inpaint_amd import functional as FF, _lib  # noqa: E402
 
 dev = torch.device("cuda:0")
-libs = [_lib.Library(sys.argv[1]), _lib.Library(sys.argv[2])]
+libs = [_lib.Library(sys.argv[1], strict=False), _lib.Library(sys.argv[2], strict=False)]
 gen = torch.Generator().manual_seed(0)
 F32, BF16 = torch.float32, torch.bfloat16
 bad = ran = 0
@@ -182,6 +183,19 @@ case("dgrad stride 2 2x64x64 k3", *dgrad(2, 64, 64, 64, 128, 3, 2, 1))
 case("dgrad 1x1 stride 2 (three tap-less phases write zeros)", *dgrad(2, 16, 16, 64, 128, 1, 2, 0))
 case("dgrad 32-deep tiles 64->96 2x20x20 k3", *dgrad(2, 20, 20, 64, 96, 3, 1, 1))
 case("dgrad split workspace 512->512 8x8 k3", *dgrad(2, 8, 8, 512, 512, 3, 1, 1, split=True), det=True)
+
+
+# the shapes of tests/test_gpu_vgg_bf16.py's masked adjoint (the plain adjoint shares its kernels' inner loop) under every tile mode, and the
+# decoder's large layers (tools/bench_tools/bf16_time.py) on the eight-phase kernel, forward and adjoint
+for g in ((2, 8, 8, 64, 64), (1, 12, 20, 128, 64), (2, 16, 16, 256, 512), (2, 16, 16, 512, 256)):
+    for mode in (0, 2, 8):
+        case(f"dgrad {g} k3", *dgrad(*g, 3, 1, 1), tile=mode)
+        case(f"fwd {g} k3", *fwd(*g, 3, 1, 1), tile=mode)
+for g in ((4, 64, 64, 512, 512), (4, 128, 128, 256, 256), (4, 256, 256, 128, 128)):
+    case(f"dgrad decoder layer {g} k3", *dgrad(*g, 3, 1, 1))
+    case(f"fwd decoder layer {g} k3", *fwd(*g, 3, 1, 1))
+case("fwd_act decoder layer (4, 128, 128, 256, 256) noise + colscale", *act(4, 128, 128, 256, 256, True, 0.2, 2 ** 0.5))
+case("fwd_act decoder layer (4, 256, 256, 128, 128) noise + colscale", *act(4, 256, 256, 128, 128, True, 0.2, 2 ** 0.5))
 
 
 # ---- fmi_conv2d_wgrad_bf16 (reproducible mode: one workgroup per tile walks the whole pixel range) ----
