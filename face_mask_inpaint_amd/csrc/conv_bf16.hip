@@ -18,7 +18,126 @@
 #include <type_traits>
 
 #include "bf16x8.h"
+#include "conv_bf16_plan.h"
 #include "gemm_core.h"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// host side of the dispatch that needs no GPU (also the g++ -DFMI_HOST_EMU build, tests/test_host_conv_bf16_plan.py): descriptor checks,
+// the integer geometry of the phases, the inputs of the plan (conv_bf16_plan.h) and the query fmi_conv2d_bf16_plan
+// ---------------------------------------------------------------------------------------------------------------------------
+// kernel selection override (tests): 0 = by shape, 1 = never the 8-wave tiles, 2 = no eight-phase kernel, 8 = the eight-phase kernel
+// wherever it is legal
+static int g_bf16_tile_mode = 0;
+extern "C" int fmi_debug_bf16_tile(int mode) {
+  const int prev = g_bf16_tile_mode;
+  if (mode >= 0) g_bf16_tile_mode = mode;
+  return prev;
+}
+// the tile of the last launch of conv_bf16_kernel / the eight-phase kernel, whichever entry made it (tests assert which kernel a shape
+// reached): the plan's tile id
+static int g_bf16_last_tile = 0;
+extern "C" int fmi_debug_bf16_last_tile(void) { return g_bf16_last_tile; }
+
+static int check_desc_b(const fmi_conv_desc* d) {
+  if (!d) return FMI_ERR_BAD_ARG;
+  if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->C <= 0 || d->K <= 0 || d->kh <= 0 || d->kw <= 0 || d->stride <= 0 || d->pad < 0 ||
+      d->x_cstride < d->C || d->y_cstride < d->K)
+    return FMI_ERR_BAD_ARG;
+  if (d->dil > 1) return FMI_ERR_UNSUPPORTED;  // dilated convolutions (modules/drn.py) exist in the fp32 family only
+  if (d->OH != (d->H + 2 * d->pad - d->kh) / d->stride + 1 || d->OW != (d->W + 2 * d->pad - d->kw) / d->stride + 1) return FMI_ERR_BAD_ARG;
+  if (d->OH <= 0 || d->OW <= 0) return FMI_ERR_BAD_ARG;
+  if (d->pad_mode != 0) return FMI_ERR_UNSUPPORTED;
+  if ((int64_t)d->N * d->H * d->W > 0x7fffffffLL / 2 || (int64_t)d->N * d->OH * d->OW > 0x7fffffffLL / 2 ||
+      (int64_t)d->kh * d->kw * d->C > 0x3fffffffLL || (int64_t)d->kh * d->kw * d->K > 0x3fffffffLL)
+    return FMI_ERR_UNSUPPORTED;
+  return FMI_OK;
+}
+
+extern "C" int fmi_conv2d_bf16_supported(const fmi_conv_desc* d) {
+  if (check_desc_b(d) != FMI_OK) return 0;
+  return d->C % 32 == 0 && d->K % 32 == 0 && d->x_cstride % 8 == 0 && d->y_cstride % 8 == 0;
+}
+
+// The integer part of a launch's phases: one geometry per phase -- the one phase of a forward convolution (pass 0), or the non-empty
+// sub-pixel phases (py, px) of the stride of an adjoint (pass 1: up to four, d->stride <= 2).  conv_set_b puts the pointers around.
+struct ConvPhasesB {
+  int nph;
+  ConvGeom g[4];
+  int py[4], px[4];
+};
+static ConvPhasesB conv_phases_b(const fmi_conv_desc* d, int pass) {
+  ConvPhasesB ph{};
+  if (pass == 0) {
+    ConvGeom& g = ph.g[ph.nph++];
+    g = fwd_geom(d, d->N);               // check_desc_b: no dilation, pad_mode 0.  img_bs stays 0: no per-sample weights in this family
+    g.vec = d->C % 64 == 0 ? 6 : 5;      // here: log2 of the reduction tile BK (the fp32 family keeps a float4 flag in this field)
+    g.dC = make_fastdiv(g.nty * g.ntx);  // here: divides by the number of TAPS (ConvKB::tile; the weight gradients and fp32 divide by C)
+    return ph;
+  }
+  const int s = d->stride;
+  for (int py = 0; py < s; ++py) {
+    for (int px = 0; px < s; ++px) {
+      ConvGeom g = adj_geom(d, d->N, py, px);  // img_bs stays 0: no per-sample weights in this family
+      if (g.GH <= 0 || g.GW <= 0) continue;
+      g.vec = d->K % 64 == 0 ? 6 : 5;                              // here: log2 of the reduction tile
+      g.dC = make_fastdiv(g.nty * g.ntx > 0 ? g.nty * g.ntx : 1);  // here: divides by the number of TAPS (1: the empty phase)
+      ph.py[ph.nph] = py, ph.px[ph.nph] = px;
+      ph.g[ph.nph++] = g;
+    }
+  }
+  return ph;
+}
+// elements of the tensor a pass writes (y of the forward, dx of the adjoint) and whether it takes the 8-byte stores (ConvEpB::vec)
+static int64_t out_elems_b(const fmi_conv_desc* d, int pass) {
+  return pass == 0 ? (int64_t)d->N * d->OH * d->OW * d->y_cstride : (int64_t)d->N * d->H * d->W * d->x_cstride;
+}
+static int out_vec_b(const fmi_conv_desc* d, int pass, bool out_al8) {
+  return ((pass == 0 ? d->K % 4 == 0 && d->y_cstride % 4 == 0 : d->C % 4 == 0 && d->x_cstride % 4 == 0) && out_al8) ? 1 : 0;
+}
+// The plan's inputs of a call.  flags: FMI_PLAN_* (include/fmi_hip.h) -- what the plan reads of the call's pointers, which an entry derives
+// from them and the query is told; without FMI_PLAN_MODES the reproducible mode and the tile mode are the library's current ones.
+static bool plan_det_b(int flags) { return flags & FMI_PLAN_MODES ? (flags & FMI_PLAN_DET) != 0 : fmi_det(); }
+static int plan_tile_mode_b(int flags) { return flags & FMI_PLAN_MODES ? (flags >> 8) & 15 : g_bf16_tile_mode; }
+static ConvPlanInB conv_plan_in_b(const fmi_conv_desc* d, int pass, int stage, int groups, const ConvPhasesB& ph, int flags) {
+  ConvPlanInB in{};
+  in.stage = stage;
+  in.BK = 1 << ph.g[0].vec;
+  in.N = pass == 0 ? d->K : d->C;
+  in.groups = groups;
+  in.nph = ph.nph;
+  for (int p = 0; p < ph.nph; ++p) {
+    in.M[p] = ph.g[p].Mdim(), in.K[p] = ph.g[p].Kdim(), in.taps[p] = ph.g[p].ntaps();
+    in.vec[p] = out_vec_b(d, pass, (flags & FMI_PLAN_OUT_AL8) != 0);
+  }
+  in.colscale = (flags & FMI_PLAN_COLSCALE) != 0, in.colscale_al16 = (flags & FMI_PLAN_COLSCALE_AL16) != 0;
+  in.split_ws = (flags & FMI_PLAN_SPLIT_WS) && out_elems_b(d, pass) % 4 == 0;
+  in.det = plan_det_b(flags), in.tile_mode = plan_tile_mode_b(flags);
+  return in;
+}
+static WgradPlanInB wgrad_plan_in_b(const fmi_conv_desc* d, int flags) {
+  return WgradPlanInB{d->kh * d->kw * d->C, d->K, d->N * d->OH * d->OW, (int64_t)d->N * d->H * d->W * d->x_cstride, plan_det_b(flags),
+                      plan_tile_mode_b(flags)};
+}
+
+/* The plan of a launch without the launch (include/fmi_hip.h): the entries fill the plan's inputs through the functions above, and so
+ * does this.  The descriptor is checked as every entry checks it first; the further refusals of an entry (channel multiples, pointers)
+ * are the entry's. */
+extern "C" int fmi_conv2d_bf16_plan(const fmi_conv_desc* d, int pass, int stage, int groups, int flags, int* out) {
+  if (!out || pass < 0 || pass > 2 || stage < STAGE_PLAIN_B || stage > STAGE_MASK_B || groups < 1) return FMI_ERR_BAD_ARG;
+  for (int i = 0; i < FMI_CONV_BF16_PLAN_INTS; ++i) out[i] = 0;
+  int rc = check_desc_b(d);
+  if (rc == FMI_OK && pass == 1 && d->stride > 2) rc = FMI_ERR_UNSUPPORTED;  // at most four sub-pixel phases per launch
+  if (rc) return out[0] = rc;
+  ConvPhasesB ph{};
+  ph.nph = 1;
+  if (pass < 2) ph = conv_phases_b(d, pass);
+  const ConvPlanB pl = pass == 2 ? wgrad_plan_b(wgrad_plan_in_b(d, flags)) : conv_plan_b(conv_plan_in_b(d, pass, stage, groups, ph, flags));
+  if (pl.status) return out[0] = pl.status;
+  const int v[FMI_CONV_BF16_PLAN_INTS] = {FMI_OK, pl.tile, pl.ksplit, (int)pl.grid[0], (int)pl.grid[1], (int)pl.grid[2], pl.tiles[0],
+                                          pl.tiles[1], pl.tiles[2], pl.tiles[3], pl.tiles_n, ph.nph, pl.kchunk, pl.xcd_splits};
+  for (int i = 0; i < FMI_CONV_BF16_PLAN_INTS; ++i) out[i] = v[i];
+  return FMI_OK;
+}
 
 #ifndef FMI_HOST_EMU
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -519,169 +638,109 @@ __global__ void __launch_bounds__(256) f32_to_bf16_kernel(const float* __restric
 
 #include "conv_bf16_8ph.h"
 
-// kernel selection override (tests): 0 = by shape, 1 = never the 8-wave tiles, 2 = no eight-phase kernel, 8 = the eight-phase kernel
-// wherever it is legal
-static int g_bf16_tile_mode = 0;
-extern "C" int fmi_debug_bf16_tile(int mode) {
-  const int prev = g_bf16_tile_mode;
-  if (mode >= 0) g_bf16_tile_mode = mode;
-  return prev;
-}
-// the tile launch_conv_bf16 took last (tests assert which kernel a shape reached): 1000 BM + BN, plus 1000000 for the eight-phase kernel
-static int g_bf16_last_tile = 0;
-extern "C" int fmi_debug_bf16_last_tile(void) { return g_bf16_last_tile; }
+// ---------------------------------------------------------------------------------------------------------------------------
+// the launcher of the forward / adjoint entries: conv_bf16_plan.h decides, this launches what it decided
+// ---------------------------------------------------------------------------------------------------------------------------
+template <class T>
+struct Is8P : std::false_type {};
+template <int WM, int WN>
+struct Is8P<Tile8P<WM, WN>> : std::true_type {};
 
-// phases: nph filled entries of set.ph (la, lb, ep, M, K); N = output channels.  ws (may be null): zeroed fp32 twin of the output
-// tensor with out_elems elements -- small feature maps with a deep reduction (the 4^2 .. 16^2 layers: 2 - 32 output tiles) then
-// split the reduction over workgroups and the sums are converted to bf16 by a second launch.
-template <int BK>
-static int launch_conv_bf16(ConvSetB& set, int nph, int N, bf16_t* y, float* ws, int64_t ws_floats, int64_t out_elems, hipStream_t st,
-                            const EpActB* act = nullptr, const EpMaskB* mask = nullptr) {
-  int Mmax = 0, Kmax = 0;
-  for (int p = 0; p < nph; ++p) {
-    if (set.ph[p].M > Mmax) Mmax = set.ph[p].M;
-    if (set.ph[p].K > Kmax) Kmax = set.ph[p].K;
-  }
-  set.N = N;
-  const bool can_split = ws && ws_floats >= out_elems && out_elems % 4 == 0 && !set.ph[0].ep.colscale && !fmi_det();  // reproducible mode: no split
-#define FMI_LAUNCH_B(TILE)                                                                                                        \
-  do {                                                                                                                            \
-    const int64_t tn = ceil_div64(N, TILE::BN);                                                                                   \
-    int64_t tmax = 0, tsum = 0;                                                                                                   \
-    for (int p = 0; p < nph; ++p) {                                                                                               \
-      const int64_t t = ceil_div64(set.ph[p].M, TILE::BM) * tn;                                                                   \
-      if (t > 0x7fffffffLL) return FMI_ERR_UNSUPPORTED;                                                                           \
-      set.ph[p].tiles = (int)t;                                                                                                   \
-      tsum += t;                                                                                                                  \
-      if (t > tmax) tmax = t;                                                                                                     \
-    }                                                                                                                             \
-    int64_t ks = 1;                                                                                                               \
-    if (can_split && tsum < 128 && Kmax >= 1024) {                                                                                \
-      ks = ceil_div64(256, tsum);                                                                                                 \
-      if (ks > Kmax / 256) ks = Kmax / 256;                                                                                       \
-    }                                                                                                                             \
-    set.tiles_n = (int)tn;                                                                                                        \
-    set.ksplit = (int)ks;                                                                                                         \
-    g_bf16_last_tile = TILE::BM * 1000 + TILE::BN;                                                                                \
-    set.ws = ks > 1 ? ws : nullptr;                                                                                               \
-    if (mask) { /* the masked adjoint: 64-deep reduction tiles and at least 64 output columns (ws is null: ks == 1) */           \
-      if constexpr (BK == 64 && TILE::BN >= 64)                                                                                   \
-        hipLaunchKernelGGL((conv_bf16_kernel<TILE, BK, 2, EpMaskB>), dim3((unsigned)tmax, nph, 1), dim3(TILE::NT), 0, st, set, *mask); \
-      else return FMI_ERR_UNSUPPORTED;                                                                                            \
-      break;                                                                                                                      \
-    }                                                                                                                             \
-    hipLaunchKernelGGL((conv_bf16_kernel<TILE, BK>), dim3((unsigned)tmax, nph, (unsigned)ks), dim3(TILE::NT), 0, st, set, EpNoneB{}); \
-    if (ks > 1)                                                                                                                   \
-      hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(fmi_bw_grid(out_elems / 4, 256)), dim3(256), 0, st, ws, y, out_elems / 4);      \
-  } while (0)
-  auto wgs = [&](int bm, int bn) { return ceil_div64(Mmax, bm) * ceil_div64(N, bn) * nph; };
-  const int tile_dbg = g_bf16_tile_mode;
-  // the eight-phase kernel (conv_bf16_8ph.h): whole 64-deep reduction tiles, 8-byte output stores, no split reduction
-  // (narrower outputs reach it only for its fused output stage: the UNet's 64-channel layers, half of the 128-column tile masked off.
-  // With that stage on this kernel is taken whatever the tile count -- it is the only one that has the stage -- so a deep, small map at
-  // a small batch runs on a handful of workgroups: a throughput compromise of the one-launch eval form, not a tuned choice.)
-  bool ok8 = BK == 64 && tile_dbg != 1 && tile_dbg != 2 && N % 4 == 0 && (N > 64 || (act && act->on));
-  for (int p = 0; p < nph && ok8; ++p)
-    ok8 = set.ph[p].K % 64 == 0 && set.ph[p].la.g.ntaps() <= 32 && set.ph[p].ep.vec && (!set.ph[p].ep.colscale || (((uintptr_t)set.ph[p].ep.colscale & 15) == 0));
-  if (act && act->on && !ok8) return FMI_ERR_UNSUPPORTED;
-  if (ok8) {
-    const bool wide = N > 128;
-    const int64_t w8 = wide ? wgs(256, 256) : wgs(512, 128);
-    if (tile_dbg == 8 || (act && act->on) || w8 >= 200) {
-      const int64_t tn = ceil_div64(N, wide ? 256 : 128);
-      int64_t tmax = 0;
-      for (int p = 0; p < nph; ++p) {
-        const int64_t t = ceil_div64(set.ph[p].M, wide ? 256 : 512) * tn;
-        if (t > 0x7fffffffLL) return FMI_ERR_UNSUPPORTED;
-        set.ph[p].tiles = (int)t;
-        if (t > tmax) tmax = t;
-      }
-      set.tiles_n = (int)tn;
-      set.ksplit = 1;
-      set.ws = nullptr;
-      g_bf16_last_tile = 1000000 + (wide ? 256256 : 512128);
-      EpActB a{};
-      if (act) a = *act;
-      if (mask) {
-        if constexpr (BK == 64) {
-          if (wide) hipLaunchKernelGGL((conv_bf16_8ph_kernel<T8P256x256, EpMaskB>), dim3((unsigned)tmax, nph, 1), dim3(512), 0, st, set, *mask);
-          else hipLaunchKernelGGL((conv_bf16_8ph_kernel<T8P512x128, EpMaskB>), dim3((unsigned)tmax, nph, 1), dim3(512), 0, st, set, *mask);
-        }
-      } else if (wide) hipLaunchKernelGGL((conv_bf16_8ph_kernel<T8P256x256>), dim3((unsigned)tmax, nph, 1), dim3(512), 0, st, set, a);
-      else hipLaunchKernelGGL((conv_bf16_8ph_kernel<T8P512x128>), dim3((unsigned)tmax, nph, 1), dim3(512), 0, st, set, a);
-      return fmi_launch_status();
-    }
-  }
-  if (N <= 32) {
-    FMI_LAUNCH_B(TB128x32);
-  } else if (N <= 64) {
-    if (wgs(128, 64) >= 384) FMI_LAUNCH_B(TB128x64);
-    else FMI_LAUNCH_B(TB64x64);
+// The (tile, BK, output stage) combinations that exist as kernels -- what this predicate admits is what the library instantiates: every
+// TileB tile with the plain store, at both BK; with 64-deep reduction tiles the masked stage on at least 64 columns, the per-column stage
+// on the two tiles of two 64-row wave blocks, the grouped stage on the four tiles of its table; the eight-phase kernel with its own
+// stage (EpActB, which also is its plain store) and the masked one.
+template <class TILE, int BK, class EP>
+constexpr bool conv_kernel_exists_b() {
+  if (Is8P<TILE>::value) return BK == 64 && (std::is_same<EP, EpActB>::value || std::is_same<EP, EpMaskB>::value);
+  if (std::is_same<EP, EpNoneB>::value) return true;
+  if (std::is_same<EP, EpMaskB>::value) return BK == 64 && TILE::BN >= 64;
+  if (std::is_same<EP, EpChanB>::value) return BK == 64 && TILE::BM == 128 && TILE::BN >= 64;
+  if (std::is_same<EP, EpGroupB>::value) return BK == 64 && TILE::BM <= TILE::BN;
+  return false;
+}
+template <class TILE, int BK, class EP>
+static int launch_tile_b(const ConvSetB& set, const ConvPlanB& pl, const EP& ep, hipStream_t st) {
+  const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
+  if constexpr (Is8P<TILE>::value && std::is_same<EP, EpNoneB>::value) {
+    return launch_tile_b<TILE, BK>(set, pl, EpActB{}, st);  // the plain store of the eight-phase kernel: its own stage, switched off
+  } else if constexpr (!conv_kernel_exists_b<TILE, BK, EP>()) {
+    return FMI_ERR_UNSUPPORTED;  // the plan returns no such combination
   } else {
-    // measured (512 -> 512 at 64^2, 256 -> 256 at 128^2): 256x256 / 2 stages 870-990 TFLOP/s, 128x128 690-820, 256x256 with BK 32 and
-    // four stages 780-900; for N = 128 the 256x128 tile loses to 128x128 (660 vs 690)
-    if (BK == 64 && tile_dbg != 1 && N > 128 && wgs(256, 256) >= 200) FMI_LAUNCH_B(TB256x256);
-    else if (wgs(128, 128) >= 512) FMI_LAUNCH_B(TB128x128);
-    else if (wgs(64, 128) >= 256) FMI_LAUNCH_B(TB64x128);
-    else FMI_LAUNCH_B(TB64x64);
+    if constexpr (Is8P<TILE>::value) hipLaunchKernelGGL((conv_bf16_8ph_kernel<TILE, EP>), grid, dim3(TILE::NT), 0, st, set, ep);
+    else hipLaunchKernelGGL((conv_bf16_kernel<TILE, BK, 2, EP>), grid, dim3(TILE::NT), 0, st, set, ep);
+    return FMI_OK;
   }
-#undef FMI_LAUNCH_B
-  return fmi_launch_status();
+}
+template <int BK, class EP>
+static int launch_conv_bf16(const ConvSetB& set, const ConvPlanB& pl, const EP& ep, hipStream_t st) {
+  switch (pl.tile) {
+    case tile_id_b(128, 32): return launch_tile_b<TB128x32, BK>(set, pl, ep, st);
+    case tile_id_b(128, 64): return launch_tile_b<TB128x64, BK>(set, pl, ep, st);
+    case tile_id_b(64, 64): return launch_tile_b<TB64x64, BK>(set, pl, ep, st);
+    case tile_id_b(64, 128): return launch_tile_b<TB64x128, BK>(set, pl, ep, st);
+    case tile_id_b(128, 128): return launch_tile_b<TB128x128, BK>(set, pl, ep, st);
+    case tile_id_b(256, 256): return launch_tile_b<TB256x256, BK>(set, pl, ep, st);
+    case tile_id_b(512, 128, true): return launch_tile_b<T8P512x128, BK>(set, pl, ep, st);
+    case tile_id_b(256, 256, true): return launch_tile_b<T8P256x256, BK>(set, pl, ep, st);
+  }
+  return FMI_ERR_UNSUPPORTED;
 }
 
-static int check_desc_b(const fmi_conv_desc* d) {
-  if (!d) return FMI_ERR_BAD_ARG;
-  if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->C <= 0 || d->K <= 0 || d->kh <= 0 || d->kw <= 0 || d->stride <= 0 || d->pad < 0 ||
-      d->x_cstride < d->C || d->y_cstride < d->K)
-    return FMI_ERR_BAD_ARG;
-  if (d->dil > 1) return FMI_ERR_UNSUPPORTED;  // dilated convolutions (modules/drn.py) exist in the fp32 family only
-  if (d->OH != (d->H + 2 * d->pad - d->kh) / d->stride + 1 || d->OW != (d->W + 2 * d->pad - d->kw) / d->stride + 1) return FMI_ERR_BAD_ARG;
-  if (d->OH <= 0 || d->OW <= 0) return FMI_ERR_BAD_ARG;
-  if (d->pad_mode != 0) return FMI_ERR_UNSUPPORTED;
-  if ((int64_t)d->N * d->H * d->W > 0x7fffffffLL / 2 || (int64_t)d->N * d->OH * d->OW > 0x7fffffffLL / 2 ||
-      (int64_t)d->kh * d->kw * d->C > 0x3fffffffLL || (int64_t)d->kh * d->kw * d->K > 0x3fffffffLL)
-    return FMI_ERR_UNSUPPORTED;
-  return FMI_OK;
-}
-
-extern "C" int fmi_conv2d_bf16_supported(const fmi_conv_desc* d) {
-  if (check_desc_b(d) != FMI_OK) return 0;
-  return d->C % 32 == 0 && d->K % 32 == 0 && d->x_cstride % 8 == 0 && d->y_cstride % 8 == 0;
-}
-
-// The one-phase ConvSetB of a plain forward convolution: geometry, both loaders, the addressing of the output stage, M, K and the unsplit
-// defaults of N / ksplit / ws (launch_conv_bf16 sets those three again).  vec_flag: y takes the 8-byte stores (ConvEpB::vec).
-static ConvSetB fwd_set_b(const fmi_conv_desc* d, const uint16_t* x, const uint16_t* wnk, uint16_t* y, const float* colscale, int vec_flag) {
-  ConvGeom g = fwd_geom(d, d->N);      // check_desc_b: no dilation, pad_mode 0.  img_bs stays 0: no per-sample weights in this family
-  g.vec = d->C % 64 == 0 ? 6 : 5;      // here: log2 of the reduction tile BK (the fp32 family keeps a float4 flag in this field)
-  g.dC = make_fastdiv(g.nty * g.ntx);  // here: divides by the number of TAPS (ConvKB::tile; the weight gradients and fp32 divide by C)
+// The ConvSetB of a launch: the pointers around the phases' geometry (both loaders, the addressing of the output stage) and the plan's
+// tile counts and split.  a: the gathered tensor (x of the forward, dy of the adjoint), w: the weights packed [columns][kh*kw][reduction]
+// ([K][taps][C] forward, [C][taps][K] adjoint), out: y / dx.  ws: the split reduction's fp32 twin of the output, used when the plan splits.
+static ConvSetB conv_set_b(const fmi_conv_desc* d, int pass, const ConvPhasesB& ph, const ConvPlanInB& in, const ConvPlanB& pl, const uint16_t* a,
+                           const uint16_t* w, const float* colscale, uint16_t* out, float* ws) {
   ConvSetB set{};
-  set.ph[0].la = ConvKB{x, g};
-  set.ph[0].lb = ConvWKB{wnk, g, d->K, d->kh * d->kw};
-  set.ph[0].ep = ConvEpB{y, colscale, d->OH, d->OW, 1, 0, 0, d->OH, d->OW, d->y_cstride, d->K, g.dGW, g.dG, vec_flag};
-  set.ph[0].M = g.Mdim();
-  set.ph[0].K = g.Kdim();
-  set.N = d->K;
-  set.ksplit = 1;
+  for (int p = 0; p < ph.nph; ++p) {
+    const ConvGeom& g = ph.g[p];
+    ConvPhaseB& P = set.ph[p];
+    P.la = ConvKB{a, g};
+    P.lb = ConvWKB{w, g, in.N, d->kh * d->kw};
+    if (pass == 0) P.ep = ConvEpB{out, colscale, g.GH, g.GW, 1, 0, 0, d->OH, d->OW, d->y_cstride, in.N, g.dGW, g.dG, in.vec[p]};
+    else P.ep = ConvEpB{out, colscale, g.GH, g.GW, d->stride, ph.py[p], ph.px[p], d->H, d->W, d->x_cstride, in.N, g.dGW, g.dG, in.vec[p]};
+    P.M = in.M[p], P.K = in.K[p], P.tiles = pl.tiles[p];
+  }
+  set.N = in.N, set.tiles_n = pl.tiles_n, set.ksplit = pl.ksplit;
+  set.ws = pl.ksplit > 1 ? ws : nullptr;
   return set;
 }
 
-static int conv2d_fwd_bf16_impl(const fmi_conv_desc* d, const uint16_t* x, const uint16_t* wnk, const float* colscale, uint16_t* y, float* ws,
-                               int64_t ws_floats, const EpActB* act, void* stream) {
+// Every forward / adjoint entry behind its argument checks: phases, plan, set, launch -- and, where the plan split the reduction (small
+// feature maps with a deep reduction; partial sums meet through atomics in ws, which the caller zeroed), the conversion of the sums to bf16.
+template <class EP>
+static int run_conv_b(const fmi_conv_desc* d, int pass, int stage, int groups, const uint16_t* a, const uint16_t* w, const float* colscale,
+                      uint16_t* out, float* ws, int64_t ws_floats, const EP& ep, void* stream) {
+  const ConvPhasesB ph = conv_phases_b(d, pass);
+  const int64_t out_elems = out_elems_b(d, pass);
+  const bool out_al8 = ((uintptr_t)out & 7) == 0;
+  const int flags = (out_al8 ? FMI_PLAN_OUT_AL8 : 0) | (colscale ? FMI_PLAN_COLSCALE : 0) | (fmi_al16(colscale) ? FMI_PLAN_COLSCALE_AL16 : 0) |
+                    (ws && fmi_al16(ws) && out_al8 && ws_floats >= out_elems ? FMI_PLAN_SPLIT_WS : 0);
+  const ConvPlanInB in = conv_plan_in_b(d, pass, stage, groups, ph, flags);
+  const ConvPlanB pl = conv_plan_b(in);
+  if (pl.status) return pl.status;
+  const ConvSetB set = conv_set_b(d, pass, ph, in, pl, a, w, colscale, out, ws);
+  hipStream_t st = (hipStream_t)stream;
+  g_bf16_last_tile = pl.tile;
+  const int rc = in.BK == 64 ? launch_conv_bf16<64>(set, pl, ep, st) : launch_conv_bf16<32>(set, pl, ep, st);
+  if (rc) return rc;
+  if (pl.ksplit > 1) hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(fmi_bw_grid(out_elems / 4, 256)), dim3(256), 0, st, ws, out, out_elems / 4);
+  return fmi_launch_status();
+}
+
+static int conv2d_fwd_bf16_check(const fmi_conv_desc* d, const uint16_t* x, const uint16_t* wnk, const uint16_t* y) {
   int rc = check_desc_b(d);
   if (rc) return rc;
   if (!x || !wnk || !y) return FMI_ERR_BAD_ARG;
   if (d->C % 32 != 0 || d->x_cstride % 8 != 0 || !fmi_al16(x) || !fmi_al16(wnk)) return FMI_ERR_UNSUPPORTED;
-  ConvSetB set = fwd_set_b(d, x, wnk, y, colscale, (d->K % 4 == 0 && d->y_cstride % 4 == 0 && ((uintptr_t)y & 7) == 0) ? 1 : 0);
-  const int64_t out_elems = (int64_t)d->N * d->OH * d->OW * d->y_cstride;
-  if (ws && (((uintptr_t)ws & 15) || ((uintptr_t)y & 7))) ws = nullptr;
-  if (d->C % 64 == 0) return launch_conv_bf16<64>(set, 1, d->K, y, ws, ws_floats, out_elems, (hipStream_t)stream, act);
-  return launch_conv_bf16<32>(set, 1, d->K, y, ws, ws_floats, out_elems, (hipStream_t)stream, act);
+  return FMI_OK;
 }
-
 extern "C" int fmi_conv2d_fwd_bf16(const fmi_conv_desc* d, const uint16_t* x, const uint16_t* wnk, const float* colscale, uint16_t* y,
                                    float* ws, int64_t ws_floats, void* stream) {
-  return conv2d_fwd_bf16_impl(d, x, wnk, colscale, y, ws, ws_floats, nullptr, stream);
+  int rc = conv2d_fwd_bf16_check(d, x, wnk, y);
+  if (rc) return rc;
+  return run_conv_b(d, 0, STAGE_PLAIN_B, 1, x, wnk, colscale, y, ws, ws_floats, EpNoneB{}, stream);
 }
 /* y = lrelu(conv(x, W) * colscale[n][k] + nw[0] * noise[n][oy][ox] + bias[k], slope) * gain: a StyledConv without upsampling in one
  * launch (stylegan2/model.py:241-279 ModulatedConv2d on pre-scaled activations, :250-252 demodulation, :282-294 NoiseInjection,
@@ -691,8 +750,9 @@ extern "C" int fmi_conv2d_fwd_act_bf16(const fmi_conv_desc* d, const uint16_t* x
                                        const float* nw, const float* bias, float slope, float gain, uint16_t* y, void* stream) {
   if (noise && !nw) return FMI_ERR_BAD_ARG;
   if (bias && ((uintptr_t)bias & 15)) return FMI_ERR_UNSUPPORTED;
-  EpActB act{noise, nw, bias, slope, gain, 1};
-  return conv2d_fwd_bf16_impl(d, x, wnk, colscale, y, nullptr, 0, &act, stream);
+  int rc = conv2d_fwd_bf16_check(d, x, wnk, y);
+  if (rc) return rc;
+  return run_conv_b(d, 0, STAGE_ACT_B, 1, x, wnk, colscale, y, nullptr, 0, EpActB{noise, nw, bias, slope, gain, 1}, stream);
 }
 /* y = prelu(conv(x, W) * scale[k] + bias[k], slope[k]): the per-column output stage EpChanB of conv_bf16_kernel, for the eval-mode IR-SE
  * block (helpers.py:85-89 / :107-113 of the reference: conv1 + PReLU with slope; conv2 + BatchNorm and the shortcut's 1x1 convolution +
@@ -704,76 +764,22 @@ extern "C" int fmi_conv2d_fwd_chan_bf16(const fmi_conv_desc* d, const uint16_t* 
   if (!x || !wnk || !y) return FMI_ERR_BAD_ARG;
   const bool k3 = d->kh == 3 && d->kw == 3 && d->pad == 1, k1 = d->kh == 1 && d->kw == 1 && d->pad == 0;
   if (!(k3 || k1) || (d->stride != 1 && d->stride != 2) || d->C % 64 != 0 || d->K % 64 != 0) return FMI_ERR_UNSUPPORTED;
-  const int64_t M = (int64_t)d->N * d->OH * d->OW;
   if (colsum) {
     if ((int64_t)d->OH * d->OW < 128) return FMI_ERR_UNSUPPORTED;  // a 128-row tile would touch more than two samples
-    if (colsum_floats < ceil_div64(M, FMI_CHAN_COLSUM_ROWS) * 2 * d->K) return FMI_ERR_BAD_ARG;
+    if (colsum_floats < ceil_div64((int64_t)d->N * d->OH * d->OW, FMI_CHAN_COLSUM_ROWS) * 2 * d->K) return FMI_ERR_BAD_ARG;
   }
   if (d->x_cstride % 8 != 0 || d->y_cstride % 4 != 0 || !fmi_al16(x) || !fmi_al16(wnk) || ((uintptr_t)y & 7) || !fmi_al16(scale) ||
       !fmi_al16(bias) || !fmi_al16(slope) || !fmi_al16(colsum))
     return FMI_ERR_UNSUPPORTED;
-  ConvSetB set = fwd_set_b(d, x, wnk, y, nullptr, 1);  // C % 64 == 0 (above): 64-deep reduction tiles
-  const EpChanB ch{scale, bias, slope, colsum};
-  hipStream_t st = (hipStream_t)stream;
-  // both tiles have 128 rows in two 64-row wave blocks (the column sums' granularity); 64 output columns take the narrow one
-  const int bn = d->K <= 64 ? 64 : 128;
-  const int64_t tn = ceil_div64(d->K, bn), tiles = ceil_div64(M, 128) * tn;
-  if (tiles > 0x7fffffffLL) return FMI_ERR_UNSUPPORTED;
-  set.tiles_n = (int)tn;
-  set.ph[0].tiles = (int)tiles;
-  if (bn == 64) hipLaunchKernelGGL((conv_bf16_kernel<TB128x64, 64, 2, EpChanB>), dim3((unsigned)tiles, 1, 1), dim3(TB128x64::NT), 0, st, set, ch);
-  else hipLaunchKernelGGL((conv_bf16_kernel<TB128x128, 64, 2, EpChanB>), dim3((unsigned)tiles, 1, 1), dim3(TB128x128::NT), 0, st, set, ch);
-  return fmi_launch_status();
+  return run_conv_b(d, 0, STAGE_CHAN_B, 1, x, wnk, nullptr, y, nullptr, 0, EpChanB{scale, bias, slope, colsum}, stream);
 }
 /* The tile path of fmi_conv2d_grouped_fwd_bf16 (style_heads_bf16.hip, which has checked every argument): G convolutions as one launch
  * of conv_bf16_kernel with the grouped output stage, grid = (tiles of one group, G).  d->C / d->K are per group; x_off / w_off are the
  * element offsets between consecutive groups inside a pixel of x and between their weight packs.  A shared map (x_off == 0) arrives here
- * as ONE group of G*K columns: the stacked packs are its [G*K][taps][C] weight as they lie.  The tile follows launch_conv_bf16's measured
- * table, with the groups counted into the workgroups of a candidate. */
+ * as ONE group of G*K columns: the stacked packs are its [G*K][taps][C] weight as they lie. */
 int fmi_conv_bf16_grouped_tiles(const fmi_conv_desc* d, int G, int64_t x_off, int64_t w_off, const uint16_t* x, const uint16_t* wnk,
                                 const float* bias, float slope, uint16_t* y, void* stream) {
-  ConvSetB set = fwd_set_b(d, x, wnk, y, nullptr, 1);  // C % 64 == 0 (the caller checks): 64-deep reduction tiles
-  const EpGroupB ch{bias, slope, x_off, w_off};
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t M = set.ph[0].M;
-  auto wgs = [&](int bm, int bn) { return ceil_div64(M, bm) * ceil_div64(d->K, bn) * G; };
-#define FMI_LAUNCH_G(TILE)                                                                                                             \
-  do {                                                                                                                                 \
-    const int64_t tn = ceil_div64(d->K, TILE::BN), tiles = ceil_div64(M, TILE::BM) * tn;                                               \
-    if (tiles > 0x7fffffffLL) return FMI_ERR_UNSUPPORTED;                                                                              \
-    set.tiles_n = (int)tn;                                                                                                             \
-    set.ph[0].tiles = (int)tiles;                                                                                                      \
-    hipLaunchKernelGGL((conv_bf16_kernel<TILE, 64, 2, EpGroupB>), dim3((unsigned)tiles, (unsigned)G, 1), dim3(TILE::NT), 0, st, set, ch); \
-  } while (0)
-  if (d->K > 128 && wgs(256, 256) >= 200) FMI_LAUNCH_G(TB256x256);
-  else if (d->K > 64 && wgs(128, 128) >= 512) FMI_LAUNCH_G(TB128x128);
-  else if (d->K > 64 && wgs(64, 128) >= 256) FMI_LAUNCH_G(TB64x128);
-  else FMI_LAUNCH_G(TB64x64);
-#undef FMI_LAUNCH_G
-  return fmi_launch_status();
-}
-// The phases of an adjoint launch: one ConvPhaseB per non-empty sub-pixel phase of the stride (geometry, both loaders, the addressing of
-// the output stage, M, K); returns their number.
-static int adj_set_b(const fmi_conv_desc* d, const uint16_t* dy, const uint16_t* wck, const float* colscale, uint16_t* dx, ConvSetB& set) {
-  const int s = d->stride;
-  int nph = 0;
-  for (int py = 0; py < s; ++py) {
-    for (int px = 0; px < s; ++px) {
-      ConvGeom g = adj_geom(d, d->N, py, px);  // img_bs stays 0: no per-sample weights in this family
-      const int GH = g.GH, GW = g.GW;
-      if (GH <= 0 || GW <= 0) continue;
-      g.vec = d->K % 64 == 0 ? 6 : 5;                                      // here: log2 of the reduction tile
-      g.dC = make_fastdiv(g.nty * g.ntx > 0 ? g.nty * g.ntx : 1);          // here: divides by the number of TAPS (1: the empty phase)
-      ConvPhaseB& P = set.ph[nph++];
-      P.la = ConvKB{dy, g};
-      P.lb = ConvWKB{wck, g, d->C, d->kh * d->kw};
-      P.ep = ConvEpB{dx, colscale, GH, GW, s, py, px, d->H, d->W, d->x_cstride, d->C, g.dGW, g.dG,
-                     (d->C % 4 == 0 && d->x_cstride % 4 == 0 && ((uintptr_t)dx & 7) == 0) ? 1 : 0};
-      P.M = g.Mdim();
-      P.K = g.Kdim();
-    }
-  }
-  return nph;
+  return run_conv_b(d, 0, STAGE_GROUP_B, G, x, wnk, nullptr, y, nullptr, 0, EpGroupB{bias, slope, x_off, w_off}, stream);
 }
 /* dx = adjoint of the convolution described by d applied to dy; wck = weights packed [C][kh*kw][K] */
 extern "C" int fmi_conv2d_dgrad_bf16(const fmi_conv_desc* d, const uint16_t* dy, const uint16_t* wck, const float* colscale, uint16_t* dx,
@@ -783,13 +789,7 @@ extern "C" int fmi_conv2d_dgrad_bf16(const fmi_conv_desc* d, const uint16_t* dy,
   if (!dy || !wck || !dx) return FMI_ERR_BAD_ARG;
   if (d->K % 32 != 0 || d->y_cstride % 8 != 0 || !fmi_al16(dy) || !fmi_al16(wck)) return FMI_ERR_UNSUPPORTED;
   if (d->stride > 2) return FMI_ERR_UNSUPPORTED;  // at most four sub-pixel phases per launch
-  ConvSetB set{};
-  const int nph = adj_set_b(d, dy, wck, colscale, dx, set);
-  if (nph == 0) return FMI_OK;
-  const int64_t out_elems = (int64_t)d->N * d->H * d->W * d->x_cstride;
-  if (ws && (((uintptr_t)ws & 15) || ((uintptr_t)dx & 7))) ws = nullptr;
-  return d->K % 64 == 0 ? launch_conv_bf16<64>(set, nph, d->C, dx, ws, ws_floats, out_elems, (hipStream_t)stream)
-                        : launch_conv_bf16<32>(set, nph, d->C, dx, ws, ws_floats, out_elems, (hipStream_t)stream);
+  return run_conv_b(d, 1, STAGE_PLAIN_B, 1, dy, wck, colscale, dx, ws, ws_floats, EpNoneB{}, stream);
 }
 /* dx = a_in > 0 ? adjoint(dy) : 0 -- fmi_conv2d_dgrad_bf16 with the mask of the ReLU that produced the convolution's input in the output
  * stage (EpMaskB): the convolutions of a VGG16 block that read another convolution's activated map (modules/loss.py:33-52 of the
@@ -802,11 +802,9 @@ extern "C" int fmi_conv2d_dgrad_relu_bf16(const fmi_conv_desc* d, const uint16_t
   if (!dy || !wck || !a_in || !dx) return FMI_ERR_BAD_ARG;
   if (d->kh != 3 || d->kw != 3 || d->pad != 1 || d->stride != 1 || d->C % 64 != 0 || d->K % 64 != 0) return FMI_ERR_UNSUPPORTED;
   if (d->x_cstride % 4 != 0 || d->y_cstride % 8 != 0 || !fmi_al16(dy) || !fmi_al16(wck) || !fmi_al16(a_in) || !fmi_al16(dx)) return FMI_ERR_UNSUPPORTED;
-  ConvSetB set{};
-  const int nph = adj_set_b(d, dy, wck, nullptr, dx, set);  // one phase, its 8-byte stores on (checked above)
-  const EpMaskB mask{a_in};
-  return launch_conv_bf16<64>(set, nph, d->C, dx, nullptr, 0, (int64_t)d->N * d->H * d->W * d->x_cstride, (hipStream_t)stream, nullptr, &mask);
+  return run_conv_b(d, 1, STAGE_MASK_B, 1, dy, wck, nullptr, dx, nullptr, 0, EpMaskB{a_in}, stream);
 }
+
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // weight packs: src fp32 [T][A][B] (the fp32 packs wf[tap][C][K] / wt[tap][K][C]) -> bf16 [B][T][A]
@@ -1001,55 +999,25 @@ extern "C" int fmi_conv2d_wgrad_bf16(const fmi_conv_desc* d, const uint16_t* x, 
   if (!x || !dy || !dwf) return FMI_ERR_BAD_ARG;
   if (d->C % 32 != 0 || d->K % 8 != 0 || d->x_cstride % 8 != 0 || d->y_cstride % 8 != 0 || !fmi_al16(x) || !fmi_al16(dy))
     return FMI_ERR_UNSUPPORTED;
-  WgArgsB a{};
-  a.x = x; a.dy = dy; a.dwf = dwf;
-  ConvGeom& g = a.g;
-  g = fwd_geom(d, d->N);     // vec and img_bs stay 0: the weight gradient reads neither
-  g.dC = make_fastdiv(g.C);  // here: divides by C (output row -> tap), as in the fp32 family
-  a.Kout = d->K; a.ycs = d->y_cstride; a.Mrows = d->kh * d->kw * d->C; a.P = d->N * d->OH * d->OW;
-  // the eight-phase kernel (wgrad_bf16_8ph.h): 256 x 256 tiles, one workgroup per CU -- for wide layers with a long pixel range
-  {
-    const int mode = g_bf16_tile_mode;
-    const int64_t tm8 = ceil_div64(a.Mrows, 256), tn8 = ceil_div64(d->K, 256);
-    const bool fits = d->K >= 256 && tn8 * 256 - d->K <= d->K / 8 && tm8 * 256 - a.Mrows <= a.Mrows / 8 && tm8 * tn8 <= 256 && a.P >= 4096 &&
-                      (int64_t)d->kh * d->kw * d->C < (1ll << 30) && (int64_t)d->N * d->H * d->W * d->x_cstride < (1ll << 31);
-    if (fits && !fmi_det() && mode != 1 && mode != 2) {
-      Wg8Args w{};
-      w.x = x; w.dy = dy; w.dwf = dwf; w.g = g;
-      w.Kout = d->K; w.ycs = d->y_cstride; w.Mrows = a.Mrows; w.P = a.P;
-      w.tiles = (int)(tm8 * tn8); w.tiles_n = (int)tn8;
-      int64_t ks = 256 / w.tiles;
-      if (ks > a.P / 1024) ks = a.P / 1024;
-      if (ks < 1) ks = 1;
-      w.kchunk = (int)(ceil_div64(ceil_div64(a.P, ks), 64) * 64);
-      w.ksplit = (int)ceil_div64(a.P, w.kchunk);
-      hipLaunchKernelGGL(wgrad_bf16_8ph_kernel, dim3((unsigned)(w.tiles * w.ksplit)), dim3(512), 0, (hipStream_t)stream, w);
-      return fmi_launch_status();
-    }
-  }
-  // the 8-wave 256x256 tile (the kernel takes it: WPP = 2) measured SLOWER here than 128x128 (574 vs 770 TFLOP/s at 512 -> 512, 64^2):
-  // one workgroup per CU and a 16-accumulator atomic epilogue per split leave the CU idle between tiles
-  const int bn = d->K <= 32 ? 32 : (d->K <= 64 ? 64 : 128);
-  const int64_t tm = ceil_div64(a.Mrows, 128), tn = ceil_div64(d->K, bn);
-  int64_t ksplit = 2048 / (tm * tn);
-  const int64_t kmax = a.P / 1024;
-  if (ksplit > kmax) ksplit = kmax;
-  if (ksplit < 1) ksplit = 1;
-  if (ksplit > 65535) ksplit = 65535;
-  if (ksplit >= 6) ksplit = (ksplit + 4) / 8 * 8;  // splits are dealt to the 8 XCDs in groups of 8: keep the groups full
-  if (fmi_det()) ksplit = 1;                       // reproducible mode
-  a.kchunk = (int)(ceil_div64(ceil_div64(a.P, ksplit), 64) * 64);
-  ksplit = ceil_div64(a.P, a.kchunk);
-  a.tiles = (int)(tm * tn);
-  a.ksplit = (int)ksplit;
-  a.xcd_splits = ksplit >= 8 ? 1 : 0;
-  const int64_t nwg = a.xcd_splits ? tm * tn * ceil_div64(ksplit, 8) * 8 : tm * tn;
-  if (nwg > 0x7fffffffLL) return FMI_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)nwg, a.xcd_splits ? 1u : (unsigned)ksplit);
+  const WgradPlanInB in = wgrad_plan_in_b(d, 0);
+  const ConvPlanB pl = wgrad_plan_b(in);
+  if (pl.status) return pl.status;
+  ConvGeom g = fwd_geom(d, d->N);  // vec and img_bs stay 0: the weight gradient reads neither
+  g.dC = make_fastdiv(g.C);        // here: divides by C (output row -> tap), as in the fp32 family
+  const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
   hipStream_t st = (hipStream_t)stream;
-  if (bn == 32) hipLaunchKernelGGL((wgrad_bf16_kernel<TB128x32>), grid, dim3(256), 0, st, a, (int)tn);
-  else if (bn == 64) hipLaunchKernelGGL((wgrad_bf16_kernel<TB128x64>), grid, dim3(256), 0, st, a, (int)tn);
-  else hipLaunchKernelGGL((wgrad_bf16_kernel<TB128x128>), grid, dim3(256), 0, st, a, (int)tn);
+  // the two kernels take their own argument structs (and wgrad_bf16_kernel the column tile count beside it): their launch lines stay here
+  if (tile_8p_b(pl.tile)) {
+    const Wg8Args w{x, dy, dwf, g, d->K, d->y_cstride, in.Mrows, in.P, pl.kchunk, pl.tiles[0], pl.tiles_n, pl.ksplit};
+    hipLaunchKernelGGL(wgrad_bf16_8ph_kernel, grid, dim3(512), 0, st, w);
+    return fmi_launch_status();
+  }
+  const WgArgsB a{x, dy, dwf, g, d->K, d->y_cstride, in.Mrows, in.P, pl.kchunk, pl.tiles[0], pl.ksplit, pl.xcd_splits};
+  const int bn = tile_bn_b(pl.tile);
+  if (bn == 32) hipLaunchKernelGGL((wgrad_bf16_kernel<TB128x32>), grid, dim3(256), 0, st, a, pl.tiles_n);
+  else if (bn == 64) hipLaunchKernelGGL((wgrad_bf16_kernel<TB128x64>), grid, dim3(256), 0, st, a, pl.tiles_n);
+  else hipLaunchKernelGGL((wgrad_bf16_kernel<TB128x128>), grid, dim3(256), 0, st, a, pl.tiles_n);
   return fmi_launch_status();
 }
+
 #endif  // FMI_HOST_EMU

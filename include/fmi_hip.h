@@ -48,15 +48,6 @@ int fmi_version(void);
 int fmi_set_deterministic(int on);
 int fmi_get_deterministic(void);
 
-/* Kernel selection override of the bf16 convolution family (tests; initial value 0): 0 = by shape,
- * 1 = never the eight-wave tiles, 2 = no eight-phase kernel, 8 = the eight-phase kernel (csrc/conv_bf16_8ph.h) wherever it is legal.
- * mode < 0 only queries.  Returns the previous mode. */
-int fmi_debug_bf16_tile(int mode);
-/* The tile the last launch of the bf16 forward / adjoint dispatch took (tests assert which kernel a shape reached): 1000 BM + BN of the
- * tile (rows x output columns), plus 1000000 for the eight-phase kernel; 0 before the first launch.  fmi_conv2d_fwd_chan_bf16 and the
- * grouped entry choose their tiles themselves and do not set it. */
-int fmi_debug_bf16_last_tile(void);
-
 /* ------------------------------------------------------------------------
  * Dense batched GEMM on the fp32 matrix cores (v_mfma_f32_32x32x2_f32).
  *   C[b] = alpha * A[b] . B[b] (+ bias[n]) + beta * C[b]
@@ -278,6 +269,31 @@ int fmi_conv2d_thin_in_wgrad_f32(const fmi_conv_desc* d, const float* x, const f
  * phases of a stride-2 adjoint run in ONE launch; stride > 2 is FMI_ERR_UNSUPPORTED.
  * ---------------------------------------------------------------------- */
 int fmi_conv2d_bf16_supported(const fmi_conv_desc* d);
+/* Kernel selection override of the bf16 convolution family (tests; initial value 0): 0 = by shape,
+ * 1 = never the eight-wave tiles, 2 = no eight-phase kernel, 8 = the eight-phase kernel (csrc/conv_bf16_8ph.h) wherever it is legal.
+ * mode < 0 only queries.  Returns the previous mode. */
+int fmi_debug_bf16_tile(int mode);
+/* The tile the last launch of the bf16 forward / adjoint kernels took (tests assert which kernel a shape reached): 1000 BM + BN of the
+ * tile (rows x output columns), plus 1000000 for the eight-phase kernel; 0 before the first launch.  Every entry that launches them records
+ * it: fmi_conv2d_fwd_bf16, _fwd_act_bf16, _fwd_chan_bf16, the tile path of _grouped_fwd_bf16, _dgrad_bf16 and _dgrad_relu_bf16. */
+int fmi_debug_bf16_last_tile(void);
+/* The launch one of those entries, or fmi_conv2d_wgrad_bf16, would make for d -- decided by the code the entries run (csrc/conv_bf16_plan.h),
+ * without a launch and without a GPU.  pass: 0 forward, 1 adjoint, 2 weight gradient.  stage: 0 plain, 1 the fused StyledConv stage
+ * (_fwd_act_), 2 per-column (_fwd_chan_), 3 grouped (groups = G, d per group; a shared map is ONE group of G K columns), 4 masked
+ * (_dgrad_relu_).  flags: what the decision reads of a call's pointers, and optionally the two modes.  out[FMI_CONV_BF16_PLAN_INTS]:
+ * [0] status (FMI_OK / FMI_ERR_UNSUPPORTED as the entry returns it; the rest is 0 when refused), [1] tile code as above (weight gradient:
+ * 128 x {32, 64, 128}, or 256 x 256 + 1000000 for its eight-phase kernel), [2] splits of the reduction, [3..5] grid, [6..9] tiles per
+ * phase, [10] column tiles, [11] phases, [12] / [13] the weight gradient's pixels per split / splits dealt to the XCDs in groups of 8.
+ * Returns out[0]; FMI_ERR_BAD_ARG for a null d or out, an unknown pass or stage.  Only the descriptor checks common to the entries are
+ * made: an entry's own refusals (channel multiples, alignment) are not repeated. */
+#define FMI_CONV_BF16_PLAN_INTS 14
+#define FMI_PLAN_SPLIT_WS 1       /* a split workspace is offered: 16-byte aligned, at least the output's element count in floats */
+#define FMI_PLAN_COLSCALE 2       /* colscale != NULL */
+#define FMI_PLAN_COLSCALE_AL16 4  /* ... and 16-byte aligned */
+#define FMI_PLAN_OUT_AL8 8        /* the output tensor is 8-byte aligned */
+#define FMI_PLAN_DET 16           /* with FMI_PLAN_MODES: reproducible mode */
+#define FMI_PLAN_MODES 32         /* take reproducible mode and tile mode (bits 8..11) from flags, not from the library's current settings */
+int fmi_conv2d_bf16_plan(const fmi_conv_desc* d, int pass, int stage, int groups, int flags, int* out);
 int fmi_conv2d_fwd_bf16(const fmi_conv_desc* d, const uint16_t* x, const uint16_t* wnk, const float* colscale, uint16_t* y, float* ws,
                         int64_t ws_floats, void* stream);
 /* y = lrelu(conv(x, W) * colscale[n][k] + nw[0] * noise[n][oy][ox] + bias[k], slope) * gain in one launch: ModulatedConv2d on pre-scaled

@@ -1,7 +1,7 @@
 """cmp_conv_bf16.py <cand.so> <ref.so>: every entry of the bf16 convolution family (csrc/conv_bf16.hip and the grouped tile path of
 style_heads_bf16.hip) and the Python forward wrappers that share _conv_fwd_bf16_pre, under two builds of the library on identical inputs;
-every output must be torch.equal on the raw bits.  The shapes take each branch of the host set-up (the tile table of launch_conv_bf16, the
-grouped table, the adjoint's phases) and each output stage of conv_bf16_kernel.  The weight gradient and the split reduction accumulate
+every output must be torch.equal on the raw bits.  The shapes take each branch of the host set-up (the tables of csrc/conv_bf16_plan.h, plain and
+grouped, the adjoint's phases) and each output stage of conv_bf16_kernel.  The weight gradient and the split reduction accumulate
 with atomics outside the reproducible mode: they run in that mode only.  A refusal (FmiError) is reported; where one is expected both
 builds must refuse alike.  Exit status 1 on any difference.  Either build may lack entries the other has (an older library next to a newer
 one): only the entries the cases call are needed."""
@@ -78,7 +78,7 @@ def wpack(k, taps, c):
 p, st = FF._p, FF._st
 
 
-# ---- fmi_conv2d_fwd_bf16: one case per branch of launch_conv_bf16's table ----
+# ---- fmi_conv2d_fwd_bf16: one case per branch of the plain table of conv_bf16_plan.h ----
 def fwd(n, h, w, c, k, ks, stride, pad, colscale=False, split=False):
     def run(lib, x, wnk, cs):
         d, oh, ow = desc(n, h, w, c, k, ks, stride, pad)
@@ -191,6 +191,22 @@ for g in ((2, 8, 8, 64, 64), (1, 12, 20, 128, 64), (2, 16, 16, 256, 512), (2, 16
     for mode in (0, 2, 8):
         case(f"dgrad {g} k3", *dgrad(*g, 3, 1, 1), tile=mode)
         case(f"fwd {g} k3", *fwd(*g, 3, 1, 1), tile=mode)
+
+
+# ---- fmi_conv2d_dgrad_relu_bf16: the masked output stage on each of its seven kernels (ADJ_CASES of tests/test_gpu_vgg_bf16.py) ----
+def dgrad_relu(n, h, w, c, k):
+    def run(lib, gy, wck, a):
+        d, _, _ = desc(n, h, w, c, k, 3, 1, 1)
+        dx = nan((n, h, w, c))
+        lib.conv2d_dgrad_relu_bf16(C.byref(d), p(gy), p(wck), p(a), p(dx), st())
+        return dx
+    return run, rn(n, h, w, k, dtype=BF16), wpack(c, 9, k), rn(n, h, w, c, dtype=BF16)
+
+
+for g, modes in (((2, 8, 8, 64, 64), (0, 2, 8)), ((1, 12, 20, 128, 64), (0, 2, 8)), ((2, 16, 16, 256, 512), (0, 2, 8)), ((2, 16, 16, 512, 256), (0, 2, 8)),
+                 ((1, 192, 256, 64, 64), (0,)), ((1, 128, 128, 128, 64), (2,)), ((1, 128, 128, 512, 64), (2,)), ((1, 160, 160, 512, 64), (2,))):
+    for mode in modes:
+        case(f"dgrad_relu {g} k3", *dgrad_relu(*g), tile=mode)
 for g in ((4, 64, 64, 512, 512), (4, 128, 128, 256, 256), (4, 256, 256, 128, 128)):
     case(f"dgrad decoder layer {g} k3", *dgrad(*g, 3, 1, 1))
     case(f"fwd decoder layer {g} k3", *fwd(*g, 3, 1, 1))
