@@ -217,7 +217,7 @@ SIGNATURES = {
 STATUS = {0: "ok", 1: "bad argument", 2: "unsupported shape/mode", 3: "kernel launch failed"}
 
 
-PREDICATES = {"fmi_debug_bf16_tile": [i32], "fmi_debug_bf16_last_tile": [], "fmi_conv2d_bf16_plan": [PD, i32, i32, i32, i32, vp], "fmi_set_deterministic": [i32], "fmi_get_deterministic": [], "fmi_conv2d_thin_supported": [PD], "fmi_conv2d_bf16_supported": [PD], "fmi_conv2d_thin_lrelu_supported": [PD], "fmi_conv2d_thin_lrelu_bwd_ws_bytes": [PD], "fmi_conv2d_thin_in_supported": [PD], "fmi_conv2d_thin_in_routed": [PD], "fmi_conv2d_thin_in_wgrad_ws_bytes": [PD], "fmi_conv2d_pair_supported": [PD, i32], "fmi_conv2d_pair_routed": [PD, i32], "fmi_conv2d_pair_ksplit": [PD, i32, i32], "fmi_conv_transpose2d_pair_bwd_supported": [PD, i32, i32], "fmi_conv_transpose2d_pair_bwd_ws_bytes": [PD, i32, i32], "fmi_attention_fwd_uses_pieces": [i32] * 5, "fmi_attention_bwd_uses_pieces": [i32] * 5, "fmi_attention_fwd_waves": [i32] * 2, "fmi_attention_fwd_bf16_waves": [i32] * 2, "fmi_guided_attention_fwd_bf16_waves": [i32] * 2, "fmi_attention_bwd_structure": [i32] * 2}
+PREDICATES = {"fmi_debug_bf16_tile": [i32], "fmi_debug_bf16_last_tile": [], "fmi_conv2d_bf16_plan": [PD, i32, i32, i32, i32, vp], "fmi_conv2d_f32_plan": [PD, i32, i32, vp], "fmi_debug_f32_last_plan": [], "fmi_set_deterministic": [i32], "fmi_get_deterministic": [], "fmi_conv2d_thin_supported": [PD], "fmi_conv2d_bf16_supported": [PD], "fmi_conv2d_thin_lrelu_supported": [PD], "fmi_conv2d_thin_lrelu_bwd_ws_bytes": [PD], "fmi_conv2d_thin_in_supported": [PD], "fmi_conv2d_thin_in_routed": [PD], "fmi_conv2d_thin_in_wgrad_ws_bytes": [PD], "fmi_conv2d_pair_supported": [PD, i32], "fmi_conv2d_pair_routed": [PD, i32], "fmi_conv2d_pair_ksplit": [PD, i32, i32], "fmi_conv_transpose2d_pair_bwd_supported": [PD, i32, i32], "fmi_conv_transpose2d_pair_bwd_ws_bytes": [PD, i32, i32], "fmi_attention_fwd_uses_pieces": [i32] * 5, "fmi_attention_bwd_uses_pieces": [i32] * 5, "fmi_attention_fwd_waves": [i32] * 2, "fmi_attention_fwd_bf16_waves": [i32] * 2, "fmi_guided_attention_fwd_bf16_waves": [i32] * 2, "fmi_attention_bwd_structure": [i32] * 2}
 
 
 class FmiError(RuntimeError):

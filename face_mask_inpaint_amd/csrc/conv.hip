@@ -28,14 +28,15 @@ static int check_desc(const fmi_conv_desc* d) {
 }
 
 // the fields the shared builders (gemm_core.h) leave to the family, as the fp32 gathers read them; img = the gathered tensor
-static ConvGeom f32_geom(ConvGeom g, const fmi_conv_desc* d, const float* img) {
+static ConvGeom f32_geom_al(ConvGeom g, const fmi_conv_desc* d, bool img_al16) {
   const int dl = d->dil > 1 ? d->dil : 1;  // dilation = the tap step of the gather (modules/drn.py); adjoint: only with stride 1 (the caller checks)
   g.ystep *= dl; g.xstep *= dl;
-  g.vec = (g.C % 4 == 0) && (g.cstride % 4 == 0) && aligned16(img);  // 1 = four channels are one float4 load
+  g.vec = (g.C % 4 == 0) && (g.cstride % 4 == 0) && img_al16;  // 1 = four channels are one float4 load
   g.dC = make_fastdiv(g.C);                                          // reduction index -> tap
   g.img_bs = (int64_t)g.IH * g.IW * g.cstride;                       // per-sample weight mode: one sample of the image
   return g;
 }
+static ConvGeom f32_geom(ConvGeom g, const fmi_conv_desc* d, const float* img) { return f32_geom_al(g, d, aligned16(img)); }
 
 #ifndef FMI_HOST_EMU
 // y[pixel][k] = bias[k] + bias2[k] + residual[pixel][k] (each may be null): first pass of a split-reduction convolution; bias2 = the second
@@ -53,85 +54,107 @@ __global__ void __launch_bounds__(256) conv_split_init_kernel(float* __restrict_
 }
 #endif
 
-// Small feature maps with deep reductions (the 128-channel residual stacks at 32x32 and below, and the discriminator) give
-// the implicit GEMM only a handful of output tiles: split the (tap, channel) reduction over several workgroups per tile.
-static int conv_ksplit(int64_t M, int N, int K) {
-#ifdef FMI_HOST_EMU
-  return 1;
-#else
-  // keep the 128-wide tiles (operand reuse) and fill the chip by splitting the reduction instead of shrinking the tile
-  const int64_t tiles = ceil_div64(M, 128) * ceil_div64(N, N <= 32 ? 32 : (N <= 64 ? 64 : 128));
-  if (K < 512 || fmi_det()) return 1;  // reproducible mode: no split reduction (partial sums would meet through atomics)
-  if (tiles >= 320) {
-    // between one and two "waves" of workgroups (3 per CU x 256 CUs) the CUs that got 3 tiles set the time while the others idle
-    // (VGG 28^2: 588 tiles = 2.3 per CU): splitting the work unit lets the dispatcher even it out.  Measured (TFLOP/s, split 1 / 2 / 3):
-    // 588 tiles K 4608: 102 / 111 / 118;  588 tiles K 2304: 101 / 107 / 109;  512 tiles K 2304: 111 / 116 / 111;
-    // 1024 tiles K 2304: 125 / 118 / 114;  1176 tiles K 2304: 101 / 97 / 100  ->  no split from ~800 tiles up
-    if (tiles >= 800 || K < 2304) return 1;
-    return tiles <= 520 ? 2 : 3;
+// Every routing decision below is conv_f32_plan.h's: this file gathers the facts a plan reads (ConvCallF, ConvPhaseInF), launches what
+// comes back, and answers fmi_conv2d_f32_plan from the same functions.
+extern "C" int fmi_debug_f32_last_plan(void) { return __atomic_load_n(&fmi_f32_last_plan_code, __ATOMIC_RELAXED); }
+
+// what an entry learns from its pointers and the process.  x: the gathered tensor; w: the second operand (weights; the weight gradient's dy)
+static ConvCallF call_facts(const fmi_conv_desc* d, const void* x, const void* w, const void* out, const void* bias, const void* res,
+                            const void* mask, int act, int batch_w) {
+  ConvCallF c{};
+  c.x_al16 = aligned16(x); c.w_al16 = aligned16(w); c.out_al16 = aligned16(out); c.res_al16 = aligned16(res);
+  c.x3 = d->x3 != nullptr; c.x3_al16 = aligned16(d->x3); c.w3 = d->w3 != nullptr; c.w3_al16 = aligned16(d->w3);
+  c.y3 = d->y3 != nullptr; c.y3_al16 = aligned16(d->y3);
+  c.bias = bias != nullptr; c.res = res != nullptr; c.mask = mask != nullptr;
+  c.act = act; c.batch_w = batch_w;
+  c.det = fmi_det();
+#ifndef FMI_HOST_EMU
+  c.dma_off = fmi_dma_off_env();
+  if (batch_w == 1) {  // every thin exit needs shared weights: the predicates are not asked otherwise
+    c.thin_out = fmi_conv2d_thin_supported(d) != 0;
+    c.thin_in = d->kh == 3 && fmi_conv2d_thin_in_routed(d) != 0;  // only the forward's 3x3 exit reads it (fwd_early_f)
   }
-  // 192 .. 319 tiles: unsplit wins up to K = 2304 (256 tiles: 8 x 64^2 128 -> 128 92 vs 81 TFLOP/s split in two; the IR-SE50 stage
-  // 16 x 32^2 256 -> 256 94.5 vs 89)
-  if (tiles >= 192 && K < 4608) return 1;
-  int64_t ks = ceil_div64(384, tiles);
-  // at least 16 k-tiles per split; a handful of output tiles (M <= 128 rows: the pSp style heads at 4^2 .. 1^2) only stream the
-  // weights, so more, shorter splits put more loads in flight: 4 k-tiles there
-  const int64_t kmin = (M <= 128 && tiles <= 16) ? 64 : 256;
-  if (ks > K / kmin) ks = K / kmin;
-  return ks < 2 ? 1 : (int)(ks > (kmin == 64 ? 64 : 16) ? (kmin == 64 ? 64 : 16) : ks);
+#else  // the emulation has no thin kernels and reads no piece images
+  c.x3 = c.w3 = c.y3 = false;
 #endif
+  return c;
 }
 
-// One output phase: the forward convolution, or one sub-pixel phase of the adjoint (flip = 1: the 3x3 tap-reuse kernels take the
-// flipped taps of the adjoint's weight pack).  g gathers x (g.C channels at pitch g.cstride; x3 = its bf16 piece image or null); w / w3 =
-// the weights packed for this direction and their piece image (null where it cannot be used); ep writes Nout channels.  may_split: the
-// reduction may be split over workgroups, whose partial sums meet through atomics in an output initialised first; shared_init: the caller
-// has initialised the output once for all phases (the adjoint's strided split) and this phase only adds to it.
-static int conv_phase(const fmi_conv_desc* d, const ConvGeom& g, const float* x, const void* x3, const float* w, const void* w3p,
-                      int64_t w_bstride, int Nout, int flip, ConvEp ep, int batch_w, bool may_split, bool shared_init, hipStream_t st) {
-  ConvK la{x, g};
-  ConvWX lb{w, g, w_bstride, Nout, (Nout % 4 == 0) && aligned16(w) && (w_bstride % 4 == 0)};
-  const int ks = may_split ? conv_ksplit(g.Mdim(), Nout, g.Kdim()) : 1;
-#ifndef FMI_HOST_EMU
-  if (shared_init || ks > 1) {
-    if (!shared_init) {
-      const int64_t total = (int64_t)g.N * ep.OHt * ep.OWt * Nout;
-      hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, st, ep.y, ep.bias, (const float*)nullptr, ep.res, Nout, ep.cstride,
-                         total);
+// the plan's inputs of one output phase: the forward convolution, or one sub-pixel phase of the adjoint.  g gathers the image (g.C channels
+// at pitch g.cstride); w3: the weights' piece image can be used (weight_pieces_f); w_vec: ConvWX's float4 loads are legal
+static ConvPhaseInF phase_in(const fmi_conv_desc* d, const ConvGeom& g, int Nout, const ConvCallF& c, bool w3, bool w_vec, bool may_split,
+                             bool shared_init) {
+  ConvPhaseInF in{};
+  in.M = g.Mdim(); in.Nout = Nout; in.Kdim = g.Kdim(); in.C = g.C; in.cstride = g.cstride;
+  in.pixels = (int64_t)g.N * g.IH * g.IW;
+  in.pad_mode = g.pad_mode;
+  in.tap3 = d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->dil <= 1 && g.pad_mode == 0;
+  in.batch_w = c.batch_w;
+  in.x3 = c.x3 && c.x3_al16; in.w3 = w3;
+  in.x_al16 = c.x_al16; in.w_al16 = c.w_al16;
+  in.la_dma = ConvK{nullptr, g}.dma_ok();
+  in.lb_dma = ConvWX{nullptr, g, 0, Nout, w_vec}.dma_ok();
+  in.may_split = may_split; in.shared_init = shared_init;
+  in.det = c.det; in.dma_off = c.dma_off;
+  return in;
+}
+static bool w_vec_of(const ConvCallF& c, int Nout, int64_t w_bstride) { return (Nout % 4 == 0) && c.w_al16 && (w_bstride % 4 == 0); }
+// bf16 piece images of the weights (fmi_weight_prepare_f32 writes them): forward [3][taps][C / 8][K][8], adjoint [3][taps][K / 8][C][8]
+static ConvPhaseInF fwd_phase_in(const fmi_conv_desc* d, const ConvGeom& g, const ConvCallF& c, bool w_vec) {
+  return phase_in(d, g, d->K, c, weight_pieces_f(c.w3 && c.w3_al16, c.batch_w, d->C), w_vec, c.act == 0 && c.batch_w == 1, false);
+}
+static ConvPhaseInF adj_phase_in(const fmi_conv_desc* d, const ConvGeom& g, const ConvCallF& c, bool w_vec, bool strided_split) {
+  return phase_in(d, g, d->C, c, weight_pieces_f(c.w3 && c.w3_al16, c.batch_w, d->K), w_vec, dgrad_may_split_f(d, c, strided_split), strided_split);
+}
+// does any sub-pixel phase of a strided adjoint want a split reduction (dgrad_phase_wants_split_f)?
+static bool adj_strided_split(const fmi_conv_desc* d, const ConvCallF& c, int n_eff) {
+  if (d->stride == 1 || c.batch_w != 1) return false;  // dgrad_phase_wants_split_f's first two terms: no geometry is built for them
+  for (int py = 0; py < d->stride; ++py)
+    for (int px = 0; px < d->stride; ++px) {
+      const ConvGeom g = adj_geom(d, n_eff, py, px);
+      if (dgrad_phase_wants_split_f(d, c, g.GH, g.GW, g.Mdim(), g.Kdim())) return true;
     }
+  return false;
+}
+
+// One output phase (flip = 1: the 3x3 tap-reuse kernels take the flipped taps of the adjoint's weight pack).  x3 = the piece image of the
+// gathered tensor; w / w3 = the weights packed for this direction and their piece image; ep writes in.Nout channels.
+static int conv_phase(const fmi_conv_desc* d, const ConvGeom& g, const ConvPhaseInF& in, const float* x, const void* x3, const float* w,
+                      const void* w3p, int64_t w_bstride, bool w_vec, int flip, ConvEp ep, hipStream_t st) {
+  const int Nout = in.Nout;
+  ConvK la{x, g};
+  ConvWX lb{w, g, w_bstride, Nout, w_vec};
+#ifdef FMI_HOST_EMU  // every convolution through the emulated launch_gemm, unsplit
+  (void)d; (void)x3; (void)w3p; (void)flip;
+  return launch_gemm(la, lb, ep, in.M, Nout, in.Kdim, in.batch_w, 1, st);
+#else
+  const LaunchPlanF pl = conv_phase_plan_f(in);
+  if (pl.init) {
+    const int64_t total = (int64_t)g.N * ep.OHt * ep.OWt * Nout;
+    hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, st, ep.y, ep.bias, (const float*)nullptr, ep.res, Nout, ep.cstride,
+                       total);
+  }
+  if (phase_adds_f(in, pl)) {
     ep.bias = nullptr;
     ep.res = nullptr;
     ep.act = 3;
     ep.vec = 0;
   }
-  const uint16_t* w3 = (const uint16_t*)w3p;
+  const uint16_t* w3 = in.w3 ? (const uint16_t*)w3p : nullptr;
   const int64_t w3_stride = (int64_t)d->kh * d->kw * d->C * d->K;
-  const int64_t pixels = (int64_t)g.N * g.IH * g.IW;
-  const bool tap3 = d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->dil <= 1 && g.pad_mode == 0;
-  // both operands as bf16 piece images (conv_p3.h): the activation pieces of x came from x's producer
-  const bool p3 = batch_w == 1 && g.cstride == g.C && g.Kdim() > 0 && p3_generic_ok(g, x3, w3, Nout);
-  if (p3 && tap3 && conv3x3_p3_eligible(x3, w3, g.C, Nout, pixels)) {
-    const C3P3Args ca{(const uint16_t*)x3, w3, g.N, g.IH, g.IW, g.C, Nout, flip, make_fastdiv(g.IW), make_fastdiv(g.IH * g.IW)};
-    return launch_conv3x3_p3(ca, ep, g.Mdim(), ks, st);
+  switch (pl.route) {
+    case ROUTE_C3_P3_F:
+      return launch_conv3x3_p3(C3P3Args{(const uint16_t*)x3, w3, g.N, g.IH, g.IW, g.C, Nout, flip, make_fastdiv(g.IW), make_fastdiv(g.IH * g.IW)}, ep, in.M, pl, st);
+    case ROUTE_GEMM_P3_F:
+      return launch_gemm_p3(ConvK3{(const uint16_t*)x3, g, make_fastdiv(g.ntaps())}, ConvWX3{w3, g, w3_stride, Nout}, ep, in.M, Nout, in.Kdim, pl, st);
+    case ROUTE_C3_F:
+    case ROUTE_C3_W3_F:
+      return launch_conv3x3(C3Args{x, w, g.N, g.IH, g.IW, g.C, g.cstride, Nout, flip, make_fastdiv(g.IW), make_fastdiv(g.IH * g.IW), w3}, ep, in.M, pl, st);
+    case ROUTE_GEMM_W3_F: return launch_gemm_plan(la, ConvWX3{w3, g, w3_stride, Nout}, ep, in.M, Nout, in.Kdim, 1, pl, st);
+    case ROUTE_GEMM_F: return launch_gemm_plan(la, lb, ep, in.M, Nout, in.Kdim, in.batch_w, pl, st);
   }
-  if (p3)
-    return launch_gemm_p3(ConvK3{(const uint16_t*)x3, g, make_fastdiv(g.ntaps())}, ConvWX3{w3, g, w3_stride, Nout}, ep, g.Mdim(), Nout,
-                          g.Kdim(), ks, st);
-  if (batch_w == 1 && tap3 && conv3x3_eligible(x, w, g.C, g.cstride, Nout, pixels)) {
-    const C3Args ca{x, w, g.N, g.IH, g.IW, g.C, g.cstride, Nout, flip, make_fastdiv(g.IW), make_fastdiv(g.IH * g.IW), w3};
-    return launch_conv3x3(ca, ep, g.Mdim(), ks, st);
-  }
-  if (w3 && la.dma_ok()) return launch_gemm(la, ConvWX3{w3, g, w3_stride, Nout}, ep, g.Mdim(), Nout, g.Kdim(), 1, ks, st);
+  return pl.status ? pl.status : FMI_ERR_BAD_ARG;
 #endif
-  return launch_gemm(la, lb, ep, g.Mdim(), Nout, g.Kdim(), batch_w, ks, st);
-}
-
-// d->w3, the bf16 piece image of the weights, where the kernels can read it: shared weights, 16-channel groups of the reduction
-static const void* weight_pieces(const fmi_conv_desc* d, int batch_w, int red_c) {
-#ifndef FMI_HOST_EMU
-  if (batch_w == 1 && red_c % 16 == 0 && aligned16(d->w3)) return d->w3;
-#endif
-  return nullptr;
 }
 
 static int check_y3(const fmi_conv_desc* d, int out_c, int out_cs) {
@@ -155,20 +178,18 @@ extern "C" int fmi_conv2d_fwd_f32(const fmi_conv_desc* d, const float* x, const 
 #endif
     return rc;
   };
+  const ConvCallF c = call_facts(d, x, wf, y, bias, residual, nullptr, act, batch_w);
 #ifndef FMI_HOST_EMU
-  if (batch_w == 1 && fmi_conv2d_thin_supported(d) && aligned16(x))
-    return finish(fmi_conv2d_thin_fwd_f32(d, x, wf, bias, residual, y, act, stream));
-  // thin INPUT (C <= 4: the image-facing first layers), 3x3 on a large map: streaming FMA kernel (thinin.hip).  The 1x1 form is a 9 - 13 us
-  // launch either way and did not clear the keep-only-if-faster rule (profiles/thin_in.txt): it stays on the generic path
-  if (batch_w == 1 && d->kh == 3 && fmi_conv2d_thin_in_routed(d) && aligned16(y) && aligned16(residual))
-    return finish(fmi_conv2d_thin_in_fwd_f32(d, x, wf, bias, residual, y, act, stream));
+  switch (fwd_early_f(d, c)) {
+    case ROUTE_THIN_OUT_F: return finish(fmi_conv2d_thin_fwd_f32(d, x, wf, bias, residual, y, act, stream));
+    case ROUTE_THIN_IN_F: return finish(fmi_conv2d_thin_in_fwd_f32(d, x, wf, bias, residual, y, act, stream));
+  }
 #endif
   const ConvGeom g = f32_geom(fwd_geom(d, batch_w > 1 ? 1 : d->N), d, x);
-  // bf16 piece images of the weights (fmi_weight_prepare_f32 writes them): [3][taps][C / 8][K][8]
-  const void* w3 = weight_pieces(d, batch_w, d->C);
+  const bool w_vec = w_vec_of(c, d->K, w_bstride);
   ConvEp ep{y, bias, residual, d->OH, d->OW, 1, 0, 0, d->OH, d->OW, d->y_cstride, act, g.dGW, g.dG, (int64_t)d->OH * d->OW * d->y_cstride};
   ep.vec = ep_vec(ep, d->K);
-  return finish(conv_phase(d, g, x, d->x3, wf, w3, w_bstride, d->K, 0, ep, batch_w, act == 0 && batch_w == 1, false, (hipStream_t)stream));
+  return finish(conv_phase(d, g, fwd_phase_in(d, g, c, w_vec), x, d->x3, wf, d->w3, w_bstride, w_vec, 0, ep, (hipStream_t)stream));
 }
 
 static int dgrad_impl(const fmi_conv_desc* d, const float* dy, const float* wt, const float* bias, const float* residual,
@@ -188,50 +209,38 @@ static int dgrad_impl(const fmi_conv_desc* d, const float* dy, const float* wt, 
 #endif
     return rc;
   };
+  const ConvCallF c = call_facts(d, dy, wt, dx, bias, residual, mask, 0, batch_w);
 #ifndef FMI_HOST_EMU
-  if (batch_w == 1 && !bias && !residual && !mask && fmi_conv2d_thin_supported(d) && aligned16(dx))
-    return finish(fmi_conv2d_thin_dgrad_f32(d, dy, wt, dx, stream));
-  // thin INPUT: VGG16's first layer (the entry's 1x1 form is not routed here: see the forward)
-  if (batch_w == 1 && !bias && !residual && !mask && d->C <= 4 && d->x_cstride == d->C && d->kh == 3) {
+  if (dgrad_thin_out_f(c)) return finish(fmi_conv2d_thin_dgrad_f32(d, dy, wt, dx, stream));
+  if (dgrad_thin_in_tried_f(d, c)) {
     const int rc_thin = fmi_conv2d_thin_input_dgrad_f32(d, dy, wt, dx, stream);
     if (rc_thin != FMI_ERR_UNSUPPORTED) return finish(rc_thin);
   }
 #endif
   const int n_eff = batch_w > 1 ? 1 : d->N;
   const int s = d->stride;
-  // bf16 piece images of the adjoint's weights: [3][taps][K / 8][C][8]
-  const void* w3 = weight_pieces(d, batch_w, d->K);
   if (d->dil > 1 && s != 1) return FMI_ERR_UNSUPPORTED;  // adjoint of a dilated AND strided convolution: not needed by modules/drn.py
   bool strided_split = false;
 #ifndef FMI_HOST_EMU
-  // Strided adjoints of small feature maps (the stride-2 style heads of the pSp encoder: 512 -> 512 at 16^2 .. 2^2) are a few
-  // output tiles per sub-pixel phase with up to 128 reduction tiles each -- 0.25 ms of pure load latency per call.  If any phase
-  // wants a split reduction, dx is initialised once and EVERY phase adds its (partial) sums atomically.
-  if (s > 1 && batch_w == 1) {
-    for (int py = 0; py < s && !strided_split; ++py)
-      for (int px = 0; px < s && !strided_split; ++px) {
-        const ConvGeom g = adj_geom(d, n_eff, py, px);
-        if (g.GH > 0 && g.GW > 0 && conv_ksplit(g.Mdim(), d->C, g.Kdim()) > 1) strided_split = true;
-      }
-    if (strided_split) {
-      const int64_t total = (int64_t)d->N * d->H * d->W * d->C;
-      hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, dx, bias, (const float*)nullptr, residual, d->C,
-                         d->x_cstride, total);
-    }
+  strided_split = adj_strided_split(d, c, n_eff);
+  if (strided_split) {  // dx is initialised once and EVERY phase adds its (partial) sums atomically
+    const int64_t total = (int64_t)d->N * d->H * d->W * d->C;
+    hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, dx, bias, (const float*)nullptr, residual, d->C,
+                       d->x_cstride, total);
   }
-  // thin ConvTranspose2d(3, stride 2) on a large map: all four sub-pixel phases in one tap-reuse launch (convt3x3.h)
-  if (batch_w == 1 && !strided_split && !d->x3 && convt3x3_eligible(d, dy, (const uint16_t*)w3)) {
+  if (dgrad_convt3x3_f(d, c, strided_split)) {
     CT3Args ca{};
-    ca.x = dy; ca.w3 = (const uint16_t*)w3; ca.N = d->N; ca.H = d->OH; ca.W = d->OW; ca.Cred = d->K; ca.cs = d->y_cstride; ca.Nout = d->C;
+    ca.x = dy; ca.w3 = (const uint16_t*)d->w3; ca.N = d->N; ca.H = d->OH; ca.W = d->OW; ca.Cred = d->K; ca.cs = d->y_cstride; ca.Nout = d->C;
     ca.dW = make_fastdiv(d->OW); ca.dHW = make_fastdiv(d->OH * d->OW);
     ConvEp ep{dx, bias, residual, d->OH, d->OW, 2, 0, 0, d->H, d->W, d->x_cstride, 0, ca.dW, ca.dHW, (int64_t)d->H * d->W * d->x_cstride};
     ep.mask = mask;
     ep.mslope = mslope;
     ep.vec = ep_vec(ep, d->C);
     ca.ep = ep;
-    return finish(launch_convt3x3(ca, d->N * d->OH * d->OW, (hipStream_t)stream));
+    return finish(launch_convt3x3(ca, d->N * d->OH * d->OW, convt3x3_plan_f(d->N * d->OH * d->OW, d->C), (hipStream_t)stream));
   }
 #endif
+  const bool w_vec = w_vec_of(c, d->C, w_bstride);
   for (int py = 0; py < s; ++py) {
     for (int px = 0; px < s; ++px) {
       const ConvGeom g = f32_geom(adj_geom(d, n_eff, py, px), d, dy);
@@ -241,8 +250,7 @@ static int dgrad_impl(const fmi_conv_desc* d, const float* dy, const float* wt, 
       ep.mask = mask;
       ep.mslope = mslope;
       ep.vec = ep_vec(ep, d->C);
-      rc = conv_phase(d, g, dy, d->x3, wt, w3, w_bstride, d->C, 1, ep, batch_w, batch_w == 1 && (s == 1 || strided_split), strided_split,
-                      (hipStream_t)stream);
+      rc = conv_phase(d, g, adj_phase_in(d, g, c, w_vec, strided_split), dy, d->x3, wt, d->w3, w_bstride, w_vec, 1, ep, (hipStream_t)stream);
       if (rc) return rc;
     }
   }
@@ -262,8 +270,8 @@ extern "C" int fmi_conv_transpose2d_pair_f32(const fmi_conv_desc* d, const float
   if (rc) return rc;
   if (!x1 || !x2 || !w3b || !d->w3 || !y || K2 <= 0) return FMI_ERR_BAD_ARG;
 #ifndef FMI_HOST_EMU
-  const uint16_t* w3 = (d->K % 16 == 0 && aligned16(d->w3)) ? (const uint16_t*)d->w3 : nullptr;
-  if (!convt3x3_eligible(d, x1, w3) || (K2 & 15) || !aligned16(x2) || !aligned16(w3b) || d->pad_mode != 0 || d->x3) return FMI_ERR_UNSUPPORTED;
+  const uint16_t* w3 = (const uint16_t*)d->w3;
+  if (!convt3x3_eligible_f(d, aligned16(x1), weight_pieces_f(aligned16(d->w3), 1, d->K)) || (K2 & 15) || !aligned16(x2) || !aligned16(w3b) || d->pad_mode != 0 || d->x3) return FMI_ERR_UNSUPPORTED;
   CT3Args ca{};
   ca.x = x1; ca.w3 = w3; ca.x2 = x2; ca.w3b = (const uint16_t*)w3b; ca.Cred2 = K2; ca.cs2 = K2;
   ca.N = d->N; ca.H = d->OH; ca.W = d->OW; ca.Cred = d->K; ca.cs = d->y_cstride; ca.Nout = d->C;
@@ -271,7 +279,7 @@ extern "C" int fmi_conv_transpose2d_pair_f32(const fmi_conv_desc* d, const float
   ConvEp ep{y, bias, nullptr, d->OH, d->OW, 2, 0, 0, d->H, d->W, d->x_cstride, 0, ca.dW, ca.dHW, (int64_t)d->H * d->W * d->x_cstride};
   ep.vec = ep_vec(ep, d->C);
   ca.ep = ep;
-  return launch_convt3x3(ca, d->N * d->OH * d->OW, (hipStream_t)stream);
+  return launch_convt3x3(ca, d->N * d->OH * d->OW, convt3x3_plan_f(d->N * d->OH * d->OW, d->C), (hipStream_t)stream);
 #else
   return FMI_ERR_UNSUPPORTED;
 #endif
@@ -294,35 +302,28 @@ extern "C" int fmi_conv2d_wgrad_f32(const fmi_conv_desc* d, const float* x, cons
   if (rc) return rc;
   if (!x || !dy || !dwf || batch_w < 1) return FMI_ERR_BAD_ARG;
   if (batch_w > 1 && batch_w != d->N) return FMI_ERR_BAD_ARG;
+  const ConvCallF c = call_facts(d, x, dy, dwf, dbias, nullptr, nullptr, 0, batch_w);
 #ifndef FMI_HOST_EMU
-  if (batch_w == 1 && fmi_conv2d_thin_supported(d) && aligned16(x)) return fmi_conv2d_thin_wgrad_f32(d, x, dy, dwf, dbias, stream);
-#endif
-#ifndef FMI_HOST_EMU
-  // both operands as bf16 piece images (d->x3 = pieces of x, d->y3 = pieces of dy, INPUTS here): no split arithmetic, transposed LDS reads.
-  // The bias gradient does not ride along on this path (the caller runs fmi_bias_grad_f32).
-  if (batch_w == 1 && !dbias && wgrad_p3_ok(d, d->x3, d->y3))
-    return launch_wgrad_p3(d, (const uint16_t*)d->x3, (const uint16_t*)d->y3, dwf, (hipStream_t)stream);
+  if (wgrad_thin_out_f(c)) return fmi_conv2d_thin_wgrad_f32(d, x, dy, dwf, dbias, stream);
 #endif
   const int n_eff = batch_w > 1 ? 1 : d->N;
   ConvGeom g = f32_geom(fwd_geom(d, n_eff), d, x);
-  // the bias gradient rides along as one extra output row (needs a float4-aligned row index and shared weights)
-  const bool fuse_bias = dbias && batch_w == 1 && (g.Kdim() % 4 == 0);
-  if (dbias && !fuse_bias) return FMI_ERR_UNSUPPORTED;
-  const int ones_row = fuse_bias ? g.Kdim() : -1;
-  const int Mg = g.Kdim() + (fuse_bias ? 1 : 0), Ng = d->K, Kg = g.Mdim();
+  const bool dy_vec = (d->K % 4 == 0) && (d->y_cstride % 4 == 0) && c.w_al16;
+  const WgradPlanF w = wgrad_plan_f(d, c, g.Kdim(), g.Mdim(), g.vec != 0, dy_vec);
+  if (w.pl.status) return w.pl.status;
+#ifndef FMI_HOST_EMU
+  if (w.pl.route != ROUTE_WGRAD_GEMM_F) return launch_wgrad_p3(d, (const uint16_t*)d->x3, (const uint16_t*)d->y3, dwf, w.pl, (hipStream_t)stream);
+#endif
+  const int ones_row = w.fuse_bias ? g.Kdim() : -1;
+  const int Mg = g.Kdim() + (w.fuse_bias ? 1 : 0), Ng = d->K, Kg = g.Mdim();
   WgradAX la{x, g, ones_row};
-  DenseX lb{dy, (int64_t)d->y_cstride, (int64_t)d->OH * d->OW * d->y_cstride, Ng, Kg,
-            (d->K % 4 == 0) && (d->y_cstride % 4 == 0) && aligned16(dy)};
+  DenseX lb{dy, (int64_t)d->y_cstride, (int64_t)d->OH * d->OW * d->y_cstride, Ng, Kg, dy_vec};
   WgradEp ep{dwf, g, d->K, w_bstride, dbias, ones_row};
-  // split the (long) pixel reduction over workgroups; partial sums meet through fp32 atomics
-  const int64_t tiles = ceil_div64(Mg, 128) * ceil_div64(Ng, Ng <= 32 ? 32 : (Ng <= 64 ? 64 : 128));
-  int64_t ksplit = 2048 / (tiles * batch_w);
-  const int64_t kmax = Kg / 512;
-  if (ksplit > kmax) ksplit = kmax;
-  if (ksplit < 1) ksplit = 1;
-  if (fmi_det()) ksplit = 1;  // reproducible mode: one workgroup per tile walks the whole pixel reduction
-  if (ksplit * batch_w > 65535) ksplit = 65535 / batch_w;
-  return launch_gemm(la, lb, ep, Mg, Ng, Kg, batch_w, (int)ksplit, (hipStream_t)stream);
+#ifndef FMI_HOST_EMU
+  return launch_gemm_plan(la, lb, ep, Mg, Ng, Kg, batch_w, w.pl, (hipStream_t)stream);
+#else
+  return launch_gemm(la, lb, ep, Mg, Ng, Kg, batch_w, 1, (hipStream_t)stream);
+#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -331,52 +332,39 @@ extern "C" int fmi_conv2d_wgrad_f32(const fmi_conv_desc* d, const float* x, cons
 // forward pack or null); x2 is dense [N][H][W][C2].
 // ---------------------------------------------------------------------------------------------
 static int pair_check(const fmi_conv_desc* d, int C2) {
-  int rc = check_desc(d);
-  if (rc) return rc;
-  if (C2 <= 0) return FMI_ERR_BAD_ARG;
-  if (d->kh != 3 || d->kw != 3 || d->stride != 1 || d->pad != 1 || d->pad_mode != 0 || d->dil > 1) return FMI_ERR_UNSUPPORTED;
-  if ((d->C & 15) || (C2 & 15) || (d->K & 3) || d->x_cstride != d->C || d->y_cstride != d->K) return FMI_ERR_UNSUPPORTED;
-  if (9ll * d->C + C2 > 0x3fffffffLL || (int64_t)d->N * d->H * d->W >= (1ll << 30)) return FMI_ERR_UNSUPPORTED;
-  return FMI_OK;
+  const int rc = check_desc(d);
+  return rc ? rc : pair_shape_check_f(d, C2);
 }
-// reduction splits of the pair's forward, as the launch takes them (1: unsplit)
-static int pair_ksplit(const fmi_conv_desc* d, int C2, int act, bool tap_reuse) {
-  const int M = d->N * d->H * d->W, Kd = 9 * d->C + C2;
-  int ks = act == 0 ? conv_ksplit(M, d->K, Kd) : 1;
-  if (tap_reuse) {  // launch_conv3x3: whole (ky, 16 channels) steps per split
-    const int nit = 3 * (d->C >> 4) + (C2 >> 4);
-    if (ks > nit) ks = nit;
-    const int it_chunk = (nit + ks - 1) / ks;
-    return (nit + it_chunk - 1) / it_chunk;
-  }
-  const int kchunk = (int)ceil_div64(ceil_div64(Kd, ks), 16) * 16;  // launch_gemm: 16-deep tiles per split
-  return (int)ceil_div64(Kd, kchunk);
-}
-static bool pair_tap_reuse(const fmi_conv_desc* d) {
-#ifndef FMI_HOST_EMU
-  return (d->C >= 64 || d->K <= 32);  // conv3x3_eligible's channel rule; alignment is checked at the call
+#ifdef FMI_HOST_EMU  // the emulation runs the pair on the plain GEMM loop, unsplit
+static bool pair_tap_reuse(const fmi_conv_desc*) { return false; }
+static int pair_ksplit(const fmi_conv_desc*, int, int, bool) { return 1; }
 #else
-  return false;
+static bool pair_tap_reuse(const fmi_conv_desc* d) { return pair_tap_reuse_f(d); }
+static int pair_ksplit(const fmi_conv_desc* d, int C2, int act, bool tap_reuse) { return pair_ksplit_f(d, C2, act, tap_reuse, fmi_det()); }
 #endif
-}
 extern "C" int fmi_conv2d_pair_supported(const fmi_conv_desc* d, int C2) { return d && pair_check(d, C2) == FMI_OK; }
 extern "C" int fmi_conv2d_pair_ksplit(const fmi_conv_desc* d, int C2, int act) {
   if (!d || pair_check(d, C2) != FMI_OK) return 0;
   return pair_ksplit(d, C2, act, pair_tap_reuse(d));
 }
-// Which passes of a supported shape the ResBlock routes here: bit 0 the forward, bit 1 the weight gradient.  A pass is routed only where the
-// fused launch was faster than conv2 + bypass in EVERY alternated round of tools/bench_tools/resblock_pair_time.py
-// (profiles/resblock_pair.txt): the weight gradient at every measured shape (8 x 8^2 .. 8 x 128^2); the forward at all of them but
-// 8 x 32^2 128 -> 128, a tie (39.6 against 39.5 us, lower in 2 rounds of 5).  Where conv2 runs from piece images of x1 today
-// (functional.p3_wanted: >= 16384 pixels, C >= 64, K >= 128) only the measured shape, 8 x 64^2 64 -> 128, is routed.  Below 32 channels
-// (nothing measured: the step has no such block) the two launches stay.
-extern "C" int fmi_conv2d_pair_routed(const fmi_conv_desc* d, int C2) {
-  if (!fmi_conv2d_pair_supported(d, C2) || d->C < 32) return 0;
-  const int64_t px = (int64_t)d->N * d->H * d->W;
-  if (px >= 16384 && d->C >= 64 && d->K >= 128) return (d->C == 64 && d->K == 128 && px <= 32768) ? 3 : 0;
-  const bool fwd_tie = d->C == 128 && d->K == 128 && px > 2048 && px < 16384;
-  return fwd_tie ? 2 : 3;
+// The pair's two launches as plans, shared by the entries and by fmi_conv2d_f32_plan.  dma_ok: both loaders stage through LDS-DMA -- true
+// for every call the entries accept (they refuse a misaligned operand, and pair_check leaves C, C2 % 16 == 0 and K % 4 == 0).  The pair's
+// loaders are not ConvK / WgradAX, so FMI_DMA_OFF reads them under its dense bit (gemm_family_f).
+static LaunchPlanF pair_fwd_plan(const fmi_conv_desc* d, int C2, int act, bool w3_both, bool dma_ok, bool det, int dma_off) {
+  const int M = d->N * d->H * d->W, Kd = 9 * d->C + C2;
+  const bool tap_reuse = pair_tap_reuse_f(d);
+  const int ks = pair_ksplit_f(d, C2, act, tap_reuse, det);
+  LaunchPlanF pl = tap_reuse ? c3_plan_f(M, d->K, 3 * (d->C >> 4) + (C2 >> 4), ks, w3_both, det)
+                             : gemm_plan_f(w3_both ? ROUTE_GEMM_W3_F : ROUTE_GEMM_F, M, d->K, Kd, 1, ks, dma_ok, DMA_FAMILY_DENSE_F, dma_off, det);
+  pl.init = ks > 1;  // y = b1 + b2 first; the partial sums meet in it through atomics
+  return pl;
 }
+static LaunchPlanF pair_wgrad_plan(const fmi_conv_desc* d, int C2, bool bias, bool dma_ok, bool det, int dma_off) {
+  const int Mg = 9 * d->C + C2 + (bias ? 1 : 0), P = d->N * d->H * d->W;
+  return gemm_plan_f(ROUTE_WGRAD_GEMM_F, Mg, d->K, P, 1, (int)pair_wgrad_split_f(Mg, d->K, P, det), dma_ok, DMA_FAMILY_DENSE_F, dma_off, det);
+}
+// which passes of a supported shape the ResBlock routes here (pair_routed_f): bit 0 the forward, bit 1 the weight gradient
+extern "C" int fmi_conv2d_pair_routed(const fmi_conv_desc* d, int C2) { return fmi_conv2d_pair_supported(d, C2) ? pair_routed_f(d) : 0; }
 
 extern "C" int fmi_conv2d_pair_fwd_f32(const fmi_conv_desc* d, const float* x1, const float* x2, int C2, const float* wf1, const float* wf2,
                                        const void* w3b, const float* b1, const float* b2, float* y, int act, void* stream) {
@@ -392,11 +380,16 @@ extern "C" int fmi_conv2d_pair_fwd_f32(const fmi_conv_desc* d, const float* x1, 
   static_cast<ConvEp&>(ep) = ConvEp{y, b1, nullptr, d->OH, d->OW, 1, 0, 0, d->OH, d->OW, d->y_cstride, act, g.dGW, g.dG, (int64_t)d->OH * d->OW * d->y_cstride};
   ep.bias2 = b2;
   ep.vec = ep_vec(ep, d->K);
-  const bool tap_reuse = pair_tap_reuse(d);
-  const int ks = pair_ksplit(d, C2, act, tap_reuse);
 #ifndef FMI_HOST_EMU
   hipStream_t st = (hipStream_t)stream;
-  if (ks > 1) {  // y = b1 + b2 first; the partial sums meet in it through atomics
+  const uint16_t* w3 = weight_pieces_f(aligned16(d->w3), 1, d->C) ? (const uint16_t*)d->w3 : nullptr;
+  const uint16_t* w32 = aligned16(w3b) ? (const uint16_t*)w3b : nullptr;
+  if (!w3 || !w32) w3 = w32 = nullptr;  // the piece images of BOTH packs, or the fp32 packs
+  const ConvK2 la{ConvK{x1, g}, x2, C2, C2, K1};
+  const ConvWX32 lb3{ConvWX3{w3, g, 9ll * d->C * d->K, d->K}, w32, C2, K1};
+  const ConvWX2 lb{ConvWX{wf1, g, 0, d->K, 1}, wf2, C2, K1};
+  const LaunchPlanF pl = pair_fwd_plan(d, C2, act, w3 != nullptr, la.dma_ok() && (w3 ? lb3.dma_ok() : lb.dma_ok()), fmi_det(), fmi_dma_off_env());
+  if (pl.init) {
     const int64_t total = (int64_t)M * d->K;
     hipLaunchKernelGGL(conv_split_init_kernel, dim3(fmi_bw_grid(total, 256)), dim3(256), 0, st, y, b1, b2, (const float*)nullptr, d->K, d->y_cstride, total);
     ep.bias = nullptr;
@@ -404,24 +397,17 @@ extern "C" int fmi_conv2d_pair_fwd_f32(const fmi_conv_desc* d, const float* x1, 
     ep.act = 3;
     ep.vec = 0;
   }
-  const uint16_t* w3 = (const uint16_t*)weight_pieces(d, 1, d->C);
-  const uint16_t* w32 = aligned16(w3b) ? (const uint16_t*)w3b : nullptr;
-  if (!w3 || !w32) w3 = w32 = nullptr;  // the piece images of BOTH packs, or the fp32 packs
-  if (tap_reuse) {
+  if (pl.route == ROUTE_C3_F || pl.route == ROUTE_C3_W3_F) {
     C3Args2 ca;
     static_cast<C3Args&>(ca) = C3Args{x1, wf1, g.N, g.IH, g.IW, g.C, g.cstride, d->K, 0, make_fastdiv(g.IW), make_fastdiv(g.IH * g.IW), w3};
     ca.x2 = x2; ca.w2 = wf2; ca.w3b = w32; ca.C2 = C2; ca.cs2 = C2;
-    return launch_conv3x3(ca, ep, M, ks, st);
+    return launch_conv3x3(ca, ep, M, pl, st);
   }
-  const ConvK2 la{ConvK{x1, g}, x2, C2, C2, K1};
-  if (w3) {
-    const int64_t w3_stride = 9ll * d->C * d->K;
-    return launch_gemm(la, ConvWX32{ConvWX3{w3, g, w3_stride, d->K}, w32, C2, K1}, ep, M, d->K, Kd, 1, ks, st);
-  }
-  return launch_gemm(la, ConvWX2{ConvWX{wf1, g, 0, d->K, 1}, wf2, C2, K1}, ep, M, d->K, Kd, 1, ks, st);
+  if (w3) return launch_gemm_plan(la, lb3, ep, M, d->K, Kd, 1, pl, st);
+  return launch_gemm_plan(la, lb, ep, M, d->K, Kd, 1, pl, st);
 #else
   (void)w3b;
-  return launch_gemm(ConvK2{ConvK{x1, g}, x2, C2, C2, K1}, ConvWX2{ConvWX{wf1, g, 0, d->K, 1}, wf2, C2, K1}, ep, M, d->K, Kd, 1, ks, (hipStream_t)stream);
+  return launch_gemm(ConvK2{ConvK{x1, g}, x2, C2, C2, K1}, ConvWX2{ConvWX{wf1, g, 0, d->K, 1}, wf2, C2, K1}, ep, M, d->K, Kd, 1, 1, (hipStream_t)stream);
 #endif
 }
 
@@ -439,15 +425,102 @@ extern "C" int fmi_conv2d_pair_wgrad_f32(const fmi_conv_desc* d, const float* x1
   const WgradAX2 la{WgradAX{x1, g, -1}, x2, C2, C2, R1, ones_row};
   const DenseX lb{dy, (int64_t)d->y_cstride, (int64_t)d->OH * d->OW * d->y_cstride, Ng, Kg, 1};
   const WgradEp2 ep{WgradEp{dw1, g, d->K, 0, dbias, ones_row}, dw2, R1};
-  // the pixel split of fmi_conv2d_wgrad_f32, over the taller row range
-  const int64_t tiles = ceil_div64(Mg, 128) * ceil_div64(Ng, Ng <= 32 ? 32 : (Ng <= 64 ? 64 : 128));
-  int64_t ksplit = 2048 / tiles;
-  const int64_t kmax = Kg / 512;
-  if (ksplit > kmax) ksplit = kmax;
-  if (ksplit < 1) ksplit = 1;
-  if (fmi_det()) ksplit = 1;
-  if (ksplit > 65535) ksplit = 65535;
-  return launch_gemm(la, lb, ep, Mg, Ng, Kg, 1, (int)ksplit, (hipStream_t)stream);
+#ifndef FMI_HOST_EMU
+  return launch_gemm_plan(la, lb, ep, Mg, Ng, Kg, 1, pair_wgrad_plan(d, C2, dbias != nullptr, la.dma_ok() && lb.dma_ok(), fmi_det(), fmi_dma_off_env()), (hipStream_t)stream);
+#else
+  return launch_gemm(la, lb, ep, Mg, Ng, Kg, 1, 1, (hipStream_t)stream);
+#endif
+}
+
+// ---------------------------------------------------------------------------------------------
+// fmi_conv2d_f32_plan: what the entries above would launch, from the functions they decide with, without a launch (include/fmi_hip.h)
+// ---------------------------------------------------------------------------------------------
+static ConvCallF call_facts_of_flags(const fmi_conv_desc* d, int flags) {
+  ConvCallF c{};
+  c.x_al16 = flags & FMI_F32_PLAN_X_AL16; c.w_al16 = flags & FMI_F32_PLAN_W_AL16; c.out_al16 = flags & FMI_F32_PLAN_OUT_AL16;
+  c.res = flags & FMI_F32_PLAN_RES; c.res_al16 = !c.res || (flags & FMI_F32_PLAN_RES_AL16);
+  c.x3 = flags & FMI_F32_PLAN_X3; c.x3_al16 = !c.x3 || (flags & FMI_F32_PLAN_X3_AL16);
+  c.w3 = flags & FMI_F32_PLAN_W3; c.w3_al16 = !c.w3 || (flags & FMI_F32_PLAN_W3_AL16);
+  c.y3 = flags & FMI_F32_PLAN_Y3; c.y3_al16 = !c.y3 || (flags & FMI_F32_PLAN_Y3_AL16);
+  c.bias = flags & FMI_F32_PLAN_BIAS; c.mask = flags & FMI_F32_PLAN_MASK;
+  c.act = flags & FMI_F32_PLAN_ACT ? 1 : 0;
+  c.batch_w = flags & FMI_F32_PLAN_BATCH_W ? d->N : 1;
+  const bool modes = flags & FMI_F32_PLAN_MODES;
+  c.det = modes ? (flags & FMI_F32_PLAN_DET) != 0 : fmi_det();
+  c.thin_out = flags & FMI_F32_PLAN_THIN_OUT; c.thin_in = flags & FMI_F32_PLAN_THIN_IN;
+#ifndef FMI_HOST_EMU  // this build has the predicates of thinconv.hip / thinin.hip: their answers, not the caller's
+  c.dma_off = modes ? (flags >> FMI_F32_PLAN_DMA_OFF_SHIFT) & 7 : fmi_dma_off_env();
+  c.thin_out = fmi_conv2d_thin_supported(d) != 0;
+  c.thin_in = fmi_conv2d_thin_in_routed(d) != 0;
+#else
+  c.dma_off = modes ? (flags >> FMI_F32_PLAN_DMA_OFF_SHIFT) & 7 : 0;
+#endif
+  return c;
+}
+static int plan_out(int* out, int& n, const LaunchPlanF& pl) {
+  if (n < 4) {
+    int* o = out + 4 + 10 * n;
+    o[0] = pl.route; o[1] = pl.tile; o[2] = pl.dma; o[3] = pl.fl; o[4] = pl.init; o[5] = pl.ksplit; o[6] = pl.chunk;
+    o[7] = (int)pl.grid[0]; o[8] = (int)pl.grid[1]; o[9] = pl.code();
+  }
+  ++n;
+  return pl.status;
+}
+extern "C" int fmi_conv2d_f32_plan(const fmi_conv_desc* d, int pass, int flags, int* out) {
+  if (!d || !out) return FMI_ERR_BAD_ARG;
+  for (int i = 0; i < FMI_CONV_F32_PLAN_INTS; ++i) out[i] = 0;
+  const int C2 = pass >> 8;
+  pass &= 255;
+  auto done = [&](int rc) {  // the rest is zero when refused
+    if (rc) for (int i = 1; i < FMI_CONV_F32_PLAN_INTS; ++i) out[i] = 0;
+    return out[0] = rc;
+  };
+  if (pass < 0 || pass > 3) return done(FMI_ERR_BAD_ARG);
+  int rc = pass == 3 ? pair_check(d, C2) : check_desc(d);
+  if (rc) return done(rc);
+  ConvCallF c = call_facts_of_flags(d, flags);
+  const int n_eff = c.batch_w > 1 ? 1 : d->N;
+  int n = 0;
+  if (pass == 0) {
+    if (c.y3 && !(d->K % 16 == 0 && d->y_cstride == d->K && c.y3_al16)) return done(FMI_ERR_BAD_ARG);
+    if ((out[2] = fwd_early_f(d, c))) return done(FMI_OK);
+    const ConvGeom g = f32_geom_al(fwd_geom(d, n_eff), d, c.x_al16);
+    rc = plan_out(out, n, conv_phase_plan_f(fwd_phase_in(d, g, c, w_vec_of(c, d->K, 0))));
+  } else if (pass == 1) {
+    if (c.y3 && !(d->C % 16 == 0 && d->x_cstride == d->C && c.y3_al16)) return done(FMI_ERR_BAD_ARG);
+    if (d->pad_mode != 0 || (c.mask && c.bias)) return done(FMI_ERR_UNSUPPORTED);
+    // the thin-input adjoint has no predicate: whether fmi_conv2d_thin_input_dgrad_f32 takes what is tried on it is the caller's THIN_IN bit
+    if (dgrad_thin_out_f(c)) out[2] = ROUTE_THIN_OUT_F;
+    else if (dgrad_thin_in_tried_f(d, c) && (flags & FMI_F32_PLAN_THIN_IN)) out[2] = ROUTE_THIN_IN_F;
+    if (out[2]) return done(FMI_OK);
+    if (d->dil > 1 && d->stride != 1) return done(FMI_ERR_UNSUPPORTED);
+    const bool strided_split = adj_strided_split(d, c, n_eff);
+    out[3] = strided_split ? 1 : 0;
+    if (dgrad_convt3x3_f(d, c, strided_split)) {
+      rc = plan_out(out, n, convt3x3_plan_f(d->N * d->OH * d->OW, d->C));
+    } else {
+      for (int py = 0; py < d->stride; ++py)
+        for (int px = 0; px < d->stride; ++px) {
+          const ConvGeom g = f32_geom_al(adj_geom(d, n_eff, py, px), d, c.x_al16);
+          if (g.GH <= 0 || g.GW <= 0) continue;
+          if (!rc) rc = plan_out(out, n, conv_phase_plan_f(adj_phase_in(d, g, c, w_vec_of(c, d->C, 0), strided_split)));
+        }
+    }
+  } else if (pass == 2) {
+    if ((out[2] = wgrad_thin_out_f(c) ? ROUTE_THIN_OUT_F : 0)) return done(FMI_OK);
+    const ConvGeom g = f32_geom_al(fwd_geom(d, n_eff), d, c.x_al16);
+    const WgradPlanF w = wgrad_plan_f(d, c, g.Kdim(), g.Mdim(), g.vec != 0, (d->K % 4 == 0) && (d->y_cstride % 4 == 0) && c.w_al16);
+    out[3] = (w.fuse_bias ? 2 : 0) | (w.pl.xcd_splits ? 4 : 0);
+    rc = plan_out(out, n, w.pl);
+  } else {  // the ResBlock pair (C2 = pass >> 8): which passes are routed to it, its forward, its weight gradient (BIAS: with a bias gradient)
+    out[3] = pair_routed_f(d) << 4;
+    // the entries refuse a misaligned operand: x1 / x2 (X_AL16), the packs or dy (W_AL16), y (OUT_AL16, the forward only)
+    if (!c.x_al16 || !c.w_al16) return done(FMI_ERR_BAD_ARG);
+    rc = c.out_al16 ? plan_out(out, n, pair_fwd_plan(d, C2, c.act, c.w3 && c.w3_al16, true, c.det, c.dma_off)) : FMI_ERR_BAD_ARG;
+    if (!rc) rc = plan_out(out, n, pair_wgrad_plan(d, C2, c.bias, true, c.det, c.dma_off));
+  }
+  out[1] = n;
+  return done(rc);
 }
 
 #ifndef FMI_HOST_EMU

@@ -262,61 +262,41 @@ __global__ void __launch_bounds__(256) conv3x3_dma_kernel(std::conditional_t<X2,
   store_tile<std::conditional_t<X2, ConvEp2, ConvEp>, T>(ep, acc, M, a.Nout, m0 + wm, n0 + wn, lh, l31);
 }
 
-// geometry the tap-reuse kernel takes (the caller falls back to the generic path otherwise).  C >= 64 or a narrow output: with 32
-// reduction channels a tile has only 6 k-steps and, for 64 outputs, the heavier prologue loses (52 -> 42 TFLOP/s at 8 x 128^2, 32 -> 64)
-// while 32 -> 32 still gains (71 -> 81)
-static bool conv3x3_eligible(const float* x, const float* w, int C, int cs, int Nout, int64_t pixels) {
-  return (C & 15) == 0 && (C >= 64 || Nout <= 32) && (cs & 3) == 0 && (Nout & 3) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0 && pixels < (1ll << 30);
-}
-
 using Tile128x64w = TileCfg<4, 1, 1, 2>;  // 128 x 64 with every wave spanning both column tiles: one activation split per 12 MFMAs
 
 // reduction steps of a launch: 3 per 16-channel chunk of x, one per 16-channel chunk of the pair's x2
 static int c3_steps(const C3Args& a) { return 3 * (a.C >> 4); }
 static int c3_steps(const C3Args2& a) { return 3 * (a.C >> 4) + (a.C2 >> 4); }
 
+// launches what the plan says (c3_plan_f of conv_f32_plan.h: eligibility is conv3x3_eligible_f there)
 template <class ARGS, class EP>
-static int launch_conv3x3(const ARGS& a, const EP& ep, int M, int ksplit, hipStream_t st) {
+static int launch_conv3x3(const ARGS& a, const EP& ep, int M, const LaunchPlanF& pl, hipStream_t st) {
   constexpr bool X2 = std::is_same<ARGS, C3Args2>::value;
   static_assert(std::is_same<EP, std::conditional_t<X2, ConvEp2, ConvEp>>::value, "the pair launches with ConvEp2");
-  const int nit = c3_steps(a);
-  if (ksplit > nit) ksplit = nit;
-  const int it_chunk = (nit + ksplit - 1) / ksplit;
-  ksplit = (nit + it_chunk - 1) / it_chunk;
-#define C3_LAUNCH_(TILE, W3)                                                                                                  \
-  do {                                                                                                                        \
-    const int64_t tm = ceil_div64(M, TILE::BM), tn = ceil_div64(a.Nout, TILE::BN);                                            \
-    if (fl)                                                                                                                   \
-      hipLaunchKernelGGL((conv3x3_dma_kernel<TILE, W3, true, X2>), dim3((unsigned)(tm * tn), (unsigned)ksplit), dim3(256), 0, st, a, ep, M, (int)tn, \
-                         ksplit, it_chunk);                                                                                   \
-    else                                                                                                                      \
-      hipLaunchKernelGGL((conv3x3_dma_kernel<TILE, W3, false, X2>), dim3((unsigned)(tm * tn), (unsigned)ksplit), dim3(256), 0, st, a, ep, M, (int)tn, ksplit, \
-                         it_chunk);                                                                                           \
-  } while (0)
-#define C3_LAUNCH(TILE) C3_LAUNCH_(TILE, false)
-  auto wgs = [&](int bm, int bn) { return ceil_div64(M, bm) * ceil_div64(a.Nout, bn) * ksplit; };
-  const int N = a.Nout;
-  const bool fl = it_chunk > 13 && fmi_det();  // blocked accumulation of a long unsplit reduction (conv_p3.h)
-  // piece images of the weights: 2 x 27 KB of LDS at 64 columns (two workgroups per CU; a 128-column piece tile would leave one).  Measured
-  // at 8 x 128^2 256 -> 256 / 24 x 224^2 64 -> 64 / 8 x 32^2 128 -> 128: 163 / 154 / 81 TFLOP/s against 170 / 144 / 75 with both operands split in the
-  // consuming waves (128 x 128 tiles): taken for narrow outputs and for launches too small to fill the chip with the large tile
-  if (a.w3 && N > 32 && (N <= 64 || wgs(128, 128) < 800)) {
-    C3_LAUNCH_(Tile128x64w, true);
-    return fmi_launch_status();
-  }
-  if (N <= 32) {
-    C3_LAUNCH(Tile128x32);
-  } else if (N <= 64) {
-    if (M > 64 && wgs(128, 64) >= 384) C3_LAUNCH(Tile128x64);
-    else C3_LAUNCH(Tile64x64);
+  if (pl.status) return pl.status;
+  const dim3 grid(pl.grid[0], pl.grid[1]);
+  auto launch = [&](auto tile, auto w3) {
+    using TILE = decltype(tile);
+    constexpr bool W3 = decltype(w3)::value;
+    if (pl.fl) {
+      hipLaunchKernelGGL((conv3x3_dma_kernel<TILE, W3, true, X2>), grid, dim3(256), 0, st, a, ep, M, pl.tiles_n, pl.ksplit, pl.chunk);
+      record_launch_f(W3 ? ROUTE_C3_W3_F : ROUTE_C3_F, false, true, TILE::BM, TILE::BN);
+    } else {
+      hipLaunchKernelGGL((conv3x3_dma_kernel<TILE, W3, false, X2>), grid, dim3(256), 0, st, a, ep, M, pl.tiles_n, pl.ksplit, pl.chunk);
+      record_launch_f(W3 ? ROUTE_C3_W3_F : ROUTE_C3_F, false, false, TILE::BM, TILE::BN);
+    }
+  };
+  if (pl.route == ROUTE_C3_W3_F) {
+    launch(Tile128x64w{}, std::true_type{});
   } else {
-    // between one and two rounds of 128x128 workgroups (3 per CU) the fullest CUs set the time: halve the work unit instead
-    // (VGG 28^2: 588 tiles = 2.3 per CU, 94 -> 100 TFLOP/s with 64x128; at 1176 tiles the 128x128 tile wins again, 114 vs 102)
-    if (M > 64 && wgs(128, 128) >= 800) C3_LAUNCH(Tile128x128);
-    else C3_LAUNCH(Tile64x128);
+    switch (pl.tile) {
+      case tile_id_f(128, 32): launch(Tile128x32{}, std::false_type{}); break;
+      case tile_id_f(128, 64): launch(Tile128x64{}, std::false_type{}); break;
+      case tile_id_f(64, 64): launch(Tile64x64{}, std::false_type{}); break;
+      case tile_id_f(128, 128): launch(Tile128x128{}, std::false_type{}); break;
+      default: launch(Tile64x128{}, std::false_type{}); break;
+    }
   }
-#undef C3_LAUNCH
-#undef C3_LAUNCH_
   return fmi_launch_status();
 }
 #endif

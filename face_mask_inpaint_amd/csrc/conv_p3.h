@@ -218,39 +218,16 @@ __global__ void __launch_bounds__(256) gemm_p3_kernel(ConvK3 la, ConvWX3 lb, Con
   store_tile<ConvEp, T>(ep, acc, M, N, m0 + wm, n0 + wn, lh, l31);
 }
 
-static bool p3_generic_ok(const ConvGeom& g, const void* x3, const void* w3, int Nout) {
-  return x3 && w3 && (g.C & 15) == 0 && !g.pad_mode && ((uintptr_t)x3 & 15) == 0 && ((uintptr_t)w3 & 15) == 0 && (Nout & 3) == 0 &&
-         (int64_t)g.N * g.IH * g.IW * 3 * g.C < (1ll << 40);
-}
-
-static int launch_gemm_p3(const ConvK3& la, const ConvWX3& lb, const ConvEp& ep, int M, int N, int K, int ksplit, hipStream_t st) {
-  if (M <= 0 || N <= 0 || K <= 0 || ksplit <= 0) return FMI_ERR_BAD_ARG;
-  int kchunk = (int)ceil_div64(ceil_div64(K, ksplit), 16) * 16;
-  ksplit = (int)ceil_div64(K, kchunk);
-  if (ksplit > 65535) return FMI_ERR_UNSUPPORTED;
-#define P3_LAUNCH(TILE)                                                                                                                        \
-  do {                                                                                                                                         \
-    const int64_t tm = ceil_div64(M, TILE::BM), tn = ceil_div64(N, TILE::BN);                                                                  \
-    if (tm * tn > 0x7fffffffLL) return FMI_ERR_UNSUPPORTED;                                                                                    \
-    if (fl)                                                                                                                                    \
-      hipLaunchKernelGGL((gemm_p3_kernel<TILE, true>), dim3((unsigned)(tm * tn), (unsigned)ksplit), dim3(256), 0, st, la, lb, ep, M, N, K, (int)tn, ksplit, \
-                         kchunk);                                                                                                              \
-    else                                                                                                                                       \
-      hipLaunchKernelGGL((gemm_p3_kernel<TILE>), dim3((unsigned)(tm * tn), (unsigned)ksplit), dim3(256), 0, st, la, lb, ep, M, N, K, (int)tn, ksplit, \
-                         kchunk);                                                                                                              \
-  } while (0)
-  // blocked accumulation (a second accumulator set: ~64 registers, an occupancy step for the 128 x 128 tile) where one workgroup adds more
-  // than ~600 products in a row AND the run asks for it: the reproducible mode, where no split reduction blocks the sum for us
-  const bool fl = kchunk > 640 && fmi_det();
-  switch (pick_gemm_tile(M, N, ksplit)) {
-    case GemmTile::t128x32: P3_LAUNCH(Tile128x32); break;
-    case GemmTile::t128x64: P3_LAUNCH(Tile128x64); break;
-    case GemmTile::t64x64: P3_LAUNCH(Tile64x64); break;
-    case GemmTile::t128x128: P3_LAUNCH(Tile128x128); break;
-    case GemmTile::t64x128: P3_LAUNCH(Tile64x128); break;
-    case GemmTile::t32x128: P3_LAUNCH(Tile32x128); break;
-  }
-#undef P3_LAUNCH
+// launches what the plan says (gemm_plan_f with ROUTE_GEMM_P3_F; eligibility is p3_generic_ok_f of conv_f32_plan.h)
+static int launch_gemm_p3(const ConvK3& la, const ConvWX3& lb, const ConvEp& ep, int M, int N, int K, const LaunchPlanF& pl, hipStream_t st) {
+  if (pl.status) return pl.status;
+  const dim3 grid(pl.grid[0], pl.grid[1]);
+  with_gemm_tile(pl.tile, [&](auto tile) {
+    using TILE = decltype(tile);
+    if (pl.fl) hipLaunchKernelGGL((gemm_p3_kernel<TILE, true>), grid, dim3(256), 0, st, la, lb, ep, M, N, K, pl.tiles_n, pl.ksplit, pl.chunk);
+    else hipLaunchKernelGGL((gemm_p3_kernel<TILE>), grid, dim3(256), 0, st, la, lb, ep, M, N, K, pl.tiles_n, pl.ksplit, pl.chunk);
+    record_launch_f(ROUTE_GEMM_P3_F, false, pl.fl, TILE::BM, TILE::BN);
+  });
   return fmi_launch_status();
 }
 #endif
@@ -430,39 +407,22 @@ using C3P3_256x64 = P3Tile<4, 2, 2, 1>;   // 8 waves, 64 x 32 per wave
 using C3P3_128x128 = P3Tile<2, 2, 2, 2>;  // 4 waves
 using C3P3_128x64 = P3Tile<4, 1, 1, 2>;   // 4 waves, every wave spans both column tiles
 
-static bool conv3x3_p3_eligible(const void* x3, const void* w3, int C, int Nout, int64_t pixels) {
-  return x3 && w3 && (C & 15) == 0 && (Nout & 3) == 0 && ((uintptr_t)x3 & 15) == 0 && ((uintptr_t)w3 & 15) == 0 && pixels < (1ll << 30);
-}
-
-static int launch_conv3x3_p3(const C3P3Args& a, const ConvEp& ep, int M, int ksplit, hipStream_t st) {
-  const int nit = 3 * (a.C >> 4);
-  if (ksplit > nit) ksplit = nit;
-  const int it_chunk = (nit + ksplit - 1) / ksplit;
-  ksplit = (nit + it_chunk - 1) / it_chunk;
-#define C3P3_LAUNCH(TILE)                                                                                                                          \
-  do {                                                                                                                                             \
-    const int64_t tm = ceil_div64(M, TILE::BM), tn = ceil_div64(a.Nout, TILE::BN);                                                                 \
-    if (fl)                                                                                                                                        \
-      hipLaunchKernelGGL((conv3x3_p3_kernel<TILE, true>), dim3((unsigned)(tm * tn), (unsigned)ksplit), dim3(TILE::NW * 64), 0, st, a, ep, M, (int)tn, \
-                         ksplit, it_chunk);                                                                                                        \
-    else                                                                                                                                           \
-      hipLaunchKernelGGL((conv3x3_p3_kernel<TILE>), dim3((unsigned)(tm * tn), (unsigned)ksplit), dim3(TILE::NW * 64), 0, st, a, ep, M, (int)tn,    \
-                         ksplit, it_chunk);                                                                                                        \
-  } while (0)
-  auto wgs = [&](int bm, int bn) { return ceil_div64(M, bm) * ceil_div64(a.Nout, bn) * ksplit; };
-  const int N = a.Nout;
-  // blocked accumulation: the eight-wave tiles hold one workgroup per CU (LDS) at 150 of 256 registers -- the second accumulator set is
-  // free there, so every long reduction takes it; the four-wave tiles only in the reproducible mode (occupancy)
-  const bool long_red = it_chunk > 13;
-  int pick;
-  if (N > 64) pick = wgs(256, 128) >= 256 ? 1 : 3;
-  else pick = wgs(256, 64) >= 256 ? 2 : 4;
-  const bool fl = long_red && (pick <= 2 || fmi_det());
-  if (pick == 1) C3P3_LAUNCH(C3P3_256x128);
-  else if (pick == 2) C3P3_LAUNCH(C3P3_256x64);
-  else if (pick == 3) C3P3_LAUNCH(C3P3_128x128);
-  else C3P3_LAUNCH(C3P3_128x64);
-#undef C3P3_LAUNCH
+// launches what the plan says (c3p3_plan_f; eligibility is conv3x3_p3_eligible_f of conv_f32_plan.h)
+static int launch_conv3x3_p3(const C3P3Args& a, const ConvEp& ep, int M, const LaunchPlanF& pl, hipStream_t st) {
+  if (pl.status) return pl.status;
+  const dim3 grid(pl.grid[0], pl.grid[1]);
+  auto launch = [&](auto tile) {
+    using TILE = decltype(tile);
+    if (pl.fl) hipLaunchKernelGGL((conv3x3_p3_kernel<TILE, true>), grid, dim3(TILE::NW * 64), 0, st, a, ep, M, pl.tiles_n, pl.ksplit, pl.chunk);
+    else hipLaunchKernelGGL((conv3x3_p3_kernel<TILE>), grid, dim3(TILE::NW * 64), 0, st, a, ep, M, pl.tiles_n, pl.ksplit, pl.chunk);
+    record_launch_f(ROUTE_C3_P3_F, false, pl.fl, TILE::BM, TILE::BN);
+  };
+  switch (pl.tile) {
+    case tile_id_f(256, 128): launch(C3P3_256x128{}); break;
+    case tile_id_f(256, 64): launch(C3P3_256x64{}); break;
+    case tile_id_f(128, 128): launch(C3P3_128x128{}); break;
+    default: launch(C3P3_128x64{}); break;
+  }
   return fmi_launch_status();
 }
 #endif
@@ -902,83 +862,48 @@ __global__ void __launch_bounds__(256, FL ? 1 : 2) wgrad3x3_p3_kernel(Wg3x3Args 
   }
 }
 
-// C % 64: with one 32-channel group per tile (GA = 1) the three taps share too little -- measured 47 against 72 TFLOP/s of the kernel above
-static bool wgrad3x3_p3_ok(const fmi_conv_desc* d) {
-  return d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->dil <= 1 && d->W >= 16 && d->OH == d->H && d->OW == d->W && d->C % 64 == 0;
-}
-
-// x3 / dy3: piece images of x [N][H][W][C] and dy [N][OH][OW][K] (dense tensors)
-static int launch_wgrad_p3(const fmi_conv_desc* d, const uint16_t* x3, const uint16_t* dy3, float* dwf, hipStream_t st) {
-  WgP3Args a{};
-  a.x3 = x3; a.dy3 = dy3; a.dwf = dwf;
-  ConvGeom& g = a.g;
-  g = fwd_geom(d, d->N);  // dense x, zero padding (wgrad_p3_ok): cstride = C, pad_mode = 0; vec and img_bs are not read here
-  g.ystep = g.xstep = d->dil > 1 ? d->dil : 1;  // dilation = the tap step of the gather
-  g.dC = make_fastdiv(g.C);                     // output row -> tap
-  a.Kout = d->K; a.Mrows = d->kh * d->kw * d->C; a.P = d->N * d->OH * d->OW;
-  if (wgrad3x3_p3_ok(d)) {
+// x3 / dy3: piece images of x [N][H][W][C] and dy [N][OH][OW][K] (dense tensors).  Launches what the plan says (wgrad_p3_plan_f of
+// conv_f32_plan.h; eligibility is wgrad_p3_ok_f there).  The two kernels take different argument structs and template parameters, so
+// each keeps its launch lines.
+static int launch_wgrad_p3(const fmi_conv_desc* d, const uint16_t* x3, const uint16_t* dy3, float* dwf, const LaunchPlanF& pl, hipStream_t st) {
+  if (pl.status) return pl.status;
+  const dim3 grid(pl.grid[0], pl.grid[1]);
+  if (pl.route == ROUTE_WGRAD_P3_3X3_F) {
     Wg3x3Args w{};
     w.x3 = x3; w.dy3 = dy3; w.dwf = dwf;
     w.H = d->H; w.W = d->W; w.C = d->C; w.Kout = d->K; w.P = d->N * d->H * d->W;
     w.dW = make_fastdiv(d->W); w.dHW = make_fastdiv(d->H * d->W);
-    const int bn3 = d->K <= 64 ? 64 : 128;
-    const int64_t tm3 = 3 * (d->C / 64), tn3 = ceil_div64(d->K, bn3);
-    int64_t ks = 2048 / (tm3 * tn3);
-    const int64_t kmax3 = w.P / 512;
-    if (ks > kmax3) ks = kmax3;
-    if (ks < 1) ks = 1;
-    if (ks >= 6) ks = (ks + 4) / 8 * 8;
-    if (fmi_det()) ks = 1;
-    w.kchunk = (int)(ceil_div64(ceil_div64(w.P, ks), 16) * 16);
-    ks = ceil_div64(w.P, w.kchunk);
-    w.tiles = (int)(tm3 * tn3);
-    w.ksplit = (int)ks;
-    w.xcd_splits = ks >= 8 ? 1 : 0;
-    const int64_t nwg3 = w.xcd_splits ? tm3 * tn3 * ceil_div64(ks, 8) * 8 : tm3 * tn3;
-    if (nwg3 > 0x7fffffffLL) return FMI_ERR_UNSUPPORTED;
-    const dim3 grid3((unsigned)nwg3, w.xcd_splits ? 1u : (unsigned)ks);
-    const bool fl3 = w.kchunk > 640 && fmi_det();
-#define WG3X3_LAUNCH(GA_, TN_)                                                                                 \
-  do {                                                                                                         \
-    if (fl3) hipLaunchKernelGGL((wgrad3x3_p3_kernel<GA_, TN_, true>), grid3, dim3(256), 0, st, w, (int)tn3);   \
-    else hipLaunchKernelGGL((wgrad3x3_p3_kernel<GA_, TN_>), grid3, dim3(256), 0, st, w, (int)tn3);             \
-  } while (0)
-    if (bn3 == 128) WG3X3_LAUNCH(2, 2);
-    else WG3X3_LAUNCH(2, 1);
-#undef WG3X3_LAUNCH
-    return fmi_launch_status();
+    w.kchunk = pl.chunk; w.tiles = pl.tiles; w.ksplit = pl.ksplit; w.xcd_splits = pl.xcd_splits;
+    if (tile_bn_f(pl.tile) == 128) {
+      if (pl.fl) hipLaunchKernelGGL((wgrad3x3_p3_kernel<2, 2, true>), grid, dim3(256), 0, st, w, pl.tiles_n);
+      else hipLaunchKernelGGL((wgrad3x3_p3_kernel<2, 2>), grid, dim3(256), 0, st, w, pl.tiles_n);
+      record_launch_f(ROUTE_WGRAD_P3_3X3_F, false, pl.fl, 192, 128);
+    } else {
+      if (pl.fl) hipLaunchKernelGGL((wgrad3x3_p3_kernel<2, 1, true>), grid, dim3(256), 0, st, w, pl.tiles_n);
+      else hipLaunchKernelGGL((wgrad3x3_p3_kernel<2, 1>), grid, dim3(256), 0, st, w, pl.tiles_n);
+      record_launch_f(ROUTE_WGRAD_P3_3X3_F, false, pl.fl, 192, 64);
+    }
+  } else {
+    WgP3Args a{};
+    a.x3 = x3; a.dy3 = dy3; a.dwf = dwf;
+    ConvGeom& g = a.g;
+    g = fwd_geom(d, d->N);  // dense x, zero padding (wgrad_p3_ok_f): cstride = C, pad_mode = 0; vec and img_bs are not read here
+    g.ystep = g.xstep = d->dil > 1 ? d->dil : 1;  // dilation = the tap step of the gather
+    g.dC = make_fastdiv(g.C);                     // output row -> tap
+    a.Kout = d->K; a.Mrows = d->kh * d->kw * d->C; a.P = d->N * d->OH * d->OW;
+    a.kchunk = pl.chunk; a.tiles = pl.tiles; a.ksplit = pl.ksplit; a.xcd_splits = pl.xcd_splits;
+    auto launch = [&](auto tile) {
+      using TILE = decltype(tile);
+      if (pl.fl) hipLaunchKernelGGL((wgrad_p3_kernel<TILE, true>), grid, dim3(256), 0, st, a, pl.tiles_n);
+      else hipLaunchKernelGGL((wgrad_p3_kernel<TILE>), grid, dim3(256), 0, st, a, pl.tiles_n);
+      record_launch_f(ROUTE_WGRAD_P3_F, false, pl.fl, TILE::BM, TILE::BN);
+    };
+    switch (tile_bn_f(pl.tile)) {
+      case 32: launch(WG3_128x32{}); break;
+      case 64: launch(WG3_128x64{}); break;
+      default: launch(WG3_128x128{}); break;
+    }
   }
-  const int bn = d->K <= 32 ? 32 : (d->K <= 64 ? 64 : 128);
-  const int64_t tm = ceil_div64(a.Mrows, 128), tn = ceil_div64(d->K, bn);
-  int64_t ksplit = 2048 / (tm * tn);
-  const int64_t kmax = a.P / 512;
-  if (ksplit > kmax) ksplit = kmax;
-  if (ksplit < 1) ksplit = 1;
-  if (ksplit > 65535) ksplit = 65535;
-  if (ksplit >= 6) ksplit = (ksplit + 4) / 8 * 8;  // splits are dealt to the 8 XCDs in groups of 8: keep the groups full
-  if (fmi_det()) ksplit = 1;                       // reproducible mode
-  a.kchunk = (int)(ceil_div64(ceil_div64(a.P, ksplit), 16) * 16);
-  ksplit = ceil_div64(a.P, a.kchunk);
-  a.tiles = (int)(tm * tn);
-  a.ksplit = (int)ksplit;
-  a.xcd_splits = ksplit >= 8 ? 1 : 0;
-  const int64_t nwg = a.xcd_splits ? tm * tn * ceil_div64(ksplit, 8) * 8 : tm * tn;
-  if (nwg > 0x7fffffffLL) return FMI_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)nwg, a.xcd_splits ? 1u : (unsigned)ksplit);
-  const bool fl = a.kchunk > 640 && fmi_det();  // blocked accumulation of a long unsplit pixel reduction
-#define WG3_LAUNCH(TILE, NT)                                                                              \
-  do {                                                                                                    \
-    if (fl) hipLaunchKernelGGL((wgrad_p3_kernel<TILE, true>), grid, dim3(NT), 0, st, a, (int)tn);         \
-    else hipLaunchKernelGGL((wgrad_p3_kernel<TILE>), grid, dim3(NT), 0, st, a, (int)tn);                  \
-  } while (0)
-  if (bn == 32) WG3_LAUNCH(WG3_128x32, 256);
-  else if (bn == 64) WG3_LAUNCH(WG3_128x64, 256);
-  else WG3_LAUNCH(WG3_128x128, 256);
-#undef WG3_LAUNCH
   return fmi_launch_status();
-}
-static bool wgrad_p3_ok(const fmi_conv_desc* d, const void* x3, const void* dy3) {
-  return x3 && dy3 && d->C % 32 == 0 && d->K % 16 == 0 && d->x_cstride == d->C && d->y_cstride == d->K && d->pad_mode == 0 && ((uintptr_t)x3 & 15) == 0 &&
-         ((uintptr_t)dy3 & 15) == 0 && (int64_t)d->N * d->H * d->W * 3 * d->C < (1ll << 40) && (int64_t)d->N * d->OH * d->OW < 0x7fffffffLL;
 }
 #endif

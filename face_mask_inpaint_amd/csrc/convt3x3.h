@@ -200,16 +200,11 @@ __global__ void __launch_bounds__(256, TN == 1 ? 3 : 2) convt3x3s2_dma_kernel(CT
   }
 }
 
-// d: the descriptor of the convolution whose adjoint this is (fmi_conv2d_dgrad_f32): d->H x d->W = the ConvTranspose's OUTPUT
-static bool convt3x3_eligible(const fmi_conv_desc* d, const float* dy, const uint16_t* w3) {
-  return w3 && d->kh == 3 && d->kw == 3 && d->stride == 2 && d->pad == 1 && d->dil <= 1 && d->H == 2 * d->OH && d->W == 2 * d->OW &&
-         (d->K & 15) == 0 && d->C <= 64 && (d->C & 3) == 0 && (d->y_cstride & 3) == 0 && ((uintptr_t)dy & 15) == 0 &&
-         (int64_t)d->N * d->OH * d->OW >= 32768 && (int64_t)d->N * d->OH * d->OW < (1ll << 30);
-}
-static int launch_convt3x3(CT3Args& a, int M, hipStream_t st) {
-  const int64_t tm = ceil_div64(M, 128), tn = ceil_div64(a.Nout, 32);
-  if (tm * tn > 0x7fffffffLL) return FMI_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL((convt3x3s2_dma_kernel<1>), dim3((unsigned)(tm * tn)), dim3(256), 0, st, a, M, (int)tn);
+// launches what the plan says (convt3x3_plan_f; eligibility is convt3x3_eligible_f of conv_f32_plan.h)
+static int launch_convt3x3(CT3Args& a, int M, const LaunchPlanF& pl, hipStream_t st) {
+  if (pl.status) return pl.status;
+  hipLaunchKernelGGL((convt3x3s2_dma_kernel<1>), dim3(pl.grid[0]), dim3(256), 0, st, a, M, pl.tiles_n);
+  record_launch_f(ROUTE_CONVT3X3_F, false, false, 128, 32);
   return fmi_launch_status();
 }
 #endif

@@ -13,6 +13,8 @@
 //  * workgroup ids are remapped so that each XCD (private L2) walks a contiguous range of tiles.
 #pragma once
 #include "common.h"
+#include "conv_f32_plan.h"
+__attribute__((visibility("hidden"))) inline int fmi_f32_last_plan_code = 0;  // fmi_debug_f32_last_plan (conv.hip): the code of the last fp32 convolution launch, see record_launch_f
 #include <cstdio>
 #include <cstdlib>
 extern "C" long fmi_debug_launch_counter;
@@ -1073,77 +1075,69 @@ __global__ void __launch_bounds__(256) gemm_dma_f32_kernel(LA la, LB lb, EP ep, 
   store_tile<EP, T>(ep, acc, M, N, m0 + wm, n0 + wn, lh, l31);
 }
 
-// Tile of the generic GEMM launchers (launch_gemm here, launch_gemm_p3 in conv_p3.h) for an M x N output with z workgroups per output
-// tile (batch x reduction splits): the largest tile that still gives ~1.5 workgroups per CU; small problems trade operand reuse for
-// occupancy.
-enum class GemmTile { t128x32, t128x64, t64x64, t128x128, t64x128, t32x128 };
-static GemmTile pick_gemm_tile(int M, int N, int64_t z) {
-  auto wgs = [&](int bm, int bn) { return ceil_div64(M, bm) * ceil_div64(N, bn) * z; };
-  const int64_t want = 384, want128 = 800;  // 128x128 only from ~one full round of workgroups (3 per CU) up: below that the
-                                           // fullest CUs set the time and the 64x128 tile balances better (measured: -0.7 ms per step)
-  if (N <= 32) return GemmTile::t128x32;
-  if (N <= 64) return (M > 64 && wgs(128, 64) >= want) ? GemmTile::t128x64 : GemmTile::t64x64;
-  if (M > 64 && wgs(128, 128) >= want128) return GemmTile::t128x128;
-  if (M > 32 && wgs(64, 128) >= want) return GemmTile::t64x128;
-  if (M > 64 && wgs(32, 128) < 256) return GemmTile::t64x128;
-  return GemmTile::t32x128;
+// The tile table (gemm_tile_f), the split normalisation and the DMA-or-register choice are gemm_plan_f of conv_f32_plan.h.
+// calls f with the tile type a plan's tile id names: the one switch of launch_gemm and launch_gemm_p3 (launch_conv3x3
+// keeps its own: it has no 32 x 128 instantiation)
+template <class F>
+static void with_gemm_tile(int tile, F&& f) {
+  switch (tile) {
+    case tile_id_f(128, 32): f(Tile128x32{}); break;
+    case tile_id_f(128, 64): f(Tile128x64{}); break;
+    case tile_id_f(64, 64): f(Tile64x64{}); break;
+    case tile_id_f(128, 128): f(Tile128x128{}); break;
+    case tile_id_f(64, 128): f(Tile64x128{}); break;
+    case tile_id_f(32, 128): f(Tile32x128{}); break;
+  }
 }
 
-// Host-side launcher: picks the tile from N (and M), validates the 32-bit index ranges the kernel assumes.
-template <class LA, class LB, class EP>
-static int launch_gemm(const LA& la, const LB& lb, const EP& ep, int M, int N, int K, int batch, int ksplit,
-                       hipStream_t st) {
-  if (M <= 0 || N <= 0 || K < 0 || batch <= 0 || ksplit <= 0) return FMI_ERR_BAD_ARG;
-  int kchunk = 16;
-  if (K == 0) {
-    ksplit = 1;  // empty reduction: the epilogue still writes bias / residual
-  } else {
-    kchunk = (int)ceil_div64(ceil_div64(K, ksplit), 16) * 16;
-    ksplit = (int)ceil_div64(K, kchunk);
-  }
-  const int64_t gy = (int64_t)batch * ksplit;
-  if (gy > 65535) return FMI_ERR_UNSUPPORTED;
-  // FMI_DMA_OFF (debug): bit 0 dense GEMM, bit 1 conv forward / adjoint, bit 2 weight gradient -> use the register-staged kernel
+// fmi_debug_f32_last_plan: written INSIDE the branch that launches, from the instantiation's own template arguments (TILE::BM / BN, FL,
+// the kernel form) -- not from the plan, so that the record says which kernel was started
+static inline void record_launch_f(int route, bool dma, bool fl, int bm, int bn) {
+  if (route != ROUTE_DENSE_F) __atomic_store_n(&fmi_f32_last_plan_code, plan_code_f(route, dma, fl, tile_id_f(bm, bn)), __ATOMIC_RELAXED);
+}
+
+template <class LA>
+constexpr int gemm_family_f() { return std::is_same<LA, ConvK>::value ? DMA_FAMILY_CONV_F : (std::is_same<LA, WgradAX>::value ? DMA_FAMILY_WGRAD_F : DMA_FAMILY_DENSE_F); }
+// FMI_DMA_OFF (debug): the families whose launches use the register-staged kernel
+static inline int fmi_dma_off_env() {
   static const int dma_off = getenv("FMI_DMA_OFF") ? atoi(getenv("FMI_DMA_OFF")) : 0;
-  const int family = std::is_same<LA, ConvK>::value ? 2 : (std::is_same<LA, WgradAX>::value ? 4 : 1);
-  bool dma = !(dma_off & family) && la.dma_ok() && lb.dma_ok();
-  if (const char* r = getenv("FMI_DMA_OFF_RANGE")) {  // debug: "a:b" = launches a <= i < b of this process use the register-staged kernel
+  return dma_off;
+}
+
+// Launches what the plan says (gemm_plan_f).  FMI_DMA_OFF_RANGE (debug): "a:b" = launches a <= i < b of this process use the
+// register-staged kernel -- the plan is made again with the family's FMI_DMA_OFF bit set.
+template <class LA, class LB, class EP>
+static int launch_gemm_plan(const LA& la, const LB& lb, const EP& ep, int M, int N, int K, int batch, LaunchPlanF pl, hipStream_t st) {
+  if (pl.status) return pl.status;
+  constexpr int family = gemm_family_f<LA>();
+  if (const char* r = getenv("FMI_DMA_OFF_RANGE")) {
     long a = 0, b = 0;
     sscanf(r, "%ld:%ld", &a, &b);
     const long i = __atomic_fetch_add(&fmi_debug_launch_counter, 1L, __ATOMIC_RELAXED);  // forward and autograd threads both launch
-    if (i >= a && i < b) dma = false;
-    if (getenv("FMI_DMA_TRACE")) fprintf(stderr, "[fmi launch %ld] family %d M %d N %d K %d batch %d ksplit %d dma %d (eligible %d %d)\n", i, family, M, N, K, batch, ksplit, (int)dma, (int)la.dma_ok(), (int)lb.dma_ok());
+    if (i >= a && i < b) pl = gemm_plan_f(pl.route, M, N, K, batch, pl.asked, la.dma_ok() && lb.dma_ok(), family, family, fmi_det());
+    if (getenv("FMI_DMA_TRACE")) fprintf(stderr, "[fmi launch %ld] family %d M %d N %d K %d batch %d ksplit %d dma %d (eligible %d %d)\n", i, family, M, N, K, batch, pl.ksplit, (int)pl.dma, (int)la.dma_ok(), (int)lb.dma_ok());
   }
-  const bool fl = kchunk > 640 && fmi_det();  // blocked accumulation of a long unsplit reduction (LDS-DMA kernel)
-#define FMI_LAUNCH(TILE)                                                                                      \
-  do {                                                                                                        \
-    const int64_t tm = ceil_div64(M, TILE::BM), tn = ceil_div64(N, TILE::BN);                                 \
-    if (tm * tn > 0x7fffffffLL) return FMI_ERR_UNSUPPORTED;                                                   \
-    {                                                                                                         \
-      if (dma && fl) {                                                                                        \
-        hipLaunchKernelGGL((gemm_dma_f32_kernel<LA, LB, EP, TILE, true>), dim3((unsigned)(tm * tn), (unsigned)gy), dim3(256), \
-                           0, st, la, lb, ep, M, N, K, (int)tn, ksplit, kchunk);                              \
-        break;                                                                                                \
-      }                                                                                                       \
-      if (dma) {                                                                                              \
-        hipLaunchKernelGGL((gemm_dma_f32_kernel<LA, LB, EP, TILE>), dim3((unsigned)(tm * tn), (unsigned)gy), dim3(256), \
-                           0, st, la, lb, ep, M, N, K, (int)tn, ksplit, kchunk);                              \
-        break;                                                                                                \
-      }                                                                                                       \
-    }                                                                                                         \
-    hipLaunchKernelGGL((gemm_mfma_f32_kernel<LA, LB, EP, TILE>), dim3((unsigned)(tm * tn), (unsigned)gy), dim3(256), \
-                       0, st, la, lb, ep, M, N, K, (int)tn, ksplit, kchunk);                                  \
-  } while (0)
-  switch (pick_gemm_tile(M, N, gy)) {
-    case GemmTile::t128x32: FMI_LAUNCH(Tile128x32); break;
-    case GemmTile::t128x64: FMI_LAUNCH(Tile128x64); break;
-    case GemmTile::t64x64: FMI_LAUNCH(Tile64x64); break;
-    case GemmTile::t128x128: FMI_LAUNCH(Tile128x128); break;
-    case GemmTile::t64x128: FMI_LAUNCH(Tile64x128); break;
-    case GemmTile::t32x128: FMI_LAUNCH(Tile32x128); break;
-  }
-#undef FMI_LAUNCH
+  const dim3 grid(pl.grid[0], pl.grid[1]);
+  with_gemm_tile(pl.tile, [&](auto tile) {
+    using TILE = decltype(tile);
+    if (pl.dma && pl.fl) {
+      hipLaunchKernelGGL((gemm_dma_f32_kernel<LA, LB, EP, TILE, true>), grid, dim3(256), 0, st, la, lb, ep, M, N, K, pl.tiles_n, pl.ksplit, pl.chunk);
+      record_launch_f(pl.route, true, true, TILE::BM, TILE::BN);
+    } else if (pl.dma) {
+      hipLaunchKernelGGL((gemm_dma_f32_kernel<LA, LB, EP, TILE>), grid, dim3(256), 0, st, la, lb, ep, M, N, K, pl.tiles_n, pl.ksplit, pl.chunk);
+      record_launch_f(pl.route, true, false, TILE::BM, TILE::BN);
+    } else {
+      hipLaunchKernelGGL((gemm_mfma_f32_kernel<LA, LB, EP, TILE>), grid, dim3(256), 0, st, la, lb, ep, M, N, K, pl.tiles_n, pl.ksplit, pl.chunk);
+      record_launch_f(pl.route, false, false, TILE::BM, TILE::BN);
+    }
+  });
   return fmi_launch_status();
+}
+// ... for a caller that brings the split it asks for, not a plan (the dense GEMM, the pair, the weight gradient)
+template <class LA, class LB, class EP>
+static int launch_gemm(const LA& la, const LB& lb, const EP& ep, int M, int N, int K, int batch, int ksplit, hipStream_t st, int route = ROUTE_DENSE_F) {
+  return launch_gemm_plan(la, lb, ep, M, N, K, batch,
+                          gemm_plan_f(route, M, N, K, batch, ksplit, la.dma_ok() && lb.dma_ok(), gemm_family_f<LA>(), fmi_dma_off_env(), fmi_det()), st);
 }
 
 #else  // ------------------------------ FMI_HOST_EMU ------------------------------

@@ -166,6 +166,49 @@ int fmi_conv2d_dgrad_f32(const fmi_conv_desc* d, const float* dy, const float* w
 int fmi_conv2d_pair_supported(const fmi_conv_desc* d, int C2);
 int fmi_conv2d_pair_routed(const fmi_conv_desc* d, int C2);
 int fmi_conv2d_pair_ksplit(const fmi_conv_desc* d, int C2, int act);
+/* What fmi_conv2d_fwd_f32 (pass 0), fmi_conv2d_dgrad_f32 and its masked forms (1), fmi_conv2d_wgrad_f32 (2) or the ResBlock pair (3 with
+ * C2 in pass >> 8) would launch for d -- decided by the code the entries run (csrc/conv_f32_plan.h), without a launch and without a GPU.
+ * flags: what the decision reads of a call's pointers and of the process (below).  out[FMI_CONV_F32_PLAN_INTS]:
+ *   [0] status as the entry returns it   [1] planned launches of the convolution kernels (0 for an early exit; the phases of a strided
+ *   adjoint, at most the first four are listed)   [2] early exit: 11 the thin-output kernels, 12 the thin-input kernels
+ *   [3] bit 0 a strided adjoint initialises dx once for all phases, bit 1 the weight gradient fuses the bias gradient, bit 2 its splits are
+ *       dealt to the XCDs in groups of 8, bits 4..5 (pair) fmi_conv2d_pair_routed
+ *   [4 + 10 p ...] launch p: route (1 GEMM, 2 GEMM on weight pieces, 3 GEMM on piece images, 4 tap-reuse 3x3, 5 tap-reuse 3x3 on weight
+ *       pieces, 6 tap-reuse 3x3 on piece images, 7 one-launch ConvTranspose 3x3, 8 / 9 / 10 weight gradient as GEMM / from piece images /
+ *       3x3 from piece images), tile (1000 rows + columns), LDS-DMA kernel, blocked accumulation, an initialising launch precedes it,
+ *       splits, reduction per split, grid x, grid y, and the code fmi_debug_f32_last_plan reports after that launch.
+ *   Pair: launch 0 is its forward, launch 1 its weight gradient (FMI_F32_PLAN_BIAS: with the bias gradient; _W3: both piece images), from
+ *   the functions its two entries launch with; X_AL16 (x1, x2), W_AL16 (both packs, dy) and OUT_AL16 must be set, as the entries refuse
+ *   a misaligned operand (FMI_ERR_BAD_ARG).
+ * The thin kernels' files decide for themselves: in the device build THIN_OUT / THIN_IN are ignored for what fmi_conv2d_thin_supported and
+ * fmi_conv2d_thin_in_routed answer; a build without those files (g++ -DFMI_HOST_EMU) is told.  Whether the thin-input ADJOINT takes a call
+ * has no predicate: pass 1 reads THIN_IN in both builds.  Returns out[0]; FMI_ERR_BAD_ARG for a null d or out or an unknown pass. */
+#define FMI_CONV_F32_PLAN_INTS 44
+#define FMI_F32_PLAN_X_AL16 0x1      /* the gathered tensor (x; the adjoint's dy) is 16-byte aligned */
+#define FMI_F32_PLAN_W_AL16 0x2      /* the second operand (weights; the weight gradient's dy) is */
+#define FMI_F32_PLAN_OUT_AL16 0x4    /* the output is */
+#define FMI_F32_PLAN_RES 0x8         /* a residual is given ... */
+#define FMI_F32_PLAN_RES_AL16 0x10   /* ... and 16-byte aligned */
+#define FMI_F32_PLAN_X3 0x20         /* d->x3 ... */
+#define FMI_F32_PLAN_X3_AL16 0x40
+#define FMI_F32_PLAN_W3 0x80         /* d->w3 ... */
+#define FMI_F32_PLAN_W3_AL16 0x100
+#define FMI_F32_PLAN_Y3 0x200        /* d->y3 ... */
+#define FMI_F32_PLAN_Y3_AL16 0x400
+#define FMI_F32_PLAN_BIAS 0x800      /* bias (weight gradient: dbias) given */
+#define FMI_F32_PLAN_MASK 0x1000
+#define FMI_F32_PLAN_ACT 0x2000      /* act != 0 */
+#define FMI_F32_PLAN_BATCH_W 0x4000  /* per-sample weights: batch_w = d->N */
+#define FMI_F32_PLAN_DET 0x8000      /* with FMI_F32_PLAN_MODES: reproducible mode */
+#define FMI_F32_PLAN_MODES 0x10000   /* take reproducible mode and FMI_DMA_OFF (bits 17..19) from flags, not from the process */
+#define FMI_F32_PLAN_DMA_OFF_SHIFT 17
+#define FMI_F32_PLAN_THIN_OUT 0x100000
+#define FMI_F32_PLAN_THIN_IN 0x200000
+int fmi_conv2d_f32_plan(const fmi_conv_desc* d, int pass, int flags, int* out);
+/* Route, kernel form and tile of the last forward, adjoint or weight-gradient launch of the fp32 family: route << 24 | LDS-DMA kernel << 23 |
+ * blocked accumulation << 22 | tile, as out[13 + 10 p] of the query names it; 0 before the first.  Each launcher writes it in the branch that
+ * launches, from that kernel instantiation's own tile and form, not from the plan.  An early exit to the thin kernels leaves it. */
+int fmi_debug_f32_last_plan(void);
 int fmi_conv2d_pair_fwd_f32(const fmi_conv_desc* d, const float* x1, const float* x2, int C2, const float* wf1, const float* wf2,
                             const void* w3b, const float* b1, const float* b2, float* y, int act, void* stream);
 int fmi_conv2d_pair_wgrad_f32(const fmi_conv_desc* d, const float* x1, const float* x2, int C2, const float* dy, float* dw1, float* dw2,
