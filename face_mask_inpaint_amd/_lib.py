@@ -96,6 +96,8 @@ SIGNATURES = {
     "fmi_vgg_tap_fwd_bf16": [vp, vp, vp, i32, i32, i32, i32, vp],
     "fmi_vgg_tap_bwd_bf16": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "fmi_conv2d_thin_input_dgrad_bf16": [PD, vp, vp, vp, vp],
+    "fmi_vgg_tap_fwd_f32": [vp, vp, vp, i32, i32, i32, i32, vp],
+    "fmi_vgg_tap_bwd_f32": [vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp],
     "fmi_resblock_tail_bf16": [vp] * 5 + [i32] * 5 + [f32, vp],
     "fmi_picnet_stem_tail_bf16": [vp] * 6 + [i32] * 5 + [f32, vp],
     "fmi_guided_attention_fwd_bf16": [vp] * 5 + [i32] * 5 + [vp],

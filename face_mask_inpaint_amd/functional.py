@@ -1976,6 +1976,174 @@ def vgg_trunk_bf16(x, packs, blocks=(2, 2, 3, 3)):
     return _vgg_trunk_fwd(x, packs, tuple(blocks))[0]
 
 
+# ---- fp32 VGG16 trunk of VGGLoss: the convolutions are the entries (and descriptors) _Conv2d runs; what one autograd node for the whole
+# trunk removes is the work around them at the taps (csrc/vgg_f32.hip) and the second launch per layer for the target batch. ----
+_PLAN_FLAGS_P3 = 0x1 | 0x2 | 0x4 | 0x20 | 0x40 | 0x80 | 0x100  # FMI_F32_PLAN_*: aligned operands, d->x3 and d->w3 given and aligned
+_PLAN_FLAG_MASK = 0x1000
+
+
+def _dgrad_reads_f32(d, masked: bool) -> bool:
+    """does the adjoint fmi_conv2d_dgrad_f32 / _masked_f32 launches for d, given the piece images of both operands, still read the fp32
+    gradient?  Routes 3 and 6 of fmi_conv2d_f32_plan (GEMM / tap-reuse 3x3 on piece images) gather from the piece image only."""
+    out = (C.c_int * 44)()
+    rc = _L().conv2d_f32_plan(C.byref(d), 1, _PLAN_FLAGS_P3 | (_PLAN_FLAG_MASK if masked else 0), out)
+    if rc != 0 or out[2] != 0 or not 1 <= out[1] <= 4:
+        return True
+    return any(out[4 + 10 * p] not in (3, 6) for p in range(out[1]))
+
+
+def vgg_trunk_f32_ok(pws: Sequence[PackedWeight], blocks) -> bool:
+    """do the tap passes take the widths of this trunk (C % 4 == 0 at every tap)?  Host only; a trunk they refuse keeps the composed ops"""
+    ends = [sum(blocks[:bi + 1]) - 1 for bi in range(len(blocks))]
+    return all(pw.kh == 3 and pw.kw == 3 for pw in pws) and all(pws[e].rows % 4 == 0 for e in ends)
+
+
+def _vgg_conv_fwd_f32(hmap, h3, pw, bias):
+    """relu(conv3x3(hmap) + bias) as _Conv2d.forward launches it; h3: hmap's piece image where p3_wanted, else None"""
+    n, h, w, c = hmap.shape
+    k = pw.wf.shape[2]
+    d, _, _ = conv_desc(n, h, w, c, k, 3, 3, 1, 1, w3=pw.w3[0], x3=h3)
+    a = torch.empty((n, h, w, k), device=hmap.device, dtype=torch.float32)
+    with _prof(f"conv_fwd|{n}x{h}x{w} {c}->{k} k3s1", 2.0 * n * h * w * k * c * 9):
+        _L().conv2d_fwd_f32(C.byref(d), _p(hmap), _p(pw.wf), _p(bias), None, _p(a), ACT_RELU, 1, 0, _st())
+    return a
+
+
+def _vgg_wants3(pw, pixels, adjoint=False):
+    """_Conv2d's rule for cutting the activation operand's pieces (forward: of x, adjoint: of dy)"""
+    if adjoint:
+        return pw.w3[1] is not None and pw.rows % 16 == 0 and p3_wanted(pixels, pw.rows, pw.C, 9)
+    return pw.w3[0] is not None and pw.C % 16 == 0 and p3_wanted(pixels, pw.C, pw.rows, 9)
+
+
+def _vgg_trunk_fwd_f32(x, convs, blocks):
+    """the activated map of every convolution; the last one of each block is that block's tap"""
+    lib = _L()
+    acts, li, hmap, h3 = [], 0, x, None
+    for bi, nconv in enumerate(blocks):
+        for _ in range(nconv):
+            pw, bias = convs[li]
+            n, h, w, c = hmap.shape
+            src = hmap if h3 is None and _vgg_wants3(pw, n * h * w) else None
+            if src is not None:
+                h3 = p3_of(src)
+            hmap, h3 = _vgg_conv_fwd_f32(hmap, h3, pw, bias), None
+            if src is not None:
+                src._fmi_p3 = None  # frozen weights: no weight gradient will ask for these pieces, the saved map does not keep them alive
+            acts.append(hmap)
+            li += 1
+        if bi + 1 < len(blocks):
+            n, h, w, c = hmap.shape
+            pooled = torch.empty((n, h // 2, w // 2, c), device=x.device, dtype=torch.float32)
+            if _vgg_wants3(convs[li][0], pooled.numel() // c):
+                h3 = torch.empty(pooled.numel() * 3, device=x.device, dtype=torch.bfloat16)
+            with _prof(f"vgg_tap_fwd_f32|{n}x{h}x{w}x{c}" + ("" if h3 is None else " +pieces"), 0.0):
+                lib.vgg_tap_fwd_f32(_p(hmap), _p(pooled), None if h3 is None else C.c_void_p(h3.data_ptr()), n, h, w, c, _st())
+            hmap = pooled
+    return acts
+
+
+def _vgg_trunk_f32_taps(x, y, convs, blocks, nslice, merge):
+    """(the activated maps the backward needs, the taps of x as nslice batch slices per block, the taps of y)"""
+    n = x.shape[0]
+    if y is not None and merge:
+        acts = _vgg_trunk_fwd_f32(torch.cat([x, y], 0), convs, blocks)
+        yacts = [a[n:] for a in acts]
+    else:
+        acts = _vgg_trunk_fwd_f32(x, convs, blocks)
+        yacts = _vgg_trunk_fwd_f32(y, convs, blocks) if y is not None else None
+    ends = [sum(blocks[:bi + 1]) - 1 for bi in range(len(blocks))]
+    xs = [s for e in ends for s in (acts[e][:n].split(n // nslice, 0) if nslice > 1 else (acts[e][:n],))]
+    return acts, xs, ([] if yacts is None else [yacts[e] for e in ends])
+
+
+class _VggTrunkF32(torch.autograd.Function):
+    """x, y fp32 [N, H, W, 3] (resized, normalised; y None: no target) -> per block the tap of x as nslice batch slices (views), then the
+    four taps of y (not differentiable).  Keeps the activated maps; the backward is per block one tap pass (the slices' gradients, the
+    un-pooled gradient of the next block, the last ReLU's mask and the adjoint's pieces in one) and the chain of masked adjoints, on the x
+    images only.  A slice nobody used arrives without a gradient and is neither filled nor read; the blocks behind the last tap that has
+    one are skipped whole."""
+
+    @staticmethod
+    def forward(ctx, x, y, convs, blocks, nslice, merge):
+        acts, xs, ys = _vgg_trunk_f32_taps(x, y, convs, blocks, nslice, merge)
+        ctx.save_for_backward(*acts)
+        ctx.convs, ctx.blocks, ctx.nslice, ctx.n = convs, blocks, nslice, x.shape[0]
+        ctx.set_materialize_grads(False)  # an unused slice arrives as None, not as a freshly zero-filled tensor
+        ctx.mark_non_differentiable(*ys)
+        return tuple(xs) + tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        lib = _L()
+        acts, convs, blocks, ns, n = ctx.saved_tensors, ctx.convs, ctx.blocks, ctx.nslice, ctx.n
+        first = [sum(blocks[:bi]) for bi in range(len(blocks))]  # index of each block's first convolution
+        gpool = None
+        for bi in reversed(range(len(blocks))):
+            last = first[bi] + blocks[bi] - 1
+            a = acts[last][:n]
+            _, h, w, k = a.shape
+            gs = [None if g is None else g.contiguous() for g in grads[bi * ns:(bi + 1) * ns]]
+            if gpool is None and all(g is None for g in gs):
+                continue
+            _chk(*gs)
+            if any(g is not None and g.data_ptr() % 16 for g in gs):  # never from the allocator: one aligned tensor instead
+                gs = [torch.cat([torch.zeros_like(a[:n // ns]) if g is None else g for g in gs], 0)]
+            pw = convs[last][0]
+            want3 = _vgg_wants3(pw, n * h * w, adjoint=True)
+            dy3 = torch.empty(a.numel() * 3, device=a.device, dtype=torch.bfloat16) if want3 else None
+            d, _, _ = conv_desc(n, h, w, pw.C, k, 3, 3, 1, 1, w3=pw.w3[1], x3=dy3)
+            # the adjoint on piece images gathers from the pieces alone: the fp32 gradient is then not written (a, an in-bounds map of its
+            # shape, stands in for the operand the entry insists on)
+            gy = torch.empty_like(a) if (dy3 is None or _dgrad_reads_f32(d, blocks[bi] > 1)) else None
+            ptrs = (C.c_void_p * len(gs))(*[None if g is None else g.data_ptr() for g in gs])
+            with _prof(f"vgg_tap_bwd_f32|{n}x{h}x{w}x{k}" + ("" if gpool is None else " +unpool") + ("" if dy3 is None else " +pieces"), 0.0):
+                lib.vgg_tap_bwd_f32(_p(a), ptrs, len(gs), n // len(gs), _p(gpool), _p(gy), None if dy3 is None else C.c_void_p(dy3.data_ptr()),
+                                    n, h, w, k, _st())
+            gy3 = dy3
+            for li in range(last, first[bi] - 1, -1):
+                pw = convs[li][0]
+                k, c = pw.rows, pw.C
+                if li < last:
+                    gy3 = p3_of(gy) if _vgg_wants3(pw, n * h * w, adjoint=True) else None
+                    d, _, _ = conv_desc(n, h, w, c, k, 3, 3, 1, 1, w3=pw.w3[1], x3=gy3)
+                gx = torch.empty((n, h, w, c), device=a.device, dtype=torch.float32)
+                with _prof(f"conv_dgrad|{n}x{h}x{w} {c}->{k} k3s1", 2.0 * n * h * w * k * c * 9):
+                    if li > first[bi]:  # its input is the previous convolution's ReLU output: that mask in the adjoint's epilogue
+                        lib.conv2d_dgrad_masked_f32(C.byref(d), _p(a if gy is None else gy), _p(pw.wt), _p(acts[li - 1][:n]), 0.0, _p(gx), _st())
+                    else:
+                        lib.conv2d_dgrad_f32(C.byref(d), _p(a if gy is None else gy), _p(pw.wt), None, None, _p(gx), 1, 0, _st())
+                gy = gx
+            gpool = gy
+        return gpool, None, None, None, None, None  # None: no tap carried a gradient
+
+
+def vgg_trunk_f32(x, y, convs, blocks=(2, 2, 3, 3), nslice=1, merge=True):
+    """the fp32 VGG16 trunk on the NHWC images x (with gradient) and y (without; may be None): (taps of x, taps of y), four each.  convs:
+    (PackedWeight, bias) per convolution, frozen; blocks: convolutions per block.  nslice > 1: every tap of x comes as a tuple of nslice
+    batch slices, whose gradients enter the backward as they are (no cat, no fill for an unused one).  merge: x and y are stacked at the
+    3-channel input and every layer is ONE launch over 2N images (profiles/vgg_f32_trunk.txt; False: the N-image launches of _Conv2d).
+    Needs vgg_trunk_f32_ok; under no_grad nothing is kept."""
+    _chk(x, y)
+    blocks = tuple(blocks)
+    if len(convs) != sum(blocks):
+        raise FmiError(f"the fp32 VGG trunk has {sum(blocks)} convolutions, got {len(convs)}")
+    if not vgg_trunk_f32_ok([pw for pw, _ in convs], blocks):
+        raise FmiError("the fp32 VGG trunk needs 3 x 3 convolutions and tap widths that are multiples of 4")
+    if not 1 <= nslice <= 4 or x.shape[0] % nslice or (y is not None and y.shape != x.shape):
+        raise FmiError(f"the fp32 VGG trunk: batch {x.shape[0]} in {nslice} slices (1..4), target {None if y is None else tuple(y.shape)}")
+    merge = bool(merge) and y is not None
+    nb = len(blocks)
+    if torch.is_grad_enabled() and x.requires_grad:
+        out = _VggTrunkF32.apply(x, y, tuple(convs), blocks, nslice, merge)
+    else:
+        with torch.no_grad():
+            _, xs, ys = _vgg_trunk_f32_taps(x, y, tuple(convs), blocks, nslice, merge)
+        out = tuple(xs) + tuple(ys)
+    xs = [out[bi] if nslice == 1 else tuple(out[bi * nslice:(bi + 1) * nslice]) for bi in range(nb)]
+    return xs, list(out[nb * nslice:])
+
+
 class _Resize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, oh, ow, mean, std):

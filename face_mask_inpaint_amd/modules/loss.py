@@ -101,11 +101,17 @@ class VGGLoss(torch.nn.Module):
                 prev_conv = True
         return x
 
-    def _taps16(self, x, y):
-        """the bf16 trunk: (taps of x with gradient, taps of y without), four fp32 NHWC maps each, or (None, None) for the fp32 trunk"""
-        if self.feature_dtype != torch.bfloat16:
-            return None, None
+    def _taps16(self, x, y, nslice=1):
+        """the one-node trunks: (taps of x with gradient, taps of y without), four fp32 NHWC maps each -- the bf16 trunk, or the fp32 trunk
+        (FF.vgg_trunk_f32; with nslice > 1 every tap of x is a tuple of nslice batch slices) -- or (None, None) where the fp32 tap passes
+        refuse the widths and the composed ``_block`` runs"""
         blocks = tuple(sum(isinstance(m, nn.Conv2d) for m in bl) for bl in self.blocks)
+        if self.feature_dtype != torch.bfloat16:
+            convs = [m for bl in self.blocks for m in bl if isinstance(m, nn.Conv2d)]
+            pws = self._cache["pws"]
+            if not (x.is_cuda and x.dtype == torch.float32 and FF.vgg_trunk_f32_ok(pws, blocks)) or x.shape[0] % nslice or nslice > 4:
+                return None, None
+            return FF.vgg_trunk_f32(x, y, [(pw, c.bias) for pw, c in zip(pws, convs)], blocks, nslice=nslice)
         xt = FF.vgg_trunk_bf16(x, self._cache["packs16"], blocks)
         with torch.no_grad():
             yt = FF.vgg_trunk_bf16(y, self._cache["packs16"], blocks)
@@ -174,7 +180,8 @@ class VGGLoss(torch.nn.Module):
         k = len(loss_types)
         n = x.shape[0] // k
         losses = [0.0] * k
-        xt, yt = self._taps16(x, y)
+        xt, yt = self._taps16(x, y, nslice=k)
+        sliced = xt is not None and k > 1 and isinstance(xt[0], tuple)  # the fp32 trunk hands out the k slices of a tap themselves
         for i in range(len(self.blocks)):
             if xt is not None:
                 x, y = xt[i], yt[i]
@@ -182,9 +189,10 @@ class VGGLoss(torch.nn.Module):
                 x = self._block(i, x)
                 with torch.no_grad():
                     y = self._block(i, y)
-            _, h, w, c = x.shape
+            # contiguous batch slices; the backward of split is one cat, the fp32 trunk's slices go back as they are
+            xparts, yparts = x if sliced else x.split(n, 0), y.split(n, 0)
+            _, h, w, c = y.shape
             dim = c * h * w
-            xparts, yparts = x.split(n, 0), y.split(n, 0)  # contiguous batch slices; the backward of split is one cat
             for j, lossType in enumerate(loss_types):
                 xs, ys = xparts[j], yparts[j]
                 if lossType == "perceptual":

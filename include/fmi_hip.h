@@ -1083,6 +1083,22 @@ int fmi_vgg_tap_bwd_bf16(const uint16_t* a, const float* gtap, const uint16_t* g
  * two, at any map size (the streaming kernel of csrc/thinin.hip); dy16 16-byte aligned. */
 int fmi_conv2d_thin_input_dgrad_bf16(const fmi_conv_desc* d, const uint16_t* dy16, const float* wt, float* dx, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The tap passes of the fp32 VGG16 trunk (csrc/vgg_f32.hip; loss.py:54-65): the activated map a fp32 [N,H,W,C] of a block's last
+ * convolution is the tap itself.  No atomics, the same code in both modes of fmi_set_deterministic.  C % 4 == 0, pieces C % 16 == 0,
+ * 16-byte aligned pointers, else FMI_ERR_UNSUPPORTED (the caller keeps the composed kernels).
+ * ---------------------------------------------------------------------- */
+/* forward, one pass over a: pooled [N,H/2,W/2,C] = the 2x2 floor-mode max pool that opens the next block (fmi_maxpool2_f32's values) and,
+ * pooled3 not NULL, pooled's bf16 piece image, bit for bit what fmi_split3_f32 makes of pooled */
+int fmi_vgg_tap_fwd_f32(const float* a, float* pooled, void* pooled3, int N, int H, int W, int C, void* stream);
+/* backward, one pass: dy = a > 0 ? (gtap + unpool(gpool)) : 0.  gtap arrives as nslice (1..4) batch slices gslice[s] of rows_per_slice =
+ * N / nslice images each; a NULL slice is zeros and is neither filled nor read.  gpool [N,H/2,W/2,C] or NULL (last block: no add) goes
+ * to the FIRST maximum of its window in row-major order (strict >, fmi_maxpool2_bwd_f32's rule); rows and columns beyond 2 (H/2), 2 (W/2)
+ * receive nothing.  dy (fp32) and dy3 (dy's piece image, fmi_split3_f32's bits) are each optional -- a NULL one is not written -- and one
+ * of them is required.  Bit-equal to zeros / cat, add, fmi_maxpool2_bwd_f32, FMI_EW_RELU_BWD_OUT (and fmi_split3_f32) on these operands. */
+int fmi_vgg_tap_bwd_f32(const float* a, const float* const* gslice, int nslice, int rows_per_slice, const float* gpool, float* dy, void* dy3,
+                        int N, int H, int W, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
